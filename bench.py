@@ -5,6 +5,7 @@ bench.py -- headline benchmark of BASELINE.json: samples/sec, forward+backward, 
 (BASELINE.json configs[2]; configs[3] = the same with N GPUs, weak scaling, global batch 16*N).
 
     python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2|cfg5] [--precision f32|f16x3|f16|bf16]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: bench.py starts the N ranks itself (a child `python -m torch.distributed.run`, one rank
 per GPU over RCCL) BEFORE anything touches the GPU, relays rank 0's JSON line and the child's exit code.  Under an
@@ -16,13 +17,25 @@ Adam update -- nothing is skipped inside the timed region.  Inputs are synthetic
 HBM before timing starts; weights are random-init (reference init rules).
 
 Prints ONE JSON line (rank 0).  Besides the contract's keys it carries
+  roofline_step -- whole-step algorithmic FLOP/s and HBM-byte fractions (both named by north_star)
+  ranks         -- rccl_ranks (dist.get_world_size()), per-rank ms/step, gradient all-reduce ms/step (HIP events)
+
+A plain run sets up, warms up, times the K steps, [writes --dump-outputs], prints the line.  Everything else runs only
+with --full (each part can still be switched off there with its --no-* option):
   roofline      -- dominant kernel, achieved algorithmic TFLOP/s from HIP-event timing on the launch stream
                    against the dense MFMA peak of the arithmetic used (the path is MFMA-bound)
-  roofline_step -- whole-step algorithmic FLOP/s and HBM-byte fractions (both named by north_star)
-  kernels       -- per-kernel-class time / launches / achieved TFLOP/s
-  ranks         -- rccl_ranks (dist.get_world_size()), per-rank ms/step, gradient all-reduce ms/step (HIP events)
+  kernels       -- per-kernel-class time / launches / achieved TFLOP/s (HIP events around every launch of the timed steps;
+                   with a HIP graph: of as many eager steps after the timed region)
+  breakdown     -- forward-only and forward+backward times, measured after the timed region
+  split_precision -- cfg3 / f32 only: the same step in the f16x3 mode, measured after the timed region
   cpu_baseline  -- the CPU oracle (same ATen conv1d ops the reference calls) timed on this box's host cores
                    on a bounded sample of the same workload (rank 0, N=1 only)
+
+--dump-outputs DIR writes what the LAST timed step computed, as a caller of the step receives it (rank 0), before anything
+else runs: loss.npy (the scalar loss), output.npy (the model output), grad.npy (the flat, all-reduced parameter gradient),
+params.npy (the parameters after the optimizer update), all float32; an array of more than DUMP_SAMPLE elements is replaced by
+the same fixed, seeded sample of its flattened elements in every run.  Inputs and weights come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -46,6 +59,7 @@ SUSTAINED_NOTE = ("1600 TFLOP/s = what back-to-back v_mfma_f32_32x32x16_f16 issu
                   "streaming the operands from HBM beside it lowers the clock further (1.53 GHz in the same model)")
 PEAK_HBM_GBS = 8000.0           # HBM3E spec peak
 PROFILE_ROUND = "r03"
+DUMP_SAMPLE = 1 << 22           # float32 elements kept per dumped array: 16 MiB, the three large arrays stay under 64 MB together
 
 # BASELINE.json configs -> workloads.  cfg3 is the configuration the metric is quoted on; the others are parity-test
 # cases that can be timed with the same harness (their lines are committed under profiles/, they are not the headline).
@@ -81,18 +95,23 @@ def parse():
                     help="weights: the reference's init rules (default), or the same with the residual path conditioned like a "
                          "trained network (proj ~ I, conv1x1_residual x0.3; default for cfg5 in f16: 60 random-init blocks "
                          "amplify the residual stream by ~2^30, beyond any 16-bit format)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure the kernel table and roofline, the forward / forward+backward breakdown, "
+                         "the f16x3 second line (cfg3/f32) and the CPU baseline; a plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, output, gradient, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-second-line", action="store_true",
-                    help="cfg3/f32 only: skip the additional f16x3 measurement reported under \"split_precision\"")
+                    help="with --full, cfg3/f32 only: skip the additional f16x3 measurement reported under \"split_precision\"")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the step from a HIP graph (wavenet_speech_amd.GraphedStep: forward + backward + gradient gather in one "
                          "graph, the all-reduce eager, the optimizer in a second graph).  auto = on for cfg2, whose ~280 launches of "
                          "5-50 us take the host longer to issue than the GPU to run; off for the long-kernel configs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seq-len", type=int, default=None)
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the kernel table and the roofline object")
     ap.add_argument("--no-breakdown", action="store_true",
-                    help="skip the extra forward-only / forward+backward runs after the timed region (used when profiling, so "
-                         "that rocprofv3's per-kernel shares are those of the timed steps)")
+                    help="with --full: skip the extra forward-only / forward+backward runs after the timed region (used when "
+                         "profiling, so that rocprofv3's per-kernel shares are those of the timed steps)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     for k in ("channels", "cycles", "seq_len", "batch", "precision"):
@@ -308,6 +327,23 @@ def pmc_lookup(args, name, exact_kernel, column):
     return (total if hit else None), (os.path.relpath(path, ROOT) if hit else None)
 
 
+def dump_outputs(path, arrays):
+    """arrays: name -> device tensor.  Each is written as path/<name>.npy in float32, flattened; beyond DUMP_SAMPLE elements only a
+    fixed sample of them (seeded by the element count, sorted, the same in every run of the same arguments)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(n)).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.float().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        log("dumped %s: %d of %d elements" % (name, a.size, n))
+
+
 def main():
     args = parse()
     args.model = CONFIGS[args.config]["model"]
@@ -392,14 +428,18 @@ def main():
         opt = torch.optim.Adam(net.parameters(), lr=1e-4)
     sync = FlatGradAllReduce(net.parameters())
     ar_events = []
+    last = {}          # --dump-outputs: output and loss of the last timed step
 
     def forward():
         return net.forward_levels(levels) if levels is not None else net(x)
 
-    def step(timed=False):
+    def step(timed=False, keep=False):
         sync.zero()
         out = forward()
-        (out * cot).sum().backward()
+        loss = (out * cot).sum()
+        loss.backward()
+        if keep:
+            last["output"], last["loss"] = out.detach(), loss.detach()
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -436,11 +476,17 @@ def main():
         torch.cuda.synchronize()
         log("warm-up step %d done" % i)
     fence()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
+    dump = args.dump_outputs is not None and rank == 0
     if args.use_graph:
         # the timed steps are graph replays: the same launches as the eager step, issued by one host call.  Per-kernel HIP
         # events cannot be recorded inside a replay, so the kernel table comes from eager steps AFTER the timed region.
-        gstep = W.GraphedStep(lambda: (forward() * cot).sum(), net.parameters(), optimizer=opt, sync=sync, warmup=1)
+        def forward_kept():
+            out = forward()
+            if dump:
+                last["output"] = out.detach()      # the captured output: every replay rewrites it in place
+            return out
+        gstep = W.GraphedStep(lambda: (forward_kept() * cot).sum(), net.parameters(), optimizer=opt, sync=sync, warmup=1)
         for i in range(max(1, args.warmup)):
             graphed_step()
         fence()
@@ -451,17 +497,22 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0
         gstep.check()
+        last["loss"] = gstep.loss
     else:
         if timing:
             HF.profile_reset()
             HF.profile_enable(True)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step(timed=True)
+        for i in range(args.steps):
+            step(timed=True, keep=dump and i == args.steps - 1)
         fence()
         elapsed = time.perf_counter() - t0
     own_elapsed = elapsed
     log("timed %d steps: %.2f ms/step" % (args.steps, elapsed / args.steps * 1e3))
+    if dump:
+        dump_outputs(args.dump_outputs, {"loss": last["loss"], "output": last["output"], "grad": sync.flat,
+                                         "params": torch.cat([p.detach().reshape(-1) for p in net.parameters()])})
+    last.clear()
     kern = {}
     eager_ms = None
     if timing and args.use_graph:
@@ -501,12 +552,12 @@ def main():
         (forward() * cot).sum().backward()
 
     breakdown = {"peak_hbm_gib_allocated": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)}
-    if not args.no_breakdown:
+    if args.full and not args.no_breakdown:
         breakdown.update({"fwd_only_ms": round(median_ms(fwd_only), 2), "fwd_bwd_ms": round(median_ms(fwd_bwd), 2)})
         breakdown["fwd_bwd_samples_per_s_per_gpu"] = round(B / (breakdown["fwd_bwd_ms"] * 1e-3), 2)
     # ---- second, separately labelled measurement: the same step in the f16x3 mode (three-product fp16 split) --------
     second = None
-    if args.config == "cfg3" and args.precision == "f32" and not args.no_second_line:
+    if args.full and args.config == "cfg3" and args.precision == "f32" and not args.no_second_line:
         with torch.no_grad():
             y32 = forward()
         W.set_precision(net, "f16x3")
@@ -684,15 +735,17 @@ def main():
                   "grad_allreduce_payload_mb": round(sync.payload_bytes() / 1e6, 1)},
         "breakdown": breakdown, "roofline": roofline, "roofline_step": roofline_step, "kernels": kernels,
         "launch": ({"mode": "hipgraph", "note": "timed steps are replays of a captured HIP graph (forward + backward + gradient gather; "
-                    "all-reduce eager; optimizer in a second graph): the same kernels as the eager step, one host call.  The kernel "
-                    "table and the roofline object were timed with HIP events over the same number of EAGER steps after the timed region",
+                    "all-reduce eager; optimizer in a second graph): the same kernels as the eager step, one host call." +
+                    ("  The kernel table and the roofline object were timed with HIP events over the same number of EAGER steps "
+                     "after the timed region" if eager_ms is not None else ""),
                     "eager_ms_per_step": round(eager_ms, 2) if eager_ms is not None else None}
                    if args.use_graph else {"mode": "eager"}),
+        "full": args.full,
     }
     if second is not None:
         result["split_precision"] = second
     result["config"]["init"] = args.init
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         del net, opt, sync, x, cot
         torch.cuda.empty_cache()
         result["cpu_baseline"] = cpu_baseline(args)

@@ -1,12 +1,12 @@
 #!/bin/bash
 # One extra rocprofv3 counter pass over the bench (no trace options beside --pmc):
-#   bash tools/pmc_pass.sh <out name> "<counters>" [bench.py args]      -> gpurun_out/<round>/<out name>.csv (per-kernel averages)
+#   bash tools/pmc_pass.sh <out name> "<counters>" [bench.py args]      -> ${WN_OUT_DIR:-bench_out}/<round>/<out name>.csv (per-kernel averages)
 set -e
 NAME=$1; CTRS=$2; shift 2
 export TMPDIR=/tmp
-OUT=gpurun_out/${WN_ROUND:-r02}
+OUT=${WN_OUT_DIR:-bench_out}/${WN_ROUND:-r02}
 mkdir -p $OUT
-rocprofv3 --pmc $CTRS --output-format csv -d $OUT/pmc_$NAME -o pmc -- python3 bench.py --steps 1 --warmup 1 --no-breakdown --no-cpu-baseline "$@" \
+rocprofv3 --pmc $CTRS --output-format csv -d $OUT/pmc_$NAME -o pmc -- python3 bench.py --full --steps 1 --warmup 1 --no-breakdown --no-cpu-baseline "$@" \
     > $OUT/bench_under_pmc_$NAME.json 2> $OUT/pmc_$NAME.err
 python3 - $OUT/pmc_$NAME > $OUT/$NAME.csv <<'PY'
 import collections, csv, glob, os, sys
