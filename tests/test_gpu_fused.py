@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from oracle import wavenet_oracle as O
+from tests import halfref as R
 from wavenet_speech_amd import _lib
 from wavenet_speech_amd import functional as HF
 from wavenet_speech_amd.modules.block import ResidualBlock, StackState, run_stack
@@ -20,8 +21,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 # max-norm relative distance of two evaluations that round to the storage format at different points / in another order
 PAIR = {"bf16": 8e-3, "f16": 1e-3}      # observed: 2.7e-3 / 3.7e-4 (worst: dx)
-# distance from the fp32 oracle (the bounds of tests/test_gpu_half.py for the plain modes)
-LOOSE = {"f16": 2e-2, "bf16": 1.2e-1}
+# distance from the oracle: the rounding reference's predicate (tests/halfref.py, as in tests/test_gpu_half.py)
 
 
 class _Stack(nn.Module):
@@ -100,28 +100,31 @@ def test_fused_forward_equals_two_launch_form_and_oracle(precision, case, monkey
     assert "hfused_fwd_kernel" not in launched and launched.get("hgemm_kernel<gate>", 0) == len(dil), launched
     assert not any(k.startswith("hcol_kernel") for k in launched), launched     # (the two-launch form also runs dz / dx on hgemm_kernel)
 
-    # oracle (fp32, CPU)
-    xr = x.clone().requires_grad_(True)
-    _, s_ref = O.block_stack(xr, torch.zeros(B, out_dim, L), sd, net.layers, causal)
-    (s_ref * cot).sum().backward()
-
-    pair, loose = PAIR[precision], LOOSE[precision]
     e_pair = {"forward": O.rel_err(s1.cpu(), s0.cpu()), "inference": O.rel_err(s1i.cpu(), s0.cpu()), "dx": O.rel_err(dx1.cpu(), dx0.cpu())}
-    e_ref = {"forward": O.rel_err(s1.cpu(), s_ref.detach()), "inference": O.rel_err(s1i.cpu(), s_ref.detach()),
-             "dx": O.rel_err(dx1.cpu(), xr.grad)}
     for k in g0:
         assert (g0[k] is None) == (g1[k] is None), k
-        ref = sd[k].grad
-        if g0[k] is None:
-            continue
-        e_pair[k] = O.rel_err(g1[k].cpu(), g0[k].cpu())
-        if ref is not None:
-            e_ref[k] = O.rel_err(g1[k].cpu(), ref)
-    wp, wr = max(e_pair, key=e_pair.get), max(e_ref, key=e_ref.get)
-    print("%s %s: fused vs two-launch: forward %.2e, worst %s %.2e | vs oracle: forward %.2e, worst %s %.2e"
-          % (precision, case, e_pair["forward"], wp, e_pair[wp], e_ref["forward"], wr, e_ref[wr]))
-    assert e_pair[wp] <= pair, (wp, e_pair[wp])
-    assert e_ref[wr] <= loose, (wr, e_ref[wr])
+        if g0[k] is not None:
+            e_pair[k] = O.rel_err(g1[k].cpu(), g0[k].cpu())
+    wp = max(e_pair, key=e_pair.get)
+    print("%s %s: fused vs two-launch: forward %.2e, worst %s %.2e" % (precision, case, e_pair["forward"], wp, e_pair[wp]))
+    assert e_pair[wp] <= PAIR[precision], (wp, e_pair[wp])
+    hip = {"forward": s1.cpu(), "dx0": dx1.cpu()}
+    hip.update({k: g.cpu() for k, g in g1.items() if g is not None})
+    _check_vs_rounding_reference("%s %s" % (precision, case), hip, x, cot, sd, net.layers, causal, precision)
+    _check_vs_rounding_reference("%s %s inference" % (precision, case), {"forward": s1i.cpu()}, x, cot, sd, net.layers, causal,
+                                 precision)
+
+
+def _check_vs_rounding_reference(label, hip, x, cot, sd, layers, causal, precision, input_grad=True):
+    """skips_sum of run_stack (dense, its cotangent stored on the way back) against tests/halfref.py"""
+    prefixes = [("convolutions.%d." % l, "bottlenecks.%d." % l) for l in range(len(layers))]
+    fn = lambda xx, s, fmt: R.stack_call(xx, s, layers, causal, fmt, prefixes)
+    res = {}
+    for fmt in (None, precision):
+        y, g = R.run(fn, [x.clone().requires_grad_(input_grad)], sd, cot, fmt)
+        g["forward"] = y
+        res[fmt] = {k: g[k] for k in hip}
+    return R.check(label, hip, res[precision], res[None])
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f16"])
@@ -291,3 +294,29 @@ def test_series_convs_and_masked_dx_column_owner_equal_tiled(precision, model, m
         assert (g0[k] is None) == (g1[k] is None), k
         if g0[k] is not None:
             assert O.rel_err(g1[k].cpu(), g0[k].cpu()) <= PAIR[precision], k
+
+
+@pytest.mark.parametrize("pair", ["1", "0"])
+@pytest.mark.parametrize("precision", ["bf16", "f16"])
+def test_run_stack_on_data_without_gradient(precision, pair, monkeypatch):
+    """run_stack on plain data (the stack's input needs no gradient) at the bottom of a paired chain and without pairing: the
+    parameters' gradients against the rounding reference"""
+    monkeypatch.setenv("WN_COL_PAIR", pair)
+    c, dil, causal, B, L = 64, (1, 2, 4), True, 2, 300
+    net = _Stack(c, dil, c, causal, seed=12)
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    torch.manual_seed(13)
+    x, cot = torch.randn(B, c, L), torch.randn(B, c, L)
+    net = net.to(DEV)
+    net.stack_state.precision = precision
+    HF.profile_reset()
+    HF.profile_enable(True)
+    s = net(x.to(DEV))
+    (s * cot.to(DEV)).sum().backward()
+    HF.profile_enable(False)
+    launched = {k: v[1] for k, v in HF.profile_read().items() if v[1]}
+    assert launched.get("hcol2_kernel<dx+dz>", 0) == (len(dil) - 1 if pair == "1" else 0), launched
+    hip = {"forward": s.detach().cpu()}
+    hip.update({k: p.grad.cpu() for k, p in net.named_parameters() if p.grad is not None})
+    _check_vs_rounding_reference("%s no input gradient pair=%s" % (precision, pair), hip, x, cot, sd, net.layers, causal, precision,
+                                 input_grad=False)

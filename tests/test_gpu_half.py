@@ -1,45 +1,166 @@
 """GPU parity of the half-precision-MFMA modes of the residual stack (wavenet_speech_amd.set_precision).
 
 f16x3 (three-product fp16 split, fp32 accumulate) is held to the SAME 1e-4 bar as the exact-fp32 path, forward and every
-gradient, on the golden fixtures and against the oracle.  Plain f16 / bf16 (BASELINE configs[4] / configs[1]) are checked
-against the oracle with the error their storage format implies; the measured errors are printed."""
+gradient, on the golden fixtures and against the oracle.  Plain f16 / bf16 (BASELINE configs[4] / configs[1]) are held to the
+error their storage format implies: tests/halfref.py evaluates the model in fp64, rounding every tensor the half path stores, and
+every compared tensor must satisfy e_hip <= KAPPA e_fmt + FLOOR in max-norm and RMS (e_hip: the HIP result's distance from exact
+fp64, e_fmt: the rounding reference's).  The measured distances are printed."""
 import pytest
 import torch
 
 import wavenet_speech_amd as W
 from oracle import wavenet_oracle as O
 from tests import goldenio
+from tests import halfref as R
+from wavenet_speech_amd import functional as HF
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-4
-LOOSE = {"f16": 2e-2, "bf16": 1.2e-1}     # max-norm relative error bounds of the plain modes on the small nets below
+PLAIN = ("f16", "bf16")
 
 
-def _cond_wavenet(c, layers, in_dim=None, seed=0):
+def _cond_wavenet(c, layers, in_dim=None, seed=0, out_dim=None):
     from wavenet_speech_amd.modules.wavenet import WaveNet
     torch.manual_seed(seed)
-    net = WaveNet(in_dim or c, 2, layers, c, softmax=False)
+    net = WaveNet(in_dim or c, 2, layers, out_dim or c, softmax=False)
+    _condition(net)
+    return net
+
+
+def _condition(net):
+    """noisy biases and a conditioned residual path, as in a trained network"""
     with torch.no_grad():
         for p in net.parameters():
             if p.dim() == 1:
                 p.add_(0.05 * torch.randn(p.shape))
-        for blk in net.convolutions:
+        blocks = list(net.convolutions) + ([net.input_block] if hasattr(net, "input_block") else [])
+        for blk in blocks:
             blk.residual_proj.weight.copy_(torch.eye(blk.out_channels, blk.in_channels)
                                            + 0.02 * torch.randn(blk.out_channels, blk.in_channels))
             blk.conv1x1_residual.weight.mul_(0.3)
     return net
 
 
-def _run(net, x, cot, layers, precision, tol, replay_slopes=True):
+def _cond_rawctc(c, layers, causal, seed, feature_kwidth=3, out_dim=None, input_kwidth=2, slope=0.01):
+    from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
+    torch.manual_seed(seed)
+    net = RawCTCNet(c, feature_kwidth, 5, layers, out_dim or c, input_kernel_size=input_kwidth, softmax=False, causal=causal)
+    if slope != 0.01:
+        for m in net.modules():
+            if isinstance(m, torch.nn.LeakyReLU):
+                m.negative_slope = slope
+    return _condition(net)
+
+
+def _half_ref(net, precision, slopes, layers_override=None):
+    """fn(x, sd, fmt) of tests/halfref.py for `net` as the half path runs it (layers_override: other (ci, co, k, d) per block)"""
+    from wavenet_speech_amd.modules.block import fusable_head
+    from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
+    if isinstance(net, RawCTCNet):
+        fused = fusable_head(net.output_block, precision) is not None
+        layers = layers_override or [(b.in_channels, b.out_channels, b.kernel_width, b.dilation) for b in net.convolutions]
+        ib = net.input_block
+        return lambda x, sd, fmt: R.raw_ctcnet(x, sd, layers, net.feature_layer[0].kernel_size[0], fmt, causal=net.causal,
+                                               input_dilation=ib.dilation, input_kwidth=ib.kernel_width, slopes=slopes,
+                                               fused=fused)
+    fused = fusable_head(net.output_stack, precision) is not None
+    layers = layers_override or [(b.in_channels, b.out_channels, b.kernel_width, b.dilation) for b in net.convolutions]
+    return lambda x, sd, fmt: R.wavenet(x, sd, layers, fmt, slopes=slopes, fused_head=fused)
+
+
+def _launched():
+    return {k: v[1] for k, v in HF.profile_read().items() if v[1]}
+
+
+def _run(net, x, cot, layers, precision, tol=None, replay_slopes=True, input_grad=True, kernels=None, label="", mutants=None):
+    """forward and backward of `net` on the GPU in `precision` against the oracle: f16x3 at `tol` (fp32 oracle), the plain modes
+    against tests/halfref.py (predicate e_hip <= KAPPA e_fmt + FLOOR).  kernels(launched) asserts the kernels the case exists to
+    exercise (HF.profile_read() of the GPU forward and backward).  mutants: {name: (state dict, layers or None)} -- references
+    built from altered parameters, each of which the predicate must REJECT for the unaltered GPU result.
+    The LeakyReLU pattern replayed by the references is the GPU's.  f16x3: O.capture_leaky_slopes.  Plain modes: one extra forward
+    on the training path (the one the measured forward takes) with the output block outside the stack function (WN_SERIES_HEAD=0:
+    its convs store the same pre-activations, its LeakyReLUs become modules whose inputs a hook reads); a fused feature layer stays
+    fused there -- run outside, it would round the signal and its weights where the fused layer does not -- and its own masks are
+    recorded by the rounding reference (halfref.Pattern), whose rounding is the GPU's."""
     sd = {k: v.clone().requires_grad_(True) for k, v in net.state_dict().items()}
+    frozen = {k for k, p in net.named_parameters() if not p.requires_grad}
     net = net.to(DEV)
     W.set_precision(net, precision)
-    slopes, remove = O.capture_leaky_slopes(net)
-    xg = x.to(DEV).requires_grad_(True)
-    y1 = net(xg)
-    remove()
-    (y1 * cot.to(DEV)).sum().backward()
+    xg = x.to(DEV).requires_grad_(input_grad)
+    front = None
+    if precision in PLAIN and hasattr(net, "feature_layer"):
+        from wavenet_speech_amd.modules.block import fusable_front
+        front = fusable_front(net.feature_layer, precision, xg)
+    if precision not in PLAIN:
+        slopes, remove = O.capture_leaky_slopes(net)
+    else:
+        import os
+        slopes, handles = {}, []
+        for name, mod in net.named_modules():
+            if isinstance(mod, torch.nn.LeakyReLU):
+                def hook(_m, inp, name=name, ns=mod.negative_slope):
+                    xin = inp[0].detach()
+                    slopes[name] = torch.where(xin > 0, torch.ones_like(xin), torch.full_like(xin, ns)).cpu()
+                handles.append(mod.register_forward_pre_hook(hook))
+        old = os.environ.get("WN_SERIES_HEAD")
+        os.environ["WN_SERIES_HEAD"] = "0"
+        try:
+            net(xg.detach().requires_grad_(input_grad))
+        finally:
+            if old is None:
+                del os.environ["WN_SERIES_HEAD"]
+            else:
+                os.environ["WN_SERIES_HEAD"] = old
+            for h in handles:
+                h.remove()
+        remove = lambda: None
+    HF.profile_reset()
+    HF.profile_enable(True)
+    try:
+        y1 = net(xg)
+        remove()
+        (y1 * cot.to(DEV)).sum().backward()
+        torch.cuda.synchronize()
+    finally:
+        HF.profile_enable(False)
+    launched = _launched()
+    if kernels is not None:
+        assert kernels(launched), launched
+    if precision in PLAIN:
+        hip = {"forward": y1.detach().cpu()}
+        if input_grad:
+            hip["dx0"] = xg.grad.cpu()
+        for k, p in net.named_parameters():
+            if k in frozen or p.grad is None:     # (the last block's residual path does not reach the output)
+                continue
+            hip[k] = p.grad.cpu()
+        xr = x.clone().requires_grad_(input_grad)
+        if front is not None:
+            head = dict(slopes)
+            slopes = R.Pattern({n: m.negative_slope for n, m in net.named_modules() if isinstance(m, torch.nn.LeakyReLU)})
+            slopes.update(head)
+            with torch.no_grad():
+                _half_ref(net, precision, slopes)(xr.detach().double(), {k: v.detach().double() for k, v in sd.items()}, precision)
+
+        def refs(base, lay):
+            fn = _half_ref(net, precision, slopes if replay_slopes else None, lay)
+            res = {}
+            for fmt in (None, precision):
+                y, g = R.run(fn, [xr], base, cot, fmt)
+                assert set(g) - set(frozen) == set(hip) - {"forward"}, sorted(set(g) ^ set(hip))   # the same tensors get gradients
+                g["forward"] = y
+                res[fmt] = {k: g[k] for k in hip}
+            return res
+        res = refs(sd, None)
+        out = R.check("%s%s" % (precision, label), hip, res[precision], res[None])
+        for name, (sd2, lay2) in (mutants or {}).items():
+            r2 = refs(sd2, lay2)
+            got = R.compare("%s%s mutant %s" % (precision, label, name), hip, r2[precision], r2[None], quiet=True)
+            bad = sorted(k for k, v in got.items() if not v[2])
+            print("%s%s mutant %s: rejected by %d of %d tensors, e.g. %s" % (precision, label, name, len(bad), len(got), bad[:3]))
+            assert bad, "mutant %s passes the predicate" % name
+        return out
     xr = x.clone().requires_grad_(True)
     y0 = O.wavenet(xr, sd, layers, False, slopes=slopes if replay_slopes else None)
     (y0 * cot).sum().backward()
@@ -103,8 +224,7 @@ def test_plain_half_modes_vs_oracle(precision):
     net = _cond_wavenet(c, layers, seed=5)
     g = torch.Generator().manual_seed(6)
     x, cot = torch.randn(B, c, L, generator=g), torch.randn(B, c, L, generator=g)
-    errs = _run(net, x, cot, layers, precision, LOOSE[precision])
-    print(precision, {k: "%.1e" % v for k, v in sorted(errs.items(), key=lambda kv: -kv[1])[:6]})
+    _run(net, x, cot, layers, precision)
 
 
 @pytest.mark.parametrize("precision,c,dims,L,B", [("f16x3", 256, (1, 2, 64), 384, 2), ("f16x3", 128, (1, 3), 256, 3),
@@ -120,7 +240,7 @@ def test_full_tile_shapes_take_the_16x16x32_gemm(precision, c, dims, L, B):
     net = _cond_wavenet(c, layers, seed=c + L)
     g = torch.Generator().manual_seed(L + B)
     x, cot = torch.randn(B, c, L, generator=g), torch.randn(B, c, L, generator=g)
-    _run(net, x, cot, layers, precision, TOL if precision == "f16x3" else LOOSE[precision])
+    _run(net, x, cot, layers, precision, TOL if precision == "f16x3" else None)
     # inference (no saved tanh / sigmoid, per-block skip accumulation on the other kernel) agrees with the training forward
     net = net.to(DEV)
     with torch.no_grad():
@@ -248,12 +368,14 @@ def test_cfg2_bf16_full_batch():
     cot = torch.randn(32, 5, 4098, generator=g).to(DEV)
     y = _properties(net, x, cot, None, 16, causal_prefix=False, additivity_tol=2e-2)
     assert tuple(y.shape) == (32, 5, 4098)
-    sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
-    with torch.no_grad():
-        y0 = O.raw_ctcnet(x[7:8].cpu(), sd, layers, 3, 1, False, False, False, impl="aten")
-    err = O.rel_err(y[7:8].cpu(), y0)
-    print("cfg2 bf16 forward error vs oracle: %.2e" % err)
-    assert err < 0.1
+    # two utterances of the same model, forward and every gradient, against the rounding reference (tests/halfref.py)
+    import copy
+    small = copy.deepcopy(net).cpu()
+    for p in small.parameters():
+        p.grad = None
+    x2, cot2 = x[6:8].cpu(), cot[6:8].cpu()
+    _run(small, x2, cot2, layers, "bf16", input_grad=False, label=" cfg2 B=2 L=4096",
+         kernels=lambda k: k.get("hfused_fwd_kernel", 0) > 0 and k.get("hcol2_kernel<dx+dz>", 0) > 0)
 
 
 def test_cfg5_f16_full_depth_and_length():
@@ -268,15 +390,19 @@ def test_cfg5_f16_full_depth_and_length():
     x = torch.randn(B, c, L, generator=g).to(DEV)
     cot = torch.randn(B, c, L, generator=g).to(DEV)
     _properties(net, x, cot, 8192, 1, causal_prefix=True, additivity_tol=2e-2)
-    # all 60 blocks against the oracle on a shorter utterance
-    sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
-    xs = x[:1, :, :4000].contiguous()
-    with torch.no_grad():
-        y1 = net(xs).cpu()
-        y0 = O.wavenet(xs.cpu(), sd, layers, False, impl="aten")
-    err = O.rel_err(y1, y0)
-    print("cfg5 f16 forward error vs oracle (60 blocks): %.2e" % err)
-    assert err < 5e-2
+
+
+def test_cfg5_f16_full_depth_gradients_vs_rounding_reference():
+    """all 60 blocks of configs[4] (512 ch, f16) on one utterance of 3000 steps: forward, dx and every parameter gradient against
+    the rounding reference (tests/halfref.py)"""
+    from tests.test_gpu_fullsize import _layers, _wavenet
+    c, L = 512, 3000
+    layers = _layers(c, 6)
+    net = _wavenet(c, layers, seed=23)
+    g = torch.Generator().manual_seed(24)
+    x, cot = torch.randn(1, c, L, generator=g), torch.randn(1, c, L, generator=g)
+    _run(net, x, cot, layers, "f16", label=" cfg5 60 blocks L=3000",
+         kernels=lambda k: "hfused_fwd_kernel" not in k and k.get("hgemm_kernel<gate>", 0) >= 60)
 
 
 def test_f16x3_wide_stack_multi_slab():
@@ -312,3 +438,157 @@ def test_grad_scale_kernel_matches_the_torch_expression():
         want = torch.exp2(torch.floor(torch.log2(FH.GRAD_TARGET / amax)).clamp(-100.0, 100.0))
         assert float(dyn) == float(want), (n, mag, float(dyn), float(want))
         assert float(inv) == 1.0 / float(want)
+
+
+# ---- plain bf16 / f16 across the half-mode dispatch, against the rounding reference (tests/halfref.py) ----------------------------
+
+def _all_k3_on_hgemm(n):
+    return lambda k: "hfused_fwd_kernel" not in k and k.get("hgemm_kernel<gate>", 0) >= n and k.get("hgemm_kernel<dz,dgate>", 0) >= n \
+        and not any(n_.startswith("hcol_kernel<dz") or n_.startswith("hcol2") for n_ in k) and "hwgrad_kernel" in k
+
+
+def _fused_and_hgemm(k):
+    return k.get("hfused_fwd_kernel", 0) > 0 and k.get("hgemm_kernel<gate>", 0) > 0 and "hwgrad_kernel" in k
+
+
+def _column_owner(k):
+    return k.get("hfused_fwd_kernel", 0) > 0 and (k.get("hcol2_kernel<dx+dz>", 0) > 0 or k.get("hcol_kernel<dz,dgate>", 0) > 0)
+
+
+def _notebook_layers(c):
+    """the reference's training model (RawCTCNet on Gaussian Model (Train), cell 5): 21 blocks of k=2 then 21 of k=3"""
+    dil = [1, 2, 4, 8, 16, 32, 64] * 3
+    return [(c, c, 2, d) for d in dil] + [(c, c, 3, d) for d in dil]
+
+
+WAVENET_CASES = {  # layers, skip rows, B, L, kernels
+    "k3_32_short_utts_d_ge_L": ([(32, 32, 3, 1), (32, 32, 3, 8)], 32, 6, 5, _all_k3_on_hgemm(2)),
+    "k3_64_ragged": ([(64, 64, 3, d) for d in (1, 2, 4)], 64, 2, 301, _all_k3_on_hgemm(3)),
+    "k3_128_d_ge_L": ([(128, 128, 3, d) for d in (1, 200)], 128, 2, 150, _all_k3_on_hgemm(2)),
+    "k3_256_skip128": ([(256, 256, 3, d) for d in (1, 4)], 128, 2, 257, _all_k3_on_hgemm(2)),
+    "k3_512_skip256": ([(512, 512, 3, d) for d in (2, 1)], 256, 1, 300, _all_k3_on_hgemm(2)),
+    "k3_256_short_utts_d_ge_L": ([(256, 256, 3, 1), (256, 256, 3, 16)], 128, 5, 9, _all_k3_on_hgemm(2)),
+    "k3_512_d_ge_L_ragged": ([(512, 512, 3, d) for d in (300, 2)], 512, 2, 130, _all_k3_on_hgemm(2)),
+    "mixed_k_alternating_64": ([(64, 64, 2 + (i % 2), 2 ** (i % 5)) for i in range(12)], 64, 2, 130, _fused_and_hgemm),
+    "mixed_widths_64_256_64": ([(64, 64, 2, 1), (64, 256, 3, 2), (256, 256, 2, 4), (256, 64, 2, 1), (64, 64, 2, 8)], 64, 2, 200,
+                               _fused_and_hgemm),
+    "narrow_under_wide": ([(64, 64, 2, 1), (64, 256, 2, 2)] + [(256, 256, 2, 2 ** i) for i in range(2, 8)], 64, 1, 160,
+                          _fused_and_hgemm),
+    # (a skip path wider than the blocks keeps dz / dx on the tiled kernels)
+    "chain_96_skip128": ([(96, 96, 2, d) for d in (1, 2, 4)], 128, 2, 300,
+                         lambda k: k.get("hfused_fwd_kernel", 0) > 0 and k.get("hgemm_kernel<dz,dgate>", 0) >= 3),
+    "chain_128": ([(128, 128, 2, d) for d in (1, 2, 4, 8)], 128, 2, 300, _column_owner),
+    "one_time_step": ([(128, 128, 2, 1), (128, 128, 2, 2)], 128, 1, 1, _column_owner),
+    "more_utts_than_unit_columns": ([(64, 64, 2, d) for d in (1, 2)], 64, 40, 3, _column_owner),
+}
+
+
+@pytest.mark.parametrize("precision", PLAIN)
+@pytest.mark.parametrize("case", sorted(WAVENET_CASES))
+def test_plain_half_wavenet_dispatch_vs_rounding_reference(precision, case):
+    layers, ms, B, L, kernels = WAVENET_CASES[case]
+    net = _cond_wavenet(layers[0][0], layers, seed=len(case), out_dim=ms)
+    g = torch.Generator().manual_seed(B * L)
+    x, cot = torch.randn(B, layers[0][0], L, generator=g), torch.randn(B, ms, L, generator=g)
+    _run(net, x, cot, layers, precision, kernels=kernels, label=" " + case)
+
+
+@pytest.mark.parametrize("case", sorted(WAVENET_CASES))
+def test_f16x3_wavenet_dispatch_vs_oracle(case):
+    """the same shapes in f16x3, which takes neither the fused forward nor the column-owner kernels: the fp32 path's 1e-4 bar"""
+    layers, ms, B, L, _ = WAVENET_CASES[case]
+    net = _cond_wavenet(layers[0][0], layers, seed=len(case), out_dim=ms)
+    g = torch.Generator().manual_seed(B * L)
+    x, cot = torch.randn(B, layers[0][0], L, generator=g), torch.randn(B, ms, L, generator=g)
+    _run(net, x, cot, layers, "f16x3", TOL, label=" " + case,
+         kernels=lambda k: "hfused_fwd_kernel" not in k and not any(n.startswith("hcol") for n in k)
+         and k.get("hgemm_kernel<dz,dgate>", 0) >= len(layers) and "hwgrad_kernel" in k)
+
+
+RAWCTC_CASES = {  # channels, layers, causal, feature kwidth, skip rows, B, L, kernels
+    "k3_64_noncausal": (64, [(64, 64, 3, d) for d in (1, 2, 5)], False, 3, 64, 2, 300, _fused_and_hgemm),
+    "k3_256_noncausal_skip128": (256, [(256, 256, 3, d) for d in (1, 3)], False, 3, 128, 1, 200, _all_k3_on_hgemm(3)),
+    "notebook_64": (64, _notebook_layers(64), True, 1, 64, 2, 117, _fused_and_hgemm),
+    "notebook_128": (128, _notebook_layers(128), True, 1, 128, 2, 117, _fused_and_hgemm),
+}
+
+
+@pytest.mark.parametrize("precision", PLAIN)
+@pytest.mark.parametrize("case", sorted(RAWCTC_CASES))
+def test_plain_half_rawctcnet_dispatch_vs_rounding_reference(precision, case):
+    """RawCTCNet: feature layer and output block inside the stack function; non-causal taps (offsets -d, 0, +d); the notebook's
+    mixed k=2 / k=3 stack, whose weight-gradient groups could not be planned before they were formed per block"""
+    c, layers, causal, kf, ms, B, L, kernels = RAWCTC_CASES[case]
+    net = _cond_rawctc(c, layers, causal, seed=c + len(layers), feature_kwidth=kf, out_dim=ms)
+    g = torch.Generator().manual_seed(L)
+    x = torch.randn(B, 1, L, generator=g)
+    cot = torch.randn(B, 5, L + kf - 1, generator=g)
+    _run(net, x, cot, layers, precision, input_grad=False, kernels=kernels, label=" " + case)
+
+
+@pytest.mark.parametrize("precision", PLAIN)
+def test_reference_training_model_in_half_modes(precision):
+    """the reference's own training model (RawCTCNet 512 ch, 21 blocks k=2 + 21 blocks k=3 at dilations 1..64, causal,
+    feature_kwidth=1, batch 8, raw one-channel signal of 117 samples) in a plain half mode, with a conditioned residual path"""
+    layers = _notebook_layers(512)
+    net = _cond_rawctc(512, layers, True, seed=117, feature_kwidth=1)
+    g = torch.Generator().manual_seed(118)
+    x, cot = torch.randn(8, 1, 117, generator=g), torch.randn(8, 5, 117, generator=g)
+    _run(net, x, cot, layers, precision, input_grad=False, label=" reference model 512ch x 43",
+         kernels=lambda k: k.get("hgemm_kernel<gate>", 0) >= 43)
+
+
+@pytest.mark.parametrize("precision", PLAIN)
+def test_frozen_entry_conv_needs_no_input_gradient(precision):
+    """the stack's input needs no gradient (entry conv frozen, data without gradient) at the bottom of a paired chain: the
+    bottom block's dz is all backward needs from it"""
+    c = 64
+    layers = [(c, c, 2, d) for d in (1, 2, 4)]
+    net = _cond_wavenet(c, layers, seed=66)
+    for p in net.entry_conv1d.parameters():
+        p.requires_grad_(False)
+    g = torch.Generator().manual_seed(67)
+    x, cot = torch.randn(2, c, 250, generator=g), torch.randn(2, c, 250, generator=g)
+    _run(net, x, cot, layers, precision, input_grad=False, kernels=_column_owner, label=" frozen entry conv")
+
+
+def test_negative_leaky_slope_is_not_fused():
+    """the series kernels take the sign of the stored activation as the LeakyReLU backward mask, valid for slopes >= 0 only: a
+    model with a negative slope runs its feature layer and output block outside the stack function"""
+    from wavenet_speech_amd.modules.block import fusable_front, fusable_head
+    layers = [(64, 64, 2, d) for d in (1, 2, 4)]
+    net = _cond_rawctc(64, layers, False, seed=5, slope=-0.2)
+    assert fusable_head(net.output_block, "bf16") is None
+    assert fusable_front(net.feature_layer, "bf16", torch.zeros(1, 1, 8)) is None
+    g = torch.Generator().manual_seed(6)
+    x, cot = torch.randn(2, 1, 300, generator=g), torch.randn(2, 5, 302, generator=g)
+    _run(net, x, cot, layers, "bf16", input_grad=False, label=" negative slope")
+
+
+def test_predicate_rejects_plausible_kernel_bugs():
+    """the predicate has teeth: references built from slightly altered parameters -- each what a plausible kernel bug would
+    compute -- are rejected for the unaltered GPU result (only the reference side changes)"""
+    c = 128
+    layers = [(c, c, 2, 1), (c, c, 3, 2), (c, c, 2, 4), (c, c, 2, 8)]
+    net = _cond_wavenet(c, layers, seed=41)
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    g = torch.Generator().manual_seed(42)
+    x, cot = torch.randn(2, c, 500, generator=g), torch.randn(2, c, 500, generator=g)
+
+    def altered(key, f):
+        s = dict(sd)
+        s[key] = f(s[key].clone())
+        return s, None
+
+    def last_tap(w):
+        w[:, :, -1] *= 1 + 2 ** -5
+        return w
+    off_by_one = list(layers)
+    off_by_one[2] = (c, c, 2, 5)
+    mutants = {
+        "conv_sigmoid bias of block 1 zero": altered("convolutions.1.conv_sigmoid.conv1d.bias", torch.zeros_like),
+        "last conv_tanh tap of block 1 x (1 + 2^-5)": altered("convolutions.1.conv_tanh.conv1d.weight", last_tap),
+        "residual_proj bias of block 2 dropped": altered("convolutions.2.residual_proj.bias", torch.zeros_like),
+        "dilation of block 2 off by one": (dict(sd), off_by_one),
+    }
+    _run(net, x, cot, layers, "bf16", kernels=_fused_and_hgemm, label=" mutant base", mutants=mutants)

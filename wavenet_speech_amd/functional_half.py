@@ -159,6 +159,50 @@ class StackPackTable(object):
         return packed
 
 
+def wgrad_groups(lib, shapes, precision_code, cap=None):
+    """The weight-gradient launches of a backward pass.  `shapes`: the BlockShape of every block in the order backward reaches
+    them (top block first).  Returns a list of (grouped, positions): grouped=False is one block on wn_hblock_backward_weights,
+    grouped=True is one wn_hblocks_backward_weights launch over the blocks at those positions of `shapes`.
+
+    Each block brings its own limit (wn_hblocks_wgrad_group_max; `cap`, if given, lowers it -- WN_WGRAD_GROUP).  A block of limit
+    1 (ordinary pairs: > 128 channels) runs alone.  The others join the open group while the group stays within every member's
+    limit and the library still plans it (wn_hblocks_wgrad_workspace_bytes > 0: no more than kMaxPair pairs); a block that does
+    not fit starts the next group.  A stack of equal blocks therefore forms groups of its limit from the top, as before."""
+    out, cur, cur_max = [], [], 0
+
+    def close():
+        if cur:
+            out.append((True, list(cur)))
+            del cur[:]
+
+    for i, s in enumerate(shapes):
+        lim = lib.wn_hblocks_wgrad_group_max(ctypes.byref(s), precision_code)
+        if lim <= 0:
+            _lib.check(-1, "wn_hblocks_wgrad_group_max")
+        if cap is not None:
+            lim = max(1, min(lim, int(cap)))
+        if lim == 1:
+            close()
+            out.append((False, [i]))
+            continue
+        if cur:
+            m = len(cur) + 1
+            arr = (_lib.BlockShape * m)(*[shapes[j] for j in cur + [i]])
+            if m > min(cur_max, lim) or lib.wn_hblocks_wgrad_workspace_bytes(arr, m, precision_code) == 0:
+                close()
+        if not cur:
+            cur_max = lim
+        cur.append(i)
+        cur_max = min(cur_max, lim)
+        if len(cur) >= cur_max:
+            close()
+    close()
+    return out
+
+
+_WGRAD_GROUPS = {}   # wgrad_groups results by (precision, WN_WGRAD_GROUP, WN_HWGRAD_COMPOSITE, block shapes)
+
+
 class _HalfStackFn(torch.autograd.Function):
     """skips_sum of a stack (modules/wavenet.py:98-100 with folded bottlenecks) on the half-precision MFMAs"""
 
@@ -409,11 +453,23 @@ class _HalfStackFn(torch.autograd.Function):
         dx0 = None
         grads_flat = [None] * (len(specs) * PARAMS_PER_BLOCK)
         # weight gradients: small blocks (<= 128 channels) are two or three gradient tiles each -- their operands are kept and
-        # several blocks go into ONE split-K launch + ONE reduction (wn_hblocks_backward_weights); WN_WGRAD_GROUP=1 = per block
-        group_max = lib.wn_hblocks_wgrad_group_max(ctypes.byref(ctx.saved[0][4]), mode.code)
+        # several blocks go into ONE split-K launch + ONE reduction (wn_hblocks_backward_weights); WN_WGRAD_GROUP=1 = per block.
+        # The groups come from every block's own shape (wgrad_groups), in the order the loop below reaches the blocks.
         env_group = os.environ.get("WN_WGRAD_GROUP")
-        if env_group:
-            group_max = max(1, min(group_max, int(env_group)))
+        order = list(range(len(specs) - 1, -1, -1))
+        shapes = [ctx.saved[l][4] for l in order]
+        gkey = (mode.code, env_group, os.environ.get("WN_HWGRAD_COMPOSITE"), tuple(tuple(getattr(s, f) for f, _ in s._fields_) for s in shapes))
+        groups = _WGRAD_GROUPS.get(gkey)
+        if groups is None:           # (the plan depends on the shapes only: planned once per stack geometry)
+            groups = wgrad_groups(lib, shapes, mode.code, int(env_group) if env_group else None)
+            if len(_WGRAD_GROUPS) >= 64:
+                _WGRAD_GROUPS.clear()
+            _WGRAD_GROUPS[gkey] = groups
+        grouped, group_end = set(), set()
+        for is_group, pos in groups:
+            if is_group:
+                grouped.update(order[p] for p in pos)
+                group_end.add(order[pos[-1]])
         pending = []          # (l, shape, x, z, da, dg, dr, grads) of blocks whose weight gradients are not launched yet
 
         def flush():
@@ -461,6 +517,8 @@ class _HalfStackFn(torch.autograd.Function):
                                                        _p(dr), _p(da), _p(dg), _p(dS), _p(zl), _p(sgl), _p(dx), _p(dal), _p(dgl),
                                                        _p(flag), _stream()), "wn_hblock_backward_pair")
                 gates = (dal, dgl)
+            elif have_dz and dx is None and dxd is None:
+                pass          # the bottom of a chain whose input needs no gradient: its dz (da, dg) is all that was needed
             elif have_dz:
                 # the bottom of a chain: the input gradient alone (series, masked by the feature layer's LeakyReLU, or dense)
                 masked = l == 0 and ctx.front is not None
@@ -482,9 +540,9 @@ class _HalfStackFn(torch.autograd.Function):
                       (spec.ms, spec.co), (spec.ms,), (spec.co, spec.ci), (spec.co,)]
             unused = (4, 5, 8, 9) if dr is None else ()
             grads = [None if i in unused else torch.empty(s, dtype=torch.float32, device=dev) for i, s in enumerate(shapes)]
-            if group_max > 1:
+            if l in grouped:
                 pending.append((l, shape, x, z, da, dg, dr, grads))
-                if len(pending) >= group_max:
+                if l in group_end:
                     flush()
             else:
                 ws_bytes = lib.wn_hblock_wgrad_workspace_bytes(ctypes.byref(shape), mode.code)

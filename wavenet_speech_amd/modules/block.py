@@ -185,6 +185,8 @@ def fusable_head(head, precision):
         if not isinstance(c, nn.Conv1d) or c.kernel_size != (1,) or c.stride != (1,) or c.padding != (0,) or c.groups != 1 \
                 or c.bias is None:
             return None
+    if not (mods[0].negative_slope >= 0 and mods[2].negative_slope >= 0):
+        return None          # the series kernels take the sign of the stored activation as the backward mask: slope >= 0 only
     return (mods[0].negative_slope, mods[2].negative_slope), [mods[1].weight, mods[1].bias, mods[3].weight, mods[3].bias]
 
 
@@ -214,6 +216,8 @@ def fusable_front(front, precision, x):
         return None
     if c1.kernel_size != (1,) or c1.stride != (1,) or c1.padding != (0,) or c1.groups != 1:
         return None
+    if not (mods[1].negative_slope >= 0 and mods[3].negative_slope >= 0):
+        return None          # (as in fusable_head: the backward mask is the sign of the stored activation)
     return (mods[1].negative_slope, mods[3].negative_slope), [c0.weight, c0.bias, c1.weight, c1.bias]
 
 
