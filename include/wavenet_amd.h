@@ -240,6 +240,29 @@ int wn_ctc_loss(const float* logits, const long long* labels, const long long* l
                 int blank, float* nll, float* dlogits /* may be NULL */, void* workspace, size_t workspace_bytes,
                 int* bad_labels /* may be NULL */, wn_stream_t stream);
 
+/* ---- CTC decoding on the device: replaces the tail of the reference's evaluation notebooks (argmax_decode + labels2strings,
+ * modules/sequence_decoders.py, and ctcdecode's CTCBeamDecoder).  The input is read through element strides: element
+ * (b, c, t) at x[b * sb + c * sc + t * st], so the stack's [B][C][T] (sb = C*T, sc = T, st = 1) and ctcdecode's (B, T, C)
+ * (sb = T*C, sc = 1, st = C) are both read in place.  fp32.  All pointers are DEVICE pointers; input_lengths [B] int64 or
+ * NULL (= every utterance has `length` frames).  An input length outside [0, length] or a blank outside [0, classes) makes
+ * that utterance decode to nothing (beam scores NaN) and is counted in *bad (DEVICE int, caller-zeroed, may be NULL).
+ *   greedy   argmax per frame (ties to the lowest class), repeats collapsed, blanks dropped:
+ *            labels [B][length] int32 (zero-padded), frames [B][length] (frame of each label, may be NULL), lengths [B]
+ *   beam     CTC prefix beam search, no language model, beam_width prefixes:  labels / frames [B][W][length] (frames may be
+ *            NULL), lengths [B][W], scores [B][W] = natural log probability of the prefix summed over the alignments the
+ *            search kept, sorted descending; slots past the distinct prefixes found: length 0, score -inf.
+ *            input_kind: 0 logits (log-softmax over the classes inside), 1 probabilities, 2 log-probabilities.
+ * Limits: classes <= 64, 1 <= beam_width <= 64, length <= 2^24 (WN_ERR_UNSUPPORTED, nothing launched).
+ * wn_ctc_decode_workspace_bytes is 0 for a bad or unsupported shape. */
+size_t wn_ctc_decode_workspace_bytes(int batch, int classes, int length, int beam_width);
+int wn_ctc_greedy_decode(const float* x, long long sb, long long sc, long long st, const long long* input_lengths /* may be NULL */,
+                         int batch, int classes, int length, int blank, int* labels, int* frames /* may be NULL */, int* lengths,
+                         int* bad /* may be NULL */, wn_stream_t stream);
+int wn_ctc_beam_decode(const float* x, long long sb, long long sc, long long st, int input_kind,
+                       const long long* input_lengths /* may be NULL */, int batch, int classes, int length, int blank,
+                       int beam_width, int* labels, int* frames /* may be NULL */, int* lengths, float* scores, void* workspace,
+                       size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -1,0 +1,151 @@
+"""
+CPU reference of the two CTC decoders of wavenet_speech_amd.decoding (csrc/wn_decode.hip).  TEST INFRASTRUCTURE ONLY.
+Plain numpy float64 in log space, loops over time and beams: small cases only.
+
+greedy: argmax per frame (ties to the lowest class, as torch.argmax / np.argmax), repeats collapsed, blanks dropped.
+
+beam:   CTC prefix beam search without a language model (Hannun, Maas, Jurafsky, Ng, arXiv:1408.2873, 2014).  Each beam is a
+        prefix l with log p_b (ends in blank) and log p_nb (ends in its last label); start {(): p_b = 1, p_nb = 0}.  Per frame:
+          stay       l      p_b' += (p_b + p_nb) y_blank;   p_nb' += p_nb y_last
+          extension  l + c  p_nb' += (c == last ? p_b : p_b + p_nb) y_c        (c != blank)
+        contributions to one prefix are summed; the W prefixes of largest p_b' + p_nb' are kept (zero-probability ones never).
+        Tie rule: score descending, then candidate key ascending -- a stay has (rank of its beam at t-1, 0), an extension
+        (parent rank, 1 + c); a merged candidate keeps the smallest key and that contributor's backpointer.  The frame of a
+        label is the step of the extension that created it on the backpointer path.
+"""
+import math
+
+import numpy as np
+
+NEG = -np.inf
+
+
+def _lae(a, b):
+    """log(exp(a) + exp(b)) of two Python floats (np.logaddexp on scalars is several times slower)"""
+    if a < b:
+        a, b = b, a
+    if b == NEG:
+        return a
+    return a + math.log1p(math.exp(b - a))
+
+
+KINDS = ("logits", "probs", "log_probs")
+
+
+def log_probs(x, kind="logits"):
+    """x [C, T] -> log-probabilities [C, T] in float64"""
+    x = np.asarray(x, dtype=np.float64)
+    if kind == "logits":
+        m = x.max(axis=0, keepdims=True)
+        return x - m - np.log(np.exp(x - m).sum(axis=0, keepdims=True))
+    if kind == "probs":
+        with np.errstate(divide="ignore"):
+            return np.log(x)
+    if kind == "log_probs":
+        return x
+    raise ValueError(kind)
+
+
+def greedy_decode(x, blank=0, input_length=None):
+    """x [C, T] (any monotone form: logits, probabilities, log-probabilities) -> (labels, frames) as lists"""
+    x = np.asarray(x)
+    tb = x.shape[1] if input_length is None else int(input_length)
+    best = np.argmax(x[:, :tb], axis=0) if tb > 0 else np.zeros(0, dtype=np.int64)
+    labels, frames, prev = [], [], -1
+    for t, a in enumerate(best):
+        a = int(a)
+        if a != blank and a != prev:
+            labels.append(a)
+            frames.append(t)
+        prev = a
+    return labels, frames
+
+
+def beam_decode(x, beam_width, blank=0, input_length=None, kind="logits"):
+    """x [C, T] of one utterance -> list of (labels tuple, frames tuple, log score), best first, at most beam_width long"""
+    lp = log_probs(x, kind)
+    tb = lp.shape[1] if input_length is None else int(input_length)
+    beams = [((), (), 0.0, NEG)]                     # (prefix, frames, log p_b, log p_nb), in rank order
+    for t in range(tb):
+        y = lp[:, t].tolist()
+        cand = {}                                    # prefix -> [log p_b, log p_nb, key, frames]
+
+        def add(prefix, pb, pnb, key, frames):
+            e = cand.get(prefix)
+            if e is None:
+                cand[prefix] = [pb, pnb, key, frames]
+                return
+            e[0] = _lae(e[0], pb)
+            e[1] = _lae(e[1], pnb)
+            if key < e[2]:
+                e[2], e[3] = key, frames
+
+        for r, (l, fr, pb, pnb) in enumerate(beams):
+            add(l, _lae(pb, pnb) + y[blank], (pnb + y[l[-1]]) if l else NEG, (r, 0), fr)
+            for c in range(lp.shape[0]):
+                if c == blank:
+                    continue
+                base = pb if (l and c == l[-1]) else _lae(pb, pnb)
+                add(l + (c,), NEG, base + y[c], (r, 1 + c), fr + (t,))
+        items = [(_lae(e[0], e[1]), e[2], p, e[3], e[0], e[1]) for p, e in cand.items()]
+        items = [it for it in items if it[0] > NEG]
+        items.sort(key=lambda it: (-it[0], it[1]))
+        beams = [(p, fr, pb, pnb) for _, _, p, fr, pb, pnb in items[:beam_width]]
+    return [(l, fr, float(_lae(pb, pnb))) for l, fr, pb, pnb in beams]
+
+
+def beam_decode_batch(x, beam_width, blank=0, input_lengths=None, kind="logits"):
+    """x [B, C, T] -> labels [B][W][T], frames [B][W][T], lengths [B][W] (int64), scores [B][W] (float64), in the layout
+    of wavenet_speech_amd.decoding.ctc_beam_decode"""
+    x = np.asarray(x)
+    B, C, T = x.shape
+    labels = np.zeros((B, beam_width, T), dtype=np.int64)
+    frames = np.zeros((B, beam_width, T), dtype=np.int64)
+    lengths = np.zeros((B, beam_width), dtype=np.int64)
+    scores = np.full((B, beam_width), NEG)
+    for b in range(B):
+        tb = None if input_lengths is None else int(input_lengths[b])
+        for w, (l, fr, s) in enumerate(beam_decode(x[b], beam_width, blank, tb, kind)):
+            labels[b, w, :len(l)] = l
+            frames[b, w, :len(fr)] = fr
+            lengths[b, w] = len(l)
+            scores[b, w] = s
+    return labels, frames, lengths, scores
+
+
+def greedy_decode_batch(x, blank=0, input_lengths=None):
+    """x [B, C, T] -> labels [B][T], frames [B][T], lengths [B] (int64), zero-padded"""
+    x = np.asarray(x)
+    B, C, T = x.shape
+    labels = np.zeros((B, T), dtype=np.int64)
+    frames = np.zeros((B, T), dtype=np.int64)
+    lengths = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        l, fr = greedy_decode(x[b], blank, None if input_lengths is None else input_lengths[b])
+        labels[b, :len(l)] = l
+        frames[b, :len(fr)] = fr
+        lengths[b] = len(l)
+    return labels, frames, lengths
+
+
+def collapse(path, blank=0):
+    """an alignment (one class per frame) -> its labelling"""
+    out, prev = [], -1
+    for a in path:
+        if a != blank and a != prev:
+            out.append(int(a))
+        prev = a
+    return tuple(out)
+
+
+def exact_labelling_log_probs(x, blank=0, kind="logits"):
+    """every labelling of x [C, T] with its exact log probability, by enumerating all C^T alignments (tiny T only)"""
+    import itertools
+    lp = log_probs(x, kind)
+    C, T = lp.shape
+    acc = {}
+    for path in itertools.product(range(C), repeat=T):
+        v = sum(lp[a, t] for t, a in enumerate(path))
+        l = collapse(path, blank)
+        acc[l] = np.logaddexp(acc.get(l, NEG), v)
+    return acc

@@ -1,0 +1,152 @@
+"""
+CTC decoding on the device: the tail every reference evaluation notebook runs after RawCTCNet / WaveNetClassifier
+(softmax, argmax_decode + labels2strings of modules/sequence_decoders.py, then ctcdecode's CTCBeamDecoder), as HIP kernels
+(csrc/wn_decode.hip) that read the model's [B][C][T] output in place.
+
+    labels, lengths, frames = ctc_greedy_decode(logits)                        # argmax, repeats collapsed, blanks dropped
+    labels, lengths, scores, frames = ctc_beam_decode(logits, beam_width=8)    # CTC prefix beam search, no language model
+    labels_to_strings(labels[:, 0], lengths[:, 0])                             # host: " AGCT" lookup, 0 = blank
+
+Results stay on the device (int32 labels / frames / lengths, fp32 scores); nothing is copied to the host.  Scores are the
+natural log probability of each prefix summed over the alignments the search kept (higher is better), sorted descending.
+There is no CPU fallback: CPU tensors raise.
+"""
+import torch
+
+from . import _flags, _lib
+
+MAX_CLASSES = 64
+MAX_BEAM_WIDTH = 64
+INPUT_KINDS = {"logits": 0, "probs": 1, "log_probs": 2}
+LAYOUTS = ("BCT", "BTC")
+DEFAULT_ALPHABET = " AGCT"          # the reference's lookup (Decoder.py:26): 0 = blank, 1..4 = A, G, C, T
+
+
+def _prep(x, layout, input_lengths, what):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: needs a GPU tensor (there is no CPU fallback)" % what)
+    if x.dim() != 3:
+        raise ValueError("wavenet_speech_amd.%s: input must be 3-d, got shape %s" % (what, tuple(x.shape)))
+    if layout not in LAYOUTS:
+        raise ValueError("wavenet_speech_amd.%s: layout must be one of %s, got %r" % (what, LAYOUTS, layout))
+    if not x.is_floating_point():
+        raise TypeError("wavenet_speech_amd.%s: input must be floating point, got %s" % (what, x.dtype))
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if layout == "BCT":
+        B, C, T = x.shape
+        sb, sc, st = x.stride()
+    else:
+        B, T, C = x.shape
+        sb, st, sc = x.stride()
+    if B < 1 or T < 1 or C < 2:
+        raise ValueError("wavenet_speech_amd.%s: need batch >= 1, length >= 1 and classes >= 2, got B=%d C=%d T=%d"
+                         % (what, B, C, T))
+    if C > MAX_CLASSES:
+        raise ValueError("wavenet_speech_amd.%s: at most %d classes, got %d" % (what, MAX_CLASSES, C))
+    if input_lengths is not None:
+        input_lengths = torch.as_tensor(input_lengths)
+        if input_lengths.shape != (B,):
+            raise ValueError("wavenet_speech_amd.%s: input_lengths must have shape (%d,), got %s"
+                             % (what, B, tuple(input_lengths.shape)))
+        input_lengths = input_lengths.to(device=x.device, dtype=torch.int64).contiguous()
+    return x, (B, C, T), (sb, sc, st), input_lengths
+
+
+def _note(bad, C, blank, what):
+    _flags.WATCH.poll()
+    _flags.WATCH.note(bad, lambda n, C=C, blank=blank: "wavenet_speech_amd.%s: input_lengths outside [0, T] or blank (%d) outside "
+                      "[0, %d) in %d utterance(s)" % (what, blank, C, n), at_once=False)
+
+
+def ctc_greedy_decode(x, blank=0, input_lengths=None, layout="BCT"):
+    """argmax per frame (ties to the lowest class, as torch.argmax), repeats collapsed, blanks dropped.
+    x: [B, C, T] (or [B, T, C] with layout="BTC") logits, probabilities or log-probabilities -- any of them, the argmax is the
+    same.  Returns (labels [B, T] int32 zero-padded, lengths [B] int32, frames [B, T] int32: the frame of each label)."""
+    x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, "ctc_greedy_decode")
+    lib = _lib.load()
+    from .functional import _p, _stream
+    dev = x.device
+    with torch.cuda.device(dev):
+        labels = torch.empty(B, T, dtype=torch.int32, device=dev)
+        frames = torch.empty(B, T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_ctc_greedy_decode(_p(x), sb, sc, st, _p(in_len), B, C, T, int(blank), _p(labels), _p(frames),
+                                            _p(lengths), _p(bad), _stream()), "wn_ctc_greedy_decode")
+        _note(bad, C, int(blank), "ctc_greedy_decode")
+    return labels, lengths, frames
+
+
+def ctc_beam_decode(x, beam_width, blank=0, input_lengths=None, input="logits", layout="BCT"):
+    """CTC prefix beam search without a language model.
+    x: [B, C, T] (layout="BCT", the model's own output) or [B, T, C] (layout="BTC", ctcdecode's), read in place through its
+    strides; input: "logits" (log-softmax over the classes is applied inside, as the CTC loss does), "probs" or "log_probs".
+    Returns (labels [B, W, T] int32 zero-padded, lengths [B, W] int32, scores [B, W] fp32, frames [B, W, T] int32).
+    scores: natural log probability, higher is better, sorted descending; slots beyond the distinct prefixes found have
+    length 0 and score -inf.  frames: the frame at which each label was emitted on the beam's backpointer path."""
+    if input not in INPUT_KINDS:
+        raise ValueError("wavenet_speech_amd.ctc_beam_decode: input must be one of %s, got %r" % (sorted(INPUT_KINDS), input))
+    W = int(beam_width)
+    if W < 1 or W > MAX_BEAM_WIDTH:
+        raise ValueError("wavenet_speech_amd.ctc_beam_decode: beam_width must be in [1, %d], got %d" % (MAX_BEAM_WIDTH, W))
+    x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, "ctc_beam_decode")
+    lib = _lib.load()
+    from .functional import _p, _stream
+    dev = x.device
+    with torch.cuda.device(dev):
+        ws_bytes = lib.wn_ctc_decode_workspace_bytes(B, C, T, W)
+        if ws_bytes == 0:
+            _lib.check(lib.wn_ctc_beam_decode(None, sb, sc, st, INPUT_KINDS[input], None, B, C, T, int(blank), W, None, None,
+                                              None, None, None, 0, None, None), "wn_ctc_beam_decode")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        labels = torch.empty(B, W, T, dtype=torch.int32, device=dev)
+        frames = torch.empty(B, W, T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, W, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_ctc_beam_decode(_p(x), sb, sc, st, INPUT_KINDS[input], _p(in_len), B, C, T, int(blank), W, _p(labels),
+                                          _p(frames), _p(lengths), _p(scores), _p(ws), ws_bytes, _p(bad), _stream()),
+                   "wn_ctc_beam_decode")
+        _note(bad, C, int(blank), "ctc_beam_decode")
+    return labels, lengths, scores, frames
+
+
+def labels_to_strings(labels, lengths=None, alphabet=DEFAULT_ALPHABET):
+    """host helper: label rows [N, T] (device or host) with their lengths [N] -> list of N strings; alphabet[i] is the
+    character of label i, and label 0 (the blank) maps to the empty string, as the reference's lookup does (Decoder.py:26)"""
+    rows = torch.as_tensor(labels).cpu().tolist()
+    if lengths is None:
+        ns = [len(r) for r in rows]
+    else:
+        ns = [int(n) for n in torch.as_tensor(lengths).cpu().reshape(-1).tolist()]
+    if len(ns) != len(rows):
+        raise ValueError("labels_to_strings: %d rows but %d lengths" % (len(rows), len(ns)))
+    table = [""] + list(alphabet[1:])
+    return ["".join(table[int(v)] for v in r[:n]) for r, n in zip(rows, ns)]
+
+
+class CTCBeamDecoder(object):
+    """The calling shape of ctcdecode's CTCBeamDecoder as the reference notebook uses it,
+        decoder = CTCBeamDecoder(alphabet, beam_width=7, blank_id=0)
+        beam_results, beam_scores, timesteps, out_lens = decoder.decode(probs)      # probs (B, T, C)
+    on ctc_beam_decode: results stay on the device.  No language model (model_path, alpha, beta are not supported).
+    beam_scores here are natural log probabilities, higher is better; ctcdecode's own score convention is not claimed."""
+
+    def __init__(self, labels, beam_width=100, blank_id=0, log_probs_input=False):
+        self.labels = list(labels)
+        if len(self.labels) > MAX_CLASSES:
+            raise ValueError("CTCBeamDecoder: at most %d labels, got %d" % (MAX_CLASSES, len(self.labels)))
+        if not 1 <= int(beam_width) <= MAX_BEAM_WIDTH:
+            raise ValueError("CTCBeamDecoder: beam_width must be in [1, %d], got %d" % (MAX_BEAM_WIDTH, beam_width))
+        self.beam_width = int(beam_width)
+        self.blank_id = int(blank_id)
+        self.log_probs_input = bool(log_probs_input)
+
+    def decode(self, probs, seq_lens=None):
+        """probs: (B, T, C) probabilities (log-probabilities with log_probs_input=True).
+        Returns (beam_results [B, W, T], beam_scores [B, W], timesteps [B, W, T], out_lens [B, W])."""
+        labels, lengths, scores, frames = ctc_beam_decode(probs, self.beam_width, blank=self.blank_id, input_lengths=seq_lens,
+                                                          input="log_probs" if self.log_probs_input else "probs", layout="BTC")
+        return labels, scores, frames, lengths
