@@ -178,11 +178,13 @@ int wn_conv_backward_weights(const wn_conv_shape* s, const float* x, const float
 
 /* ---- next-sample NLL head: replaces the L-iteration CrossEntropyLoss loop of Loss.py:38-43 /
  * legacy_code/train.py:37-39.  logits: dense [B][C][L] floats; target: [B][L] int64 class indices.
- *   forward : lse[b][t] = logsumexp_c logits[b][c][t];  partial[i] = sum over workgroup i of (lse - logits[target])
+ *   forward : lse = [2][B][L] floats, the two terms of logsumexp_c logits[b][c][t] kept apart: lse[0][b][t] = max_c logits,
+ *             lse[1][b][t] = log sum_c exp(logits - max);  partial[i] = sum over workgroup i of ((max - logits[target]) + lse[1])
  *             (wn_nll_partials(B, L) floats; the caller sums them in order and divides by B: deterministic)
  *             A target outside [0, C) is never used as an index: it is counted in *bad_targets (one DEVICE int the caller
  *             zeroed; may be NULL) and makes its workgroup's partial NaN (torch asserts on the device in that case).
- *   backward: dlogits = (exp(logits - lse) - onehot(target)) * gscale[0]      (gscale: one DEVICE float, = dloss / B) */
+ *             A logit of -inf (a masked class) contributes nothing, whatever its position; a target on one gives a loss of +inf.
+ *   backward: dlogits = (exp((logits - lse[0]) - lse[1]) - onehot(target)) * gscale[0]   (gscale: one DEVICE float, = dloss / B) */
 size_t wn_nll_partials(int batch, int length);
 int wn_nll_forward(const float* logits, const long long* target, float* lse, float* partial, int* bad_targets,
                    int batch, int classes, int length, wn_stream_t stream);

@@ -226,6 +226,49 @@ def raw_ctcnet(seq, sd, layers, feature_kwidth, fmt, causal=False, input_dilatio
     return stack_and_head(S, sd, "output_block.", gs, slopes, fused)
 
 
+POOL_MUTANTS = ("window+1", "divisor-1", "start+1", "tail_folded", "grad_not_divided")
+
+
+def avg_pool(seq, pool, mutant=None):
+    """AvgPool1d(pool) of seq [B, C, L] as WaveNetClassifier.mean_pool applies it (no padding, the tail L % pool dropped), in seq's
+    dtype.  Autograd of it is the input gradient the device spreads: / pool, broadcast to the window, zero on the dropped tail.
+    mutant: one of POOL_MUTANTS -- what a plausible kernel bug would compute instead (the references of the mutant tests)."""
+    L = seq.shape[2]
+    Lp = L // pool
+    if Lp < 1:
+        raise RuntimeError("sequence shorter than the pooling window")
+    if mutant is None:
+        return F.avg_pool1d(seq, pool)
+    if mutant == "window+1":           # pool + 1 samples from each window's start (zero beyond the end), their mean
+        return F.avg_pool1d(F.pad(seq, (0, pool + 1)), pool + 1, stride=pool)[:, :, :Lp]
+    if mutant == "divisor-1":
+        assert pool > 1
+        return F.avg_pool1d(seq, pool) * (pool / (pool - 1.0))
+    if mutant == "start+1":            # every window starts one sample late
+        return F.avg_pool1d(F.pad(seq[:, :, 1:], (0, pool)), pool)[:, :, :Lp]
+    if mutant == "tail_folded":        # the last window takes the tail with it
+        assert L % pool, "no tail to fold"
+        last = seq[:, :, (Lp - 1) * pool:].mean(dim=2, keepdim=True)
+        return torch.cat([F.avg_pool1d(seq, pool)[:, :, :Lp - 1], last], dim=2)
+    if mutant == "grad_not_divided":   # the value of the mean, the gradient of the sum
+        total = F.avg_pool1d(seq, pool) * pool
+        return (total / pool).detach() + (total - total.detach())
+    raise ValueError(mutant)
+
+
+def wavenet_classifier(seq, sd, layers, pool, fmt, input_dilation=1, input_kwidth=2, slopes=None, fused=True, pool_mutant=None):
+    """WaveNetClassifier (oracle.wavenet_classifier, softmax off) in a plain half mode: one autograd call, non-causal.  The pooled
+    load sums the window in fp32, multiplies by 1 / (16 pool) and rounds ONCE (hpool_load_kernel): here the fp64 mean stored
+    / 16, the un-pooled input not rounded.  The input gradient leaves the stack dense and is spread by pool_unload_kernel, which is
+    autograd of the mean.  fused: the output block inside the stack call (fusable_head), else on the half convs."""
+    gs = GradScale(fmt)
+    x = avg_pool(seq, pool, pool_mutant)
+    all_layers = [(None, None, input_kwidth, input_dilation)] + list(layers)
+    prefixes = [("input_block.", "input_skip_bottleneck.")] + _layers_prefixes(layers)
+    S = stack(x, sd, all_layers, False, gs, prefixes)
+    return stack_and_head(S, sd, "output_block.", gs, slopes, fused)
+
+
 def run(fn, inputs, sd, cot, fmt):
     """fn(*inputs, sd, fmt) in fp64 with autograd: (output, {name: gradient}) with the inputs' gradients under "dx0", "dx1", ..."""
     sd64 = {k: (v.detach().to(DT).requires_grad_(True) if torch.is_tensor(v) and v.is_floating_point() else v)

@@ -440,6 +440,61 @@ def test_grad_scale_kernel_matches_the_torch_expression():
         assert float(inv) == 1.0 / float(want)
 
 
+def test_grad_scale_tail_lanes_small_counts_and_clamped_grid():
+    """absmax_kernel reads 16-byte vectors and leaves n % 4 elements to the first lanes of workgroup 0; its grid is clamped to 2048
+    workgroups (beyond 4 x 256 x 2048 elements a thread strides).  The maximum in the first element, in the last, in the first
+    element of the tail and in the middle, at counts with every n % 4, below one vector, and past the clamp."""
+    from wavenet_speech_amd import functional_half as FH
+    mode = FH._Mode("f16")
+    big = 4 * 256 * 2049
+    assert big // 4 // 256 > 2048
+    for n in (1, 2, 3, 4, 5, 6, 7, 1025, 1026, 1027, 262147, big, big + 1, big + 2, big + 3):
+        for pos in sorted({0, n - 1, (n // 4) * 4 if n % 4 else n - 1, n // 2, max(n - 2, 0)}):
+            x = torch.randn(n, device=DEV) * 1e-3
+            x[pos] = -37.0 if pos % 2 else 37.0
+            dyn, inv = FH._grad_scale(x, mode)
+            amax = x.abs().amax().clamp_min(1e-30)
+            assert float(amax) == 37.0
+            want = torch.exp2(torch.floor(torch.log2(FH.GRAD_TARGET / amax)).clamp(-100.0, 100.0))
+            assert float(dyn) == float(want) == 2.0 ** -8, (n, pos, float(dyn), float(want))
+            assert float(inv) == 1.0 / float(want)
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+def test_nonfinite_cotangent_is_loud_in_f16(bad):
+    """a NaN or inf in the cotangent of an f16 training call must not come back as finite-looking gradients.  absmax_kernel's fmaxf
+    drops NaNs, so the gradient scale is that of the finite elements (inf: the smallest scale, 2^-100); the cotangent is then stored
+    scaled into the fp16 series, where NaN and inf fail the store-side test !(|v| <= 65504): the fp16-overflow error is raised, at
+    the latest by check_device_flags().  (Every returned gradient being non-finite would be loud as well.)"""
+    c = 32
+    layers = [(c, c, 2, 1), (c, c, 2, 2)]
+    net = _cond_wavenet(c, layers, seed=19).to(DEV)
+    W.set_precision(net, "f16")
+    g = torch.Generator().manual_seed(20)
+    x, cot = torch.randn(2, c, 120, generator=g).to(DEV), torch.randn(2, c, 120, generator=g)
+    cot[1, 5, 77] = bad
+    y = net(x)
+    W.check_device_flags()
+    raised = False
+    try:
+        y.backward(cot.to(DEV))
+        W.check_device_flags()
+    except RuntimeError as e:
+        assert "fp16 overflow" in str(e), str(e)
+        raised = True
+    for _ in range(4):                                   # flags of later launches of the same call may still be in flight
+        try:
+            W.check_fp16_overflow()
+            break
+        except RuntimeError:
+            pass
+    W.check_fp16_overflow()                              # nothing left pending
+    grads = [p.grad for p in net.parameters() if p.grad is not None]
+    print("f16 cotangent with %s: %s" % (bad, "fp16 overflow raised" if raised else "no error, %d of %d gradients non-finite"
+                                         % (sum(not bool(torch.isfinite(t).all()) for t in grads), len(grads))))
+    assert raised or (grads and all(not bool(torch.isfinite(t).all()) for t in grads))
+
+
 # ---- plain bf16 / f16 across the half-mode dispatch, against the rounding reference (tests/halfref.py) ----------------------------
 
 def _all_k3_on_hgemm(n):

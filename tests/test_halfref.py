@@ -67,6 +67,68 @@ def test_exact_stack_call_is_the_oracle():
     _assert_same(_grads(lambda x, s: R.stack_call(x, s, layers, True, None, prefixes), x, sd, cot), want)
 
 
+def _classifier_state(in_dim, layers, out_dim, pool, input_kwidth, input_dilation, seed):
+    from wavenet_speech_amd.modules.classifier import WaveNetClassifier
+    torch.manual_seed(seed)
+    net = WaveNetClassifier(in_dim, 5, layers, out_dim, pool_kernel_size=pool, input_kernel_size=input_kwidth,
+                            input_dilation=input_dilation, softmax=False)
+    with torch.no_grad():
+        for p in net.parameters():
+            if p.dim() == 1:
+                p.add_(0.05 * torch.randn(p.shape))
+    return {k: v.double() for k, v in net.state_dict().items()}
+
+
+@pytest.mark.parametrize("pool,L,kw,dil", [(1, 17, 2, 1), (2, 31, 3, 2), (3, 30, 2, 3), (5, 44, 2, 1), (8, 8, 3, 1)])
+def test_exact_classifier_is_the_oracle(pool, L, kw, dil):
+    layers = [(16, 16, 2, 1), (16, 24, 3, 2), (24, 16, 2, 5)]
+    sd = _classifier_state(7, layers, 12, pool, kw, dil, seed=pool)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 7, L, generator=g, dtype=torch.float64)
+    cot = torch.randn(2, 5, L // pool, generator=g, dtype=torch.float64)
+    want = _grads(lambda x, s: O.wavenet_classifier(x, s, layers, pool, dil, False), x, sd, cot)
+    if L % pool:
+        assert bool((want["dx0"][:, :, L - L % pool:] == 0).all())          # the dropped tail gets an exact zero
+    for fused in (True, False):
+        _assert_same(_grads(lambda x, s: R.wavenet_classifier(x, s, layers, pool, None, input_dilation=dil, input_kwidth=kw,
+                                                              fused=fused), x, sd, cot), want)
+
+
+@pytest.mark.parametrize("name", ["classifier_00"])
+def test_exact_classifier_reproduces_the_golden(name):
+    """forward and every gradient, x included, of the reference's own classifier run, at test_oracle_golden.py's tolerances"""
+    from tests import goldenio
+    from tests.test_oracle_golden import TOL
+    g = goldenio.load(name)
+    m = g.meta
+    assert not m["softmax"]
+    sd = {k: v.double() for k, v in g.sd.items() if v.is_floating_point()}
+    got = _grads(lambda x, s: R.wavenet_classifier(x, s, m["layers"], m["pool_kernel_size"], None, input_dilation=m["input_dilation"],
+                                                   input_kwidth=m["input_kernel_size"]), g.inputs["x"].double(), sd,
+                 g.cots[0].double())
+    assert O.rel_err(got["forward"], g.outs[0].double()) < TOL
+    seen = 0
+    for k, ref in g.grads.items():
+        if g.hasgrad[k]:
+            assert O.rel_err(got[k], ref.double()) < 1e-4, k
+            seen += 1
+    assert seen >= 20
+    assert O.rel_err(got["dx0"], g.grad_inputs["x"].double()) < 1e-4
+
+
+@pytest.mark.parametrize("mutant", R.POOL_MUTANTS)
+def test_pool_mutants_differ_from_the_mean(mutant):
+    """each altered pooling the GPU mutant tests use is a different operation (value or gradient), not a restatement"""
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(2, 3, 23, generator=g, dtype=torch.float64, requires_grad=True)
+    x2 = x.detach().clone().requires_grad_(True)
+    y, y2 = R.avg_pool(x, 5), R.avg_pool(x2, 5, mutant)
+    assert y.shape == y2.shape == (2, 3, 4)
+    y.sum().backward()
+    y2.sum().backward()
+    assert O.rel_err(y2, y) > 1e-2 or O.rel_err(x2.grad, x.grad) > 1e-2
+
+
 @pytest.mark.parametrize("fmt,bound", [("bf16", 0.1), ("f16", 0.02)])
 def test_rounding_path_stays_within_its_format(fmt, bound):
     """the rounding path differs from the exact one, by the format's error (e_fmt is what the GPU bounds are multiples of)"""

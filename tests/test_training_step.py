@@ -60,7 +60,9 @@ def test_fused_nll_head_matches_the_reference_loop(shape):
     torch.manual_seed(4)
     pred = torch.randn(B, C, L) * 3
     target = torch.randint(0, C, (B, L))
-    pc = pred.clone().requires_grad_(True)
+    # the reference's loop, evaluated in fp64: torch's own fp32 cross_entropy is 1.2e-6 from fp64 in the gradient at (2, 256, 1000),
+    # more than the bar below, so it cannot carry it (tests/test_gpu_nll.py holds the kernel to the same bars at its edges)
+    pc = pred.double().requires_grad_(True)
     if L <= 200:
         loop = sum(F.cross_entropy(pc[:, :, t], target[:, t]) for t in range(L))      # the reference's loop
     else:
@@ -70,6 +72,6 @@ def test_fused_nll_head_matches_the_reference_loop(shape):
     got = T.sequence_nll(pg, target.to("cuda:0"))
     (got * 1.7).backward()
     assert abs(float(got) - float(loop)) < 1e-5 * max(1.0, abs(float(loop)))
-    assert float((pg.grad.cpu() - pc.grad).abs().max()) < 1e-6 * max(1.0, float(pc.grad.abs().max())) + 1e-7
+    assert float((pg.grad.cpu().double() - pc.grad).abs().max()) < 1e-6 * max(1.0, float(pc.grad.abs().max())) + 1e-7
     again = T.sequence_nll(pg.detach(), target.to("cuda:0"))
     assert float(again) == float(got)            # deterministic

@@ -247,7 +247,10 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = __builtin_fmaxf(m, __builtin_fabsf(x[(n4 << 2) + threadIdx.x]));
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(acc, __builtin_bit_cast(unsigned, m));   // NaN bit patterns order above inf: they win, as in torch
+    // NaNs never get here: fmaxf returns its other operand, so the scale is that of the finite elements (inf gives 2^-100).  A NaN or
+    // inf cotangent is made loud one step on, where it is stored into the fp16 series: NaN * scale and inf * scale fail the store-side
+    // test !(|v| <= 65504) and raise the overflow flag (tests/test_gpu_half.py::test_nonfinite_cotangent_is_loud_in_f16)
+    if ((threadIdx.x & 63) == 0) atomicMax(acc, __builtin_bit_cast(unsigned, m));
 }
 
 __global__ void grad_scale_kernel(unsigned* acc, float target, float* out) {

@@ -465,7 +465,7 @@ class _SequenceNLLFn(torch.autograd.Function):
         B, C, L = logits.shape
         x = logits.detach().contiguous()
         tg = target.contiguous()
-        lse = torch.empty(B, L, dtype=torch.float32, device=x.device)
+        lse = torch.empty(2, B, L, dtype=torch.float32, device=x.device)   # (max, log sum exp(. - max)): csrc/wn_nll.hip
         partial = torch.empty(lib.wn_nll_partials(B, L), dtype=torch.float32, device=x.device)
         bad = torch.zeros(1, dtype=torch.int32, device=x.device)
         _lib.check(lib.wn_nll_forward(_p(x), _p(tg), _p(lse), _p(partial), _p(bad), B, C, L, _stream()), "wn_nll_forward")
