@@ -265,6 +265,33 @@ int wn_ctc_beam_decode(const float* x, long long sb, long long sc, long long st,
                        int beam_width, int* labels, int* frames /* may be NULL */, int* lengths, float* scores, void* workspace,
                        size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- CTC forced alignment on the device: the best single alignment (Viterbi path) of a KNOWN label sequence to the frames --
+ * which frames belong to which label -- where wn_ctc_loss sums over all alignments.  x, its element strides and input_kind as
+ * in wn_ctc_beam_decode; labels [B][max_label_len] int64, label_lengths [B] int64, input_lengths [B] int64 or NULL as in
+ * wn_ctc_loss.  With l' the blank-extended labelling (2 L + 1 states: even = blank, odd s = label (s - 1) / 2) a path starts in
+ * state 0 or 1, ends in state S - 1 or S - 2 and moves by 0, +1, or +2 (only onto a label that differs from the label two
+ * states back); its score is the sum of the frame log-probabilities of its states.  The recursion runs in float64.
+ * Ties: predecessors are tried in the order s, s - 1, s - 2 and a later one wins only if strictly greater; the path ends in
+ * S - 1 unless S - 2 scores strictly higher.
+ *   states        [B][length] int32: the state of every frame t < input_lengths[b], -1 after
+ *   frame_labels  [B][length] int32 or NULL: l' of that state (a label or the blank), -1 in the same places
+ *   spans         [B][max_label_len][2] int32 or NULL: label j < label_lengths[b] occupies frames [first, one past last);
+ *                 rows j >= label_lengths[b] are (-1, -1)
+ *   score         [B] fp32: the path's log-probability
+ * No alignment fits (fewer frames than labels + adjacent repeats, or every alignment has probability 0): score -inf, every
+ * state / label / span entry -1.  No frames: score 0 for an empty label sequence, else -inf.  A label outside [0, classes),
+ * equal to blank, or a length outside its range poisons the utterance as in wn_ctc_loss: score NaN, every entry -1, counted
+ * in *bad (DEVICE int, caller-zeroed, may be NULL).
+ * workspace: wn_ctc_align_workspace_bytes (2 bits per state and frame; 0 for a bad or unsupported shape), 16-byte aligned.
+ * Limits: classes <= 64, 1 <= max_label_len <= 2047, length <= 2^24, batch <= 65535, batch * length < 2^31
+ * (WN_ERR_UNSUPPORTED, nothing launched). */
+size_t wn_ctc_align_workspace_bytes(int batch, int classes, int length, int max_label_len);
+int wn_ctc_align(const float* x, long long sb, long long sc, long long st, int input_kind, const long long* labels,
+                 const long long* label_lengths, const long long* input_lengths /* may be NULL */, int batch, int classes,
+                 int length, int max_label_len, int blank, int* states, int* frame_labels /* may be NULL */,
+                 int* spans /* may be NULL */, float* score, void* workspace, size_t workspace_bytes, int* bad /* may be NULL */,
+                 wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

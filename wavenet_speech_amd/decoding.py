@@ -7,16 +7,23 @@ CTC decoding on the device: the tail every reference evaluation notebook runs af
     labels, lengths, scores, frames = ctc_beam_decode(logits, beam_width=8)    # CTC prefix beam search, no language model
     labels_to_strings(labels[:, 0], lengths[:, 0])                             # host: " AGCT" lookup, 0 = blank
 
+and CTC forced alignment (csrc/wn_align.hip): the best single alignment of a KNOWN label sequence to the frames,
+
+    states, frame_labels, spans, score = ctc_forced_align(logits, targets, target_lengths)   # spans[b, j] = [first, end) frames
+
 Results stay on the device (int32 labels / frames / lengths, fp32 scores); nothing is copied to the host.  Scores are the
 natural log probability of each prefix summed over the alignments the search kept (higher is better), sorted descending.
 There is no CPU fallback: CPU tensors raise.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _flags, _lib
 
 MAX_CLASSES = 64
 MAX_BEAM_WIDTH = 64
+MAX_ALIGN_LABELS = 2047
 INPUT_KINDS = {"logits": 0, "probs": 1, "log_probs": 2}
 LAYOUTS = ("BCT", "BTC")
 DEFAULT_ALPHABET = " AGCT"          # the reference's lookup (Decoder.py:26): 0 = blank, 1..4 = A, G, C, T
@@ -111,6 +118,62 @@ def ctc_beam_decode(x, beam_width, blank=0, input_lengths=None, input="logits", 
                    "wn_ctc_beam_decode")
         _note(bad, C, int(blank), "ctc_beam_decode")
     return labels, lengths, scores, frames
+
+
+CTCAlignment = namedtuple("CTCAlignment", "states frame_labels spans score")
+
+
+def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, input="logits", layout="BCT"):
+    """The best single CTC alignment (Viterbi path) of known labels to the frames.
+    x, input, layout, input_lengths: as ctc_beam_decode.  targets: [B, Lmax] labels of any integer dtype (values in [0, C),
+    none equal to blank), target_lengths: [B].  Returns CTCAlignment, all on the device:
+      states [B, T] int32        state of the blank-extended labelling per frame (even: a blank, odd s: label (s - 1) // 2), -1 past
+                                 the utterance
+      frame_labels [B, T] int32  the class of that state, -1 in the same places
+      spans [B, Lmax, 2] int32   label j occupies frames [spans[b, j, 0], spans[b, j, 1]); rows past target_lengths[b] are -1
+      score [B] fp32             log-probability of the path; -inf (and every entry -1) when no alignment fits
+    Ties go to the lower move: stay before advance before skip, the final blank before the final label.  A bad label or length
+    gives score NaN and every entry -1, and is reported through check_device_flags()."""
+    what = "ctc_forced_align"
+    if input not in INPUT_KINDS:
+        raise ValueError("wavenet_speech_amd.%s: input must be one of %s, got %r" % (what, sorted(INPUT_KINDS), input))
+    x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, what)
+    dev = x.device
+    targets, target_lengths = torch.as_tensor(targets), torch.as_tensor(target_lengths)
+    if targets.is_floating_point() or targets.dtype == torch.bool or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("wavenet_speech_amd.%s: targets must be integers of shape (%d, Lmax), got %s %s"
+                         % (what, B, targets.dtype, tuple(targets.shape)))
+    if target_lengths.shape != (B,):
+        raise ValueError("wavenet_speech_amd.%s: target_lengths must have shape (%d,), got %s" % (what, B, tuple(target_lengths.shape)))
+    lmax = width = int(targets.shape[1])
+    if lmax > MAX_ALIGN_LABELS:
+        raise ValueError("wavenet_speech_amd.%s: at most %d labels per utterance, got %d" % (what, MAX_ALIGN_LABELS, lmax))
+    if not 0 <= int(blank) < C:
+        raise ValueError("wavenet_speech_amd.%s: blank must be in [0, %d), got %d" % (what, C, int(blank)))
+    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+    target_lengths = target_lengths.to(device=dev, dtype=torch.int64).contiguous()
+    if lmax == 0:                                                    # the C ABI wants one column; no utterance may use it
+        lmax, targets = 1, torch.zeros(B, 1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    from .functional import _p, _stream
+    with torch.cuda.device(dev):
+        ws_bytes = lib.wn_ctc_align_workspace_bytes(B, C, T, lmax)
+        if ws_bytes == 0:
+            _lib.check(lib.wn_ctc_align(None, sb, sc, st, INPUT_KINDS[input], None, None, None, B, C, T, lmax, int(blank), None, None,
+                                        None, None, None, 0, None, None), "wn_ctc_align")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        states = torch.empty(B, T, dtype=torch.int32, device=dev)
+        frame_labels = torch.empty(B, T, dtype=torch.int32, device=dev)
+        spans = torch.empty(B, lmax, 2, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_ctc_align(_p(x), sb, sc, st, INPUT_KINDS[input], _p(targets), _p(target_lengths), _p(in_len), B, C, T, lmax,
+                                    int(blank), _p(states), _p(frame_labels), _p(spans), _p(score), _p(ws), ws_bytes, _p(bad),
+                                    _stream()), "wn_ctc_align")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_forced_align: labels outside [0, %d), equal to "
+                          "the blank (%d), or lengths out of range in %d utterance(s)" % (C, blank, n), at_once=False)
+    return CTCAlignment(states, frame_labels, spans[:, :width], score)
 
 
 def labels_to_strings(labels, lengths=None, alphabet=DEFAULT_ALPHABET):
