@@ -292,6 +292,33 @@ int wn_ctc_align(const float* x, long long sb, long long sc, long long st, int i
                  int* spans /* may be NULL */, float* score, void* workspace, size_t workspace_bytes, int* bad /* may be NULL */,
                  wn_stream_t stream);
 
+/* ---- Global pairwise alignment of two label sequences with affine gaps (Needleman-Wunsch / Gotoh, int32, exact): how close
+ * a decoded read is to the truth -- what the reference's evaluation notebook asks EMBOSS needle.  ref [B] rows of ref_stride
+ * elements (rows i = 1..N), query likewise (columns j = 1..M): int32 labels, compared for equality only (no class limit);
+ * values past ref_lengths[b] / query_lengths[b] are never read.  A gap of length n costs gap_open + (n - 1) gap_extend.
+ *   E[i][j] = max(H[i][j-1] - go, E[i][j-1] - ge),  F[i][j] = max(H[i-1][j] - go, F[i-1][j] - ge): opening wins a tie
+ *   H[i][j] = diagonal + (match | mismatch), then E, then F: a later candidate replaces an earlier one only if strictly greater
+ *   borders H[i][0], H[0][j]: 0 with end_gaps_free, else -(go + ge (k - 1)); H[0][0] = 0
+ *   end cell (N, M); with end_gaps_free the best of (N, M), the last row from j = M down, the last column from i = N down,
+ *   replaced only by a strictly greater one.  The trace runs back until i == 0 or j == 0; the unconsumed head and tail of
+ *   either sequence are end gaps: they appear in ops and count in the gap columns and the length.
+ *   score    [B] int32
+ *   stats    [B][4] int32 or NULL: matches, mismatches, gap columns, alignment length
+ *   ops      [B][max_ref_len + max_query_len] bytes or NULL, front to back: 1 match, 2 mismatch, 3 reference label against a
+ *            gap, 4 query label against a gap, 0 padding;  ops_len [B] int32, required if and only if ops is given
+ * ops == NULL and stats == NULL is the score-only form: no workspace (with costs 0, -1, 1, 1 and end gaps penalised,
+ * -score is the Levenshtein distance).  A length that is negative or above its maximum poisons the pair: score INT_MIN, stats
+ * -1, ops_len 0, counted in *bad (DEVICE int, caller-zeroed, may be NULL).  Length 0 is valid: all end gaps.
+ * workspace: wn_pair_align_workspace_bytes (0 for a bad or unsupported shape), 16-byte aligned.
+ * Limits: max_query_len <= 8192, max_ref_len <= 65535, batch <= 65535, 0 <= gap_extend <= gap_open <= 1024,
+ * |match|, |mismatch| <= 1024 (WN_ERR_UNSUPPORTED, nothing launched). */
+size_t wn_pair_align_workspace_bytes(int batch, int max_ref_len, int max_query_len);
+int wn_pair_align(const int* ref, long long ref_stride, const int* ref_lengths, const int* query, long long query_stride,
+                  const int* query_lengths, int batch, int max_ref_len, int max_query_len, int match, int mismatch,
+                  int gap_open, int gap_extend, int end_gaps_free, int* score, int* stats /* may be NULL */,
+                  unsigned char* ops /* may be NULL */, int* ops_len /* with ops */, void* workspace, size_t workspace_bytes,
+                  int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

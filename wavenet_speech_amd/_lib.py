@@ -154,7 +154,10 @@ SIGNATURES = {
     "wn_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wn_ctc_align": (c_int, [c_float_p, c_longlong, c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_float_p, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "wn_nll_partials": (c_size_t, [c_int, c_int]),
+    "wn_pair_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wn_pair_align": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wn_nll_partials":(c_size_t, [c_int, c_int]),
     "wn_nll_forward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wn_nll_backward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_void_p]),
     "wn_prof_enable": (c_int, [c_int]),

@@ -11,6 +11,13 @@ and CTC forced alignment (csrc/wn_align.hip): the best single alignment of a KNO
 
     states, frame_labels, spans, score = ctc_forced_align(logits, targets, target_lengths)   # spans[b, j] = [first, end) frames
 
+and global pairwise alignment with affine gaps (csrc/wn_pairalign.hip): how close a decoded read is to the truth, the
+step the reference's evaluation notebook hands to EMBOSS needle,
+
+    r = pairwise_align(targets, target_lengths, labels, lengths)     # r.score, r.matches, r.gaps, r.length, r.identity, r.ops
+    edit_distance(targets, target_lengths, labels, lengths)          # Levenshtein distance, int32 [B]
+    print("\n".join(format_alignment(targets[0], labels[0], r.ops[0])))
+
 Results stay on the device (int32 labels / frames / lengths, fp32 scores); nothing is copied to the host.  Scores are the
 natural log probability of each prefix summed over the alignments the search kept (higher is better), sorted descending.
 There is no CPU fallback: CPU tensors raise.
@@ -174,6 +181,139 @@ def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, in
         _flags.WATCH.note(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_forced_align: labels outside [0, %d), equal to "
                           "the blank (%d), or lengths out of range in %d utterance(s)" % (C, blank, n), at_once=False)
     return CTCAlignment(states, frame_labels, spans[:, :width], score)
+
+
+MAX_PAIR_QUERY = 8192
+MAX_PAIR_REF = 65535
+MAX_PAIR_COST = 1024          # of the doubled integer costs
+OP_PAD, OP_MATCH, OP_MISMATCH, OP_REF_GAP, OP_QUERY_GAP = 0, 1, 2, 3, 4
+
+
+class PairwiseAlignment(namedtuple("PairwiseAlignment", "score matches mismatches gaps length ops ops_len")):
+    """score [B] fp32; matches, mismatches, gaps (gap columns, end gaps included), length [B] int32; ops [B, N + M] uint8 front
+    to back (1 match, 2 mismatch, 3 reference label against a gap, 4 query label against a gap, 0 padding) with ops_len [B]
+    int32 -- ops and ops_len are None with return_ops=False.  All on the device."""
+    __slots__ = ()
+
+    @property
+    def identity(self):
+        """matches / length per pair (fp32, NaN for an empty alignment), as needle's 'Identity'"""
+        return self.matches.float() / self.length.float()
+
+
+def _pair_rows(rows, lengths, what, name):
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
+    if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 2:
+        raise ValueError("wavenet_speech_amd.%s: %s must be int32 or int64 of shape (B, n), got %s %s"
+                         % (what, name, rows.dtype, tuple(rows.shape)))
+    B = int(rows.shape[0])
+    lengths = torch.as_tensor(lengths)
+    if lengths.is_floating_point() or lengths.dtype == torch.bool or lengths.shape != (B,):
+        raise ValueError("wavenet_speech_amd.%s: %s_lengths must be integers of shape (%d,), got %s %s"
+                         % (what, name, B, lengths.dtype, tuple(lengths.shape)))
+    rows = rows.detach()
+    if rows.dtype != torch.int32:
+        rows = rows.to(torch.int32)                                  # on the device; labels are compared for equality only
+    if rows.shape[1] == 0:                                           # the C ABI wants one column; no pair may use it
+        rows = torch.zeros(B, 1, dtype=torch.int32, device=rows.device)
+    if rows.stride(1) != 1:
+        rows = rows.contiguous()
+    return rows, lengths.to(device=rows.device, dtype=torch.int32).contiguous()
+
+
+def _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_free, want_stats, want_ops):
+    ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
+    query, query_lengths = _pair_rows(query, query_lengths, what, "query")
+    B, N, M = int(ref.shape[0]), int(ref.shape[1]), int(query.shape[1])
+    if query.shape[0] != B or query.device != ref.device:
+        raise ValueError("wavenet_speech_amd.%s: ref and query must hold the same number of rows on one device" % what)
+    if B < 1:
+        raise ValueError("wavenet_speech_amd.%s: need at least one pair" % what)
+    if N > MAX_PAIR_REF or M > MAX_PAIR_QUERY:
+        raise ValueError("wavenet_speech_amd.%s: at most %d reference and %d query labels per pair, got %d and %d"
+                         % (what, MAX_PAIR_REF, MAX_PAIR_QUERY, N, M))
+    lib = _lib.load()
+    from .functional import _p, _stream
+    dev = ref.device
+    with torch.cuda.device(dev):
+        score = torch.empty(B, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        stats = ops = ops_len = ws = None
+        ws_bytes = 0
+        if want_stats or want_ops:
+            ws_bytes = lib.wn_pair_align_workspace_bytes(B, N, M)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            stats = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        if want_ops:
+            ops = torch.empty(B, N + M, dtype=torch.uint8, device=dev)
+            ops_len = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_pair_align(_p(ref), ref.stride(0), _p(ref_lengths), _p(query), query.stride(0), _p(query_lengths), B, N, M,
+                                     costs[0], costs[1], costs[2], costs[3], int(bool(end_gaps_free)), _p(score), _p(stats), _p(ops),
+                                     _p(ops_len), _p(ws), ws_bytes, _p(bad), _stream()), "wn_pair_align")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n, N=N, M=M: "wavenet_speech_amd.%s: ref_lengths outside [0, %d] or query_lengths outside "
+                          "[0, %d] in %d pair(s)" % (what, N, M, n), at_once=False)
+    return score, stats, ops, ops_len
+
+
+def pairwise_align(ref, ref_lengths, query, query_lengths, match=5, mismatch=-4, gap_open=10, gap_extend=0.5, end_gaps_free=True,
+                   return_ops=True):
+    """Global alignment with affine gaps of query rows against reference rows.  The defaults are EMBOSS
+    needle's for nucleotides as the reference's evaluation notebook runs it: EDNAFULL's 5 / -4 on A, C, G, T, gap open 10
+    (a gap's first column), gap extend 0.5, end gaps not penalised.
+    ref [B, N], query [B, M]: int32 or int64 GPU tensors with their lengths [B] -- `labels` / `lengths` of ctc_greedy_decode, a
+    beam of ctc_beam_decode, `targets` / `target_lengths` as ctc_forced_align takes them: nothing passes through the host.
+    Costs must be multiples of 0.5 (the kernel's arithmetic is integer, in half units: exact); the score comes back as fp32.
+    Returns PairwiseAlignment.  Among equally scoring alignments the tie rule of DESIGN.md 7d decides, so needle may show
+    another one of the same score.  A length outside its range poisons the pair (score -2^30, counts -1, ops_len 0) and is
+    reported through check_device_flags()."""
+    what = "pairwise_align"
+    costs = []
+    for name, v in (("match", match), ("mismatch", mismatch), ("gap_open", gap_open), ("gap_extend", gap_extend)):
+        d = 2.0 * float(v)
+        if d != int(d):
+            raise ValueError("wavenet_speech_amd.%s: %s must be a multiple of 0.5, got %r" % (what, name, v))
+        costs.append(int(d))
+    if not (0 <= costs[3] <= costs[2] <= MAX_PAIR_COST) or max(abs(costs[0]), abs(costs[1])) > MAX_PAIR_COST:
+        raise ValueError("wavenet_speech_amd.%s: need 0 <= gap_extend <= gap_open <= %g and |match|, |mismatch| <= %g, got %r"
+                         % (what, MAX_PAIR_COST / 2, MAX_PAIR_COST / 2, (match, mismatch, gap_open, gap_extend)))
+    score, stats, ops, ops_len = _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_free, True, return_ops)
+    if ops is not None:
+        ops = ops[:, :int(ref.shape[1]) + int(query.shape[1])]       # a row without columns went in as one unused column
+    return PairwiseAlignment(score.float() * 0.5, stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], ops, ops_len)
+
+
+def edit_distance(a, a_lengths, b, b_lengths):
+    """Levenshtein distance of every row pair, int32 [B] on the device: the score-only form of the alignment kernel with unit
+    costs (no workspace, no trace).  -1 for a pair with a length outside its range (reported through check_device_flags())."""
+    score, _, _, _ = _pair_align("edit_distance", a, a_lengths, b, b_lengths, (0, -1, 1, 1), False, False, False)
+    return torch.where(score == -2 ** 31, torch.full_like(score, -1), -score)
+
+
+def format_alignment(ref_row, query_row, ops_row, alphabet=DEFAULT_ALPHABET):
+    """host helper: the three text lines of one alignment as needle prints them -- the reference with '-' where the query has
+    a label against a gap, '|' for a match and '.' for a mismatch, the query with '-' likewise.  alphabet[i] is the character
+    of label i ('?' for a label outside it); ops_row may carry its zero padding."""
+    ref = [int(v) for v in torch.as_tensor(ref_row).cpu().reshape(-1).tolist()]
+    query = [int(v) for v in torch.as_tensor(query_row).cpu().reshape(-1).tolist()]
+    char = lambda v: alphabet[v] if 0 <= v < len(alphabet) else "?"  # noqa: E731
+    top, mid, bottom, i, j = [], [], [], 0, 0
+    for op in torch.as_tensor(ops_row).cpu().reshape(-1).tolist():
+        if op == OP_PAD:
+            break
+        if op in (OP_MATCH, OP_MISMATCH):
+            top.append(char(ref[i])); mid.append("|" if op == OP_MATCH else "."); bottom.append(char(query[j]))
+            i, j = i + 1, j + 1
+        elif op == OP_REF_GAP:
+            top.append(char(ref[i])); mid.append(" "); bottom.append("-")
+            i += 1
+        elif op == OP_QUERY_GAP:
+            top.append("-"); mid.append(" "); bottom.append(char(query[j]))
+            j += 1
+        else:
+            raise ValueError("format_alignment: op code %r" % (op,))
+    return "".join(top), "".join(mid), "".join(bottom)
 
 
 def labels_to_strings(labels, lengths=None, alphabet=DEFAULT_ALPHABET):
