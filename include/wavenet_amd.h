@@ -319,6 +319,56 @@ int wn_pair_align(const int* ref, long long ref_stride, const int* ref_lengths, 
                   unsigned char* ops /* may be NULL */, int* ops_len /* with ops */, void* workspace, size_t workspace_bytes,
                   int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Ragged synthetic reads on the device: the data of the reference's RawCTCNet workloads (RawGaussianModelLoader with
+ * random_upsample=True, utils/gaussian_kmer_model.py:181-319; RawSignalGenerator, utils/raw_signal_generator.py): reads of random
+ * length, every 5-mer held for a random number of samples (its dwell), raw fp32 picoamps zero-padded to a common row length,
+ * the bases as CTC targets.  Two launches; all pointers are DEVICE pointers; rows of bases / dwell / starts are max_bases ints.
+ * Random numbers are Philox4x32-10 of `seed`: stream 2 counter b for a length, stream 0 counter (b << 32) | i for a base,
+ * stream 3 counter (b << 32) | p for a dwell, stream 1 counter (b << 32) | t for a sample's noise -- read b's draws depend on
+ * (seed, b) only, not on the batch.
+ *   wn_reads_plan, one workgroup per read:
+ *     base_lengths[b]  uniform in [min_bases, max_bases), or base_lengths_in[b]; a given length outside [5 + 2 window, max_bases)
+ *                      poisons the read
+ *     bases[b][i]      1..4 for i < base_lengths[b], 0 after (the reference's batchify), or bases_in (a value outside 1..4
+ *                      inside the length poisons the read)
+ *     window           2: the loader's [4:-4] trim, k-mer p = bases[p+2 .. p+6];  0: RawSignalGenerator's [2:-2], k-mer p =
+ *                      bases[p .. p+4].  K_b = base_lengths[b] - 4 - 2 window k-mers
+ *     dwell[b][p] >= 1 for p < K_b, 0 after.  WN_DWELL_FIXED: p0.  WN_DWELL_UNIFORM (r = p0, w = p1): an integer in
+ *                      [max(r - w, 1), r + w) by multiply-high of one 32-bit word (bias <= range / 2^32 per value).
+ *                      WN_DWELL_GAMMA (shape p0, rate p1, sample rate p2): max(1, (int)(g * p2)), g ~ Gamma(shape, scale 1 / rate)
+ *                      by Marsaglia-Tsang with Box-Muller normals (shape < 1 through Gamma(shape + 1) U^(1 / shape)); the
+ *                      rejection loop is bounded at 16 attempts (sub-counter = attempt), all of them failing has probability
+ *                      < 1e-21 and then g = max(shape, shape + 1 below 1) / rate with U = 1/2.  Or dwell_in (an entry < 1 below
+ *                      K_b poisons the read).  Values above max_dwell are clamped to it and counted in *clamped.
+ *     starts[b][p]     exclusive prefix sum of the dwell for p <= K_b; = signal_lengths[b] for every p >= K_b
+ *     signal_lengths[b] = starts[b][K_b]
+ *     A poisoned read has base length 0, signal length 0, bases / dwell / starts all 0 and is counted in *bad; its given
+ *     values are never used as an index.  workspace (wn_reads_workspace_bytes, 16-byte aligned) receives the 5-mer index of
+ *     every k-mer for wn_reads_signal.
+ *   wn_reads_signal, grid (ceil(ld / 256), batch); ld = the caller's row capacity of signal / sample_kmer / noise:
+ *     signal[b][t]     (float)(means[k] + stdvs[k] * z) evaluated in float64, t < signal_lengths[b]; k = 5-mer index of the k-mer
+ *                      p with starts[b][p] <= t < starts[b][p + 1]; z ~ N(0, 1) by Box-Muller, or noise[b][t].  means / stdvs:
+ *                      1024 doubles.  0.0f for signal_lengths[b] <= t < ld
+ *     sample_kmer[b][t] p, -1 past the read (may be NULL).  Every element of both rows is written.
+ *     A read longer than ld is truncated at ld and counted in *bad; clipped_lengths[b] = min(signal_lengths[b], ld).
+ * bad / clamped: DEVICE ints, caller-zeroed, may be NULL.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_bases, ld < 1; window not 0 or 2; min_bases outside
+ * [5 + 2 window, max_bases); max_dwell < 1; an unknown dwell model, r < 1, an empty uniform interval, shape / rate / sample
+ * rate not positive and finite.  WN_ERR_UNSUPPORTED: batch > 65535, max_bases > 65536, (max_bases - 5) max_dwell >= 2^31,
+ * ld > 2^31 - 257.  Then WN_ERR_NULL, then WN_ERR_WORKSPACE. */
+enum { WN_DWELL_FIXED = 0, WN_DWELL_UNIFORM = 1, WN_DWELL_GAMMA = 2 };
+size_t wn_reads_workspace_bytes(int batch, int max_bases);
+int wn_reads_plan(unsigned long long seed, int batch, int min_bases, int max_bases, int window, int dwell_model, double dwell_p0,
+                  double dwell_p1, double dwell_p2, int max_dwell, const int* base_lengths_in /* may be NULL */,
+                  const int* bases_in /* may be NULL */, const int* dwell_in /* may be NULL */, int* base_lengths, int* bases,
+                  int* dwell, int* starts, int* signal_lengths, void* workspace, size_t workspace_bytes,
+                  int* bad /* may be NULL */, int* clamped /* may be NULL */, wn_stream_t stream);
+int wn_reads_signal(const int* base_lengths, const int* starts, const int* signal_lengths, const void* workspace,
+                    size_t workspace_bytes, int batch, int max_bases, int window, int ld, const double* means,
+                    const double* stdvs, unsigned long long seed, const double* noise /* may be NULL */, float* signal,
+                    int* sample_kmer /* may be NULL */, int* clipped_lengths /* may be NULL */, int* bad /* may be NULL */,
+                    wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time the HIP read generator (csrc/wn_synth.hip) against the same stages as torch ops on the GPU.
-Usage: synth_bench.py [batch length]"""
+Usage: synth_bench.py [batch length]
+       synth_bench.py --ragged [--out FILE]     the ragged generator (csrc/wn_reads.hip, two launches) next to the fixed
+                                                three-launch generator at the same sample count and the torch-op form"""
 import os
 import sys
 import time
@@ -9,6 +11,62 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
+
+
+
+def ragged(out_path):
+    """device events; B = 32 reads of about 700 bases, uniform (6, 2) (about cfg2's 4096 samples), and B = 16 at about 16 000"""
+    def timed_ev(fn, n=50, warm=5):
+        for _ in range(warm):
+            fn()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(n):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / n
+
+    dev = "cuda:0"
+    lines = ["ragged generator, uniform dwell (6, 2), loader window; ms per call by device events, host launch overhead included"]
+    table = S.standin_kmer_table(device=dev)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    host_gen = torch.Generator().manual_seed(1)                        # the seed is drawn on the host: no device read
+    for B, nb in ((32, 700), (16, 2700)):
+        lo, hi = nb - 8, nb + 8
+        pad = (hi - 9) * 7                                              # no read can be longer
+        plan = S.hip_reads_plan(B, lo, hi, 2, ("uniform", 6, 2), 7, 3, dev)
+        t_plan = timed_ev(lambda: S.hip_reads_plan(B, lo, hi, 2, ("uniform", 6, 2), 7, 3, dev))
+        t_sig = timed_ev(lambda: S.hip_reads_signal(plan, pad, table, 3))
+        t_both = timed_ev(lambda: S.ragged_reads(B, (lo, hi), ("uniform", 6, 2), table=table, generator=host_gen, device=dev, pad_to=pad))
+        t_sync = timed_ev(lambda: S.ragged_reads(B, (lo, hi), ("uniform", 6, 2), table=table, generator=host_gen, device=dev))
+        samples = int(plan["signal_lengths"].max())
+        fixed_bases = S.hip_bases(B, -(-samples // 3) + 8, 11, dev)
+
+        def fixed():
+            S.hip_bases(B, -(-samples // 3) + 8, 11, dev)
+            S.hip_signal(fixed_bases, samples, 256, 3, table, seed=3, want_one_hot=False)
+        t_fixed = timed_ev(fixed)
+        t_torch = timed_ev(lambda: S._torch_reads(B, lo, hi, 2, ("uniform", 6, 2), 7, table, gen, torch.device(dev), pad, None, None, None,
+                                                  None), n=20)
+        lines += ["B = %d, %d..%d bases, longest read %d samples, rows of %d" % (B, lo, hi - 1, samples, pad),
+                  "  wn_reads_plan                          : %.3f ms" % t_plan,
+                  "  wn_reads_signal                        : %.3f ms" % t_sig,
+                  "  ragged_reads, pad_to (two launches)    : %.3f ms" % t_both,
+                  "  ragged_reads, one host read of the max : %.3f ms" % t_sync,
+                  "  fixed generator, %d samples, 3 launches (bases, signal, quantize; no one-hot): %.3f ms" % (samples, t_fixed),
+                  "  torch ops on the GPU (randint, cumsum, searchsorted, gather, randn)         : %.3f ms" % t_torch,
+                  "  expectation (plan + signal <= fixed three-launch generator): %s" % ("holds" if t_plan + t_sig <= t_fixed else "DOES NOT HOLD")]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    open(out_path, "w").write(text + "\n")
+
+
+if "--ragged" in sys.argv:
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "r06", "ragged_bench.txt")
+    ragged(out)
+    sys.exit(0)
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 L = int(sys.argv[2]) if len(sys.argv) > 2 else 16000

@@ -17,5 +17,6 @@ from .graphs import GraphedStep  # noqa: F401
 from .decoding import (CTCAlignment, CTCBeamDecoder, PairwiseAlignment, ctc_beam_decode, ctc_forced_align,  # noqa: F401
                        ctc_greedy_decode, edit_distance, format_alignment, labels_to_strings, pairwise_align)
 from .functional_half import check_fp16_overflow  # noqa: F401
+from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 
 __version__ = "0.1.0"

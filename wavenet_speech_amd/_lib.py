@@ -157,6 +157,12 @@ SIGNATURES = {
     "wn_pair_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wn_pair_align": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wn_reads_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wn_reads_plan": (c_int, [c_ulonglong, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                              c_void_p]),
+    "wn_reads_signal": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wn_nll_partials":(c_size_t, [c_int, c_int]),
     "wn_nll_forward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wn_nll_backward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_void_p]),

@@ -16,6 +16,7 @@
 // The per-read mean is a fixed-order sum (per-workgroup partials combined in index order): bit-reproducible run to run.
 #include "../../include/wavenet_amd.h"
 #include "wn_kernels.h"
+#include "wn_philox.h"
 
 namespace wn {
 
@@ -23,22 +24,7 @@ constexpr int kSynTile = 256;   // samples per workgroup
 
 struct SynPart { double sum, mn, mx; };
 
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-// stream 0: nucleotides, stream 1: Gaussian noise (the stream number sits in the counter's top word)
-__device__ __forceinline__ void draw(unsigned long long seed, unsigned stream, unsigned long long index, unsigned (&c)[4]) {
-    c[0] = (unsigned)index; c[1] = (unsigned)(index >> 32); c[2] = 0u; c[3] = stream;
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-}
+// philox4x32_10 / draw / philox_normal: wn_philox.h (stream 0: nucleotides, stream 1: Gaussian noise)
 
 __global__ __launch_bounds__(256) void synth_bases_kernel(unsigned long long seed, long long n, long long* bases) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -75,9 +61,7 @@ __global__ __launch_bounds__(kSynTile) void synth_signal_kernel(const long long*
         } else {
             unsigned c[4];
             draw(seed, 1u, (unsigned long long)flat, c);
-            const double u1 = ((double)(((unsigned long long)(c[0] >> 5) << 26) | (c[1] >> 6)) + 0.5) * (1.0 / 9007199254740992.0);
-            const double u2 = ((double)(((unsigned long long)(c[2] >> 5) << 26) | (c[3] >> 6)) + 0.5) * (1.0 / 9007199254740992.0);
-            z = sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+            z = philox_normal(c);
         }
         x = means[kmer] + stdvs[kmer] * z;
         pico[flat] = x;
