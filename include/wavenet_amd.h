@@ -369,6 +369,38 @@ int wn_reads_signal(const int* base_lengths, const int* starts, const int* signa
                     int* sample_kmer /* may be NULL */, int* clipped_lengths /* may be NULL */, int* bad /* may be NULL */,
                     wn_stream_t stream);
 
+/* ---- Chunked whole-read inference (wavenet_speech_amd/basecalling.py): a read of any length is cut into chunks of `chunk`
+ * samples overlapping by the network's receptive field, all chunks run through ONE fixed-shape forward, and every chunk keeps
+ * only the frames whose receptive field lay inside it.  These are the two streaming launches around that forward.  All
+ * pointers are DEVICE pointers.  The plan is made on the host, five ints per chunk:
+ *     plan[n] = (read, s0, u_lo, t0, count)   chunk n holds samples [s0, s0 + chunk) of `read`; its frames [u_lo, u_lo + count)
+ *                                             are frames [t0, t0 + count) of that read.  count = 0 marks a dead chunk (padding
+ *                                             of a micro-batch): its other fields are not looked at.
+ *   wn_chunk_gather, grid (ceil(chunk / 1024), n_chunks), 4 consecutive samples per thread, one 16-byte store each:
+ *     signal           [batch][ld] fp32, or int16 DAC counts when signal_is_int16 != 0; signal_lengths[b] <= ld samples are valid
+ *     out[n][i]        x_b[s0 + i] for s0 + i < signal_lengths[b], 0.0f otherwise and in every dead chunk; [n_chunks][chunk]
+ *                      fp32, 16-byte aligned.  x_b[s] = (float(signal[b][s]) + shift[b]) * scale[b], two separately rounded
+ *                      fp32 operations (never an FMA); scale / shift: [batch] fp32, each may be NULL (then left out)
+ *     A live row with read outside [0, batch), s0 outside [0, ld), count < 0, or a length outside [0, ld] is counted in *bad
+ *     and written as zeros; none of these values is used as an index.
+ *   wn_chunk_stitch, grid (ceil(y_frames / 256), classes, n_chunks), one element per thread:
+ *     y                [n_chunks][classes][y_frames] fp32 through its element strides (stride_n, stride_c, stride_t >= 0)
+ *     out[b][c][t0 + i] = y[n][c][u_lo + i] for i < count; out: [batch][classes][out_frames] fp32 through out_stride_b /
+ *                      out_stride_c (unit stride in time), zero-filled by the caller
+ *     A live row with read outside [0, batch), a negative field, u_lo + count > y_frames, t0 + count > frame_lengths[b] or
+ *     frame_lengths[b] > out_frames is counted in *bad and skipped.
+ * bad: a DEVICE int, caller-zeroed, may be NULL.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: a dimension < 1, chunk % 4 != 0, a negative stride.
+ * WN_ERR_UNSUPPORTED: n_chunks > 65535, classes > 65535, ld / chunk / y_frames / out_frames >= 2^31 - 1024, or a grid of 2^32
+ * threads or more (256 ceil(chunk / 1024) n_chunks; 256 ceil(y_frames / 256) classes n_chunks): longer plans go in several calls.
+ * ld is both the row stride and the row capacity: lengths up to ld are accepted, so rows must be dense.  Then WN_ERR_NULL, then WN_ERR_WORKSPACE for an `out` of wn_chunk_gather that is not 16-byte aligned. */
+int wn_chunk_gather(const void* signal, int signal_is_int16, int batch, int ld, const int* signal_lengths,
+                    const float* scale /* may be NULL */, const float* shift /* may be NULL */, const int* plan, int n_chunks,
+                    int chunk, float* out, int* bad /* may be NULL */, wn_stream_t stream);
+int wn_chunk_stitch(const float* y, long long stride_n, long long stride_c, long long stride_t, int y_frames, const int* plan,
+                    int n_chunks, int classes, int batch, float* out, long long out_stride_b, long long out_stride_c,
+                    int out_frames, const int* frame_lengths, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -163,6 +163,10 @@ SIGNATURES = {
                               c_void_p]),
     "wn_reads_signal": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wn_chunk_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_void_p, c_void_p]),
+    "wn_chunk_stitch": (c_int, [c_void_p, c_longlong, c_longlong, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
     "wn_nll_partials":(c_size_t, [c_int, c_int]),
     "wn_nll_forward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wn_nll_backward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_void_p]),
