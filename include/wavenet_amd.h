@@ -401,6 +401,34 @@ int wn_chunk_stitch(const float* y, long long stride_n, long long stride_c, long
                     int n_chunks, int classes, int batch, float* out, long long out_stride_b, long long out_stride_c,
                     int out_frames, const int* frame_lengths, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Read normalisation (wavenet_speech_amd/normalise.py): exact order statistics of ragged reads, from which the median, the
+ * MAD and quantiles give the (scale, shift) of wn_chunk_gather.  All pointers but the workspace size are DEVICE pointers.
+ *     out[b][k] = the ranks[b][k]-th smallest (0-based) of the first signal_lengths[b] samples of read b, as fp32
+ *   signal           [batch][ld] fp32, or int16 with signal_is_int16 != 0; ld is both the row stride and the row capacity
+ *   ranks            [batch][K] int32, 1 <= K <= 8
+ *   center           [batch] fp32 or NULL.  Given, the elements are the absolute deviations d = |(float)x - center[b]| (one
+ *                    correctly rounded fp32 subtraction), and out holds the ranks[b][k]-th smallest deviation
+ *   out              [batch][K] fp32: the element itself (x or d), never a value rebuilt from counts
+ * A most-significant-digit radix select, 8 bits per pass, over an order-preserving unsigned key: int16 (uint16)x ^ 0x8000, two
+ * passes; fp32 u ^ (sign ? 0xFFFFFFFF : 0x80000000), u the bits of x, four passes; with center the bits of d, four passes.
+ * Integer histograms only: exact, and bitwise the same from run to run.  -0.0 sorts directly below +0.0 (either may come
+ * back; they compare equal); a NaN with its sign bit clear sorts above +inf, one with it set below -inf.  One memset, one
+ * launch per pass, grid (ceil(ld / 8192), batch), and one small closing launch: the count depends on the dtype and on center
+ * only, nothing is read back, the call can be captured into a HIP graph.
+ * Checked on the device: a read with signal_lengths[b] < 0 or > ld, and a rank outside [0, signal_lengths[b]) (every rank of
+ * an empty read), write 0.0f to their out[b][k] and count once each in *bad (DEVICE int, caller-zeroed, may be NULL); no
+ * sample at or past a length is read.
+ * workspace: wn_read_select_workspace_bytes(batch, K, signal_is_int16, has_center) bytes, 16-byte aligned, zeroed by the call
+ * itself on the stream; 0 for an unsupported shape (batch or K out of range).
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, ld or K < 1.  WN_ERR_UNSUPPORTED: K > 8, batch > 65535,
+ * ld >= 2^31 - 1024, or a grid of 2^32 threads or more (256 ceil(ld / 8192) batch).  Then WN_ERR_NULL (center and bad are
+ * optional), then WN_ERR_WORKSPACE: a workspace that is too small or not 16-byte aligned, or a signal not aligned to its
+ * element size. */
+size_t wn_read_select_workspace_bytes(int batch, int K, int signal_is_int16, int has_center);
+int wn_read_select(const void* signal, int signal_is_int16, int batch, int ld, const int* signal_lengths, const int* ranks, int K,
+                   const float* center /* may be NULL */, float* out, void* workspace, size_t workspace_bytes,
+                   int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

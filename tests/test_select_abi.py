@@ -1,0 +1,115 @@
+"""CPU: the C ABI of read selection (csrc/wn_select.hip): exported symbols, the ctypes table against the header, the workspace
+size, and the shape / limit / pointer / workspace checks, which run on the host before any HIP call -- none of the calls below
+touches a device."""
+import ctypes
+import os
+import re
+
+import pytest
+
+WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL, WN_ERR_WORKSPACE = 0, -1, -2, -3, -5
+FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below returns before it would be used
+ODD = ctypes.c_void_p((1 << 20) + 8)     # 8-byte but not 16-byte aligned
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("wn_read_select_workspace_bytes", "wn_read_select")
+EDGE = 2 ** 31 - 1024                    # the first ld that is refused
+BIG = 1 << 40                            # a workspace size that is always enough
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from wavenet_speech_amd import _lib
+    return _lib.load()
+
+
+def test_select_symbols_are_exported(lib):
+    from wavenet_speech_amd import _lib
+    for name in NAMES:
+        assert name in _lib.SIGNATURES
+        assert hasattr(lib, name)
+    assert lib.wn_version() == 300                                   # additive entry points
+
+
+def test_signature_table_matches_the_header():
+    from wavenet_speech_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wavenet_amd.h")).read(), flags=re.S)
+    kinds = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
+    for name in NAMES:
+        m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % name, src)
+        assert m, name
+        res, args = _lib.SIGNATURES[name]
+        assert res is kinds[m.group(1).strip()]
+        params = [" ".join(p.split()) for p in m.group(2).split(",")]
+        assert len(params) == len(args), (name, len(params), len(args))
+        for p, ctype in zip(params, args):
+            if "*" in p or p.startswith("wn_stream_t"):
+                assert ctype is ctypes.c_void_p, (name, p)
+            else:
+                assert ctype is kinds[p.rsplit(" ", 1)[0]], (name, p)
+
+
+def test_tile_matches_the_kernel():
+    from wavenet_speech_amd import normalise
+    src = open(os.path.join(ROOT, "wavenet_speech_amd", "csrc", "wn_select.hip")).read()
+    assert int(re.search(r"constexpr int kSelTile = (\d+);", src).group(1)) == normalise.TILE
+    assert int(re.search(r"constexpr int kSelMaxK = (\d+);", src).group(1)) == normalise.MAX_RANKS
+
+
+def test_workspace_bytes(lib):
+    ws = lib.wn_read_select_workspace_bytes
+    # per read: one histogram of 256 uint32 for the first pass, K for every later one; int16 without center has 2 passes, else 4
+    assert ws(1, 1, 1, 0) == 2 * 1024 and ws(1, 1, 0, 0) == 4 * 1024
+    assert ws(3, 2, 1, 0) == 3 * (1 + 2) * 1024
+    assert ws(3, 2, 1, 1) == ws(3, 2, 0, 0) == ws(3, 2, 0, 1) == 3 * (1 + 3 * 2) * 1024
+    assert ws(65535, 8, 0, 1) == 65535 * 25 * 1024                   # above 2^30: a size_t
+    for batch, K in ((1, 1), (65535, 1), (1, 8), (48, 2)):
+        for is_int16 in (0, 1):
+            for has_center in (0, 1):
+                assert ws(batch, K, is_int16, has_center) > 0
+    for batch, K in ((0, 1), (-1, 1), (65536, 1), (1, 0), (1, -2), (1, 9)):
+        assert ws(batch, K, 1, 0) == 0 and ws(batch, K, 0, 1) == 0
+
+
+def _select(lib, signal=FAKE, is_int16=0, batch=2, ld=100, signal_lengths=FAKE, ranks=FAKE, K=2, center=None, out=FAKE, workspace=FAKE,
+            workspace_bytes=BIG, bad=None):
+    return lib.wn_read_select(signal, is_int16, batch, ld, signal_lengths, ranks, K, center, out, workspace, workspace_bytes, bad, None)
+
+
+def test_read_select_rejects_on_the_host(lib):
+    for kw in (dict(batch=0), dict(batch=-1), dict(ld=0), dict(ld=-7), dict(K=0), dict(K=-3)):
+        assert _select(lib, **kw) == WN_ERR_BAD_SHAPE, kw
+    assert _select(lib, K=9) == WN_ERR_UNSUPPORTED
+    assert _select(lib, batch=65536) == WN_ERR_UNSUPPORTED
+    assert _select(lib, ld=EDGE) == WN_ERR_UNSUPPORTED
+    # the accepted side of each edge goes on to the pointer checks
+    assert _select(lib, K=8, out=None) == WN_ERR_NULL
+    assert _select(lib, K=1, out=None) == WN_ERR_NULL
+    assert _select(lib, batch=65535, out=None) == WN_ERR_NULL
+    assert _select(lib, batch=1, ld=1, out=None) == WN_ERR_NULL
+    assert _select(lib, batch=1, ld=EDGE - 1, out=None) == WN_ERR_NULL
+    # a launch stays below 2^32 threads: 256 * ceil(ld / 8192) * batch
+    assert _select(lib, ld=8192 * 256, batch=65535, out=None) == WN_ERR_NULL                            # 2^32 - 2^16
+    assert _select(lib, ld=8192 * 512, batch=32768) == WN_ERR_UNSUPPORTED                               # 2^32
+    assert _select(lib, ld=8192 * 512, batch=32767, out=None) == WN_ERR_NULL
+    assert _select(lib, ld=8192 * 256 + 1, batch=65535) == WN_ERR_UNSUPPORTED
+    for is_int16 in (0, 1):
+        for name in ("signal", "signal_lengths", "ranks", "out", "workspace"):       # center and bad are optional (NULL in every call here)
+            assert _select(lib, is_int16=is_int16, **{name: None}) == WN_ERR_NULL, name
+    # the workspace: 16-byte aligned and at least wn_read_select_workspace_bytes
+    assert _select(lib, workspace=ODD) == WN_ERR_WORKSPACE
+    assert _select(lib, workspace=ctypes.c_void_p((1 << 20) + 4)) == WN_ERR_WORKSPACE
+    for is_int16 in (0, 1):
+        for center in (None, FAKE):
+            need = lib.wn_read_select_workspace_bytes(2, 2, is_int16, int(center is not None))
+            assert _select(lib, is_int16=is_int16, center=center, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert _select(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
+    # a signal that is not aligned to its element could not be read 16 bytes at a time from any boundary
+    assert _select(lib, is_int16=1, signal=ctypes.c_void_p((1 << 20) + 1)) == WN_ERR_WORKSPACE
+    assert _select(lib, is_int16=0, signal=ctypes.c_void_p((1 << 20) + 2)) == WN_ERR_WORKSPACE
+    # the order of the checks: shape, then unsupported, then NULL, then the workspace
+    assert _select(lib, K=0, batch=65536, ranks=None) == WN_ERR_BAD_SHAPE
+    assert _select(lib, batch=0, ld=EDGE, ranks=None) == WN_ERR_BAD_SHAPE
+    assert _select(lib, K=9, ranks=None, workspace=ODD) == WN_ERR_UNSUPPORTED
+    assert _select(lib, ld=EDGE, signal=None) == WN_ERR_UNSUPPORTED
+    assert _select(lib, ranks=None, workspace=ODD) == WN_ERR_NULL
+    assert _select(lib, ranks=None, workspace_bytes=0) == WN_ERR_NULL

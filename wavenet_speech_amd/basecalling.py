@@ -8,6 +8,7 @@ and nothing is averaged.
 
     bc = Basecaller(model, chunk=4096, batch=32, graph=True)
     out = bc(signal, signal_lengths, decode="greedy")     # signal [B, 1, Lpad] or [B, Lpad], fp32 or int16 DAC counts
+    out = bc(raw_int16, signal_lengths, normalise="medmad")             # per-read median / MAD on the device (normalise.py)
     out.logits, out.frame_lengths, out.labels, out.label_lengths
 
 What a basecall is: the logits of read b (n samples) are the T_b = n + feature_kwidth - 1 frames of the model's forward on the
@@ -30,6 +31,7 @@ from . import _flags, _lib, series
 from .decoding import ctc_beam_decode, ctc_greedy_decode
 from .modules.block import freeze_for_inference
 from .modules.raw_ctcnet import RawCTCNet
+from .normalise import read_normalisation
 
 PLAN_INTS = 5                       # (read, s0, u_lo, t0, count)
 MAX_DIM = 2 ** 31 - 1024            # ld, chunk and frame counts of the C ABI stay below this
@@ -247,8 +249,16 @@ class Basecaller(object):
             acc.add_(flag)
         return self.y
 
-    def __call__(self, signal, signal_lengths, scale=None, shift=None, decode=None, beam_width=8, want_logits=True):
+    def __call__(self, signal, signal_lengths, scale=None, shift=None, decode=None, beam_width=8, want_logits=True, normalise=None):
+        """normalise: None (scale / shift as given, or none), "medmad" or "quantile" (normalise.read_normalisation with its
+        defaults), or a callable (signal [B, Lpad], lengths [B] int32 on the device) -> (scale, shift): computed on the device
+        before the first gather.  Not together with scale or shift."""
         what = "wavenet_speech_amd.Basecaller"
+        if normalise is not None:
+            if scale is not None or shift is not None:
+                raise ValueError("%s: give either normalise or scale / shift, not both" % what)
+            if not callable(normalise) and normalise not in ("medmad", "quantile"):
+                raise ValueError("%s: normalise must be None, 'medmad', 'quantile' or a callable, got %r" % (what, normalise))
         if decode not in (None, "greedy", "beam"):
             raise ValueError("%s: decode must be None, 'greedy' or 'beam', got %r" % (what, decode))
         if not isinstance(signal, torch.Tensor) or not signal.is_cuda:
@@ -290,6 +300,13 @@ class Basecaller(object):
                 self._capture()                                             # a parameter changed: the graph holds stale packed weights
             rows_d = rows.to(dev, non_blocking=False)
             len_d = lengths.to(device=dev, dtype=torch.int32).contiguous()
+            if normalise is not None:
+                scale, shift = normalise(signal, len_d) if callable(normalise) else read_normalisation(signal, len_d, method=normalise)
+                for name, v in (("scale", scale), ("shift", shift)):
+                    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.shape != (B,):
+                        raise ValueError("%s: normalise must return (scale, shift), GPU tensors of shape (%d,)" % (what, B))
+                scale = scale.detach().to(device=dev, dtype=torch.float32).contiguous()
+                shift = shift.detach().to(device=dev, dtype=torch.float32).contiguous()
             frame_lengths = plan.frame_lengths.to(dev)
             Tmax = int(plan.frame_lengths.max())
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
