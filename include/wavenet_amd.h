@@ -429,6 +429,42 @@ int wn_read_select(const void* signal, int signal_is_int16, int batch, int ld, c
                    const float* center /* may be NULL */, float* out, void* workspace, size_t workspace_bytes,
                    int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Per-base quality of a decoded read (wavenet_speech_amd.decoding.ctc_base_qualities): how much to
+ * trust each label a decoder emitted when the truth is not known -- a Phred quality per base, a mean error per read.  x, its
+ * element strides, input_kind and input_lengths as in wn_ctc_beam_decode.  labels / frames: int32 rows of labels_stride /
+ * frames_stride elements (>= 0), max_labels of them used -- the outputs of wn_ctc_greedy_decode, or one beam of
+ * wn_ctc_beam_decode in place; lengths [B] int32.  All pointers are DEVICE pointers.  For utterance b with T_b frames:
+ *     w_t(c)    expf(x_t(c) - max_c x_t(c)) for logits and log-probabilities, x_t(c) for probabilities
+ *     eps_t(l)  sum over c != l of w_t(c)  /  sum over c of w_t(c): both sums formed directly in fp32 in class order, never 1 - p
+ *     a_t       the lowest class among the maxima of x_t (the greedy decoder's rule)
+ *     run of base j (label l, frame f): frame f, then the frames t = f + 1, f + 2, ... below min(the next base's frame, T_b)
+ *               (T_b for the last base) for as long as a_t == l.  It always holds f, argmax or not (a beam path's emission
+ *               frame need not be one); on a greedy path it is the collapsed run.
+ *   dwell  [B][max_labels] int32    frames in the run
+ *   error  [B][max_labels] fp32     stat 0: the mean of eps_t(l) over the run, summed in frame order in float64;
+ *                                   stat 1: the least eps_t(l) of the run
+ *   qual   [B][max_labels] bytes    floor(Q + 0.5) clamped to [0, 93], Q = qscale (-10 log10 error) + qbias in float64 (error 0
+ *                                   gives 93, NaN gives 0); the FASTQ character is qual + 33
+ *   read_error [B] fp32             the mean of error[b][j] over j < lengths[b]: every thread of one workgroup sums a strided
+ *                                   share in order in float64, then a fixed tree; NaN for an empty read.  Uncalibrated.
+ * Any of the four may be NULL, not all.  Every launch is bitwise reproducible (no floating-point atomics).
+ * Checked on the device: a base with a label outside [0, classes) or equal to blank, a frame outside [0, T_b), or a frame not
+ * above its predecessor's has error NaN, qual 0, dwell 0, makes read_error[b] NaN and counts once in *bad (DEVICE int,
+ * caller-zeroed, may be NULL).  A read with lengths[b] outside [0, max_labels] or input_lengths[b] outside [0, length] has
+ * every entry of its rows so, read_error NaN, and counts once.  Entries at and past lengths[b] are NaN / 0 / 0 too (not
+ * counted).  None of these values is used as an index.
+ * One thread per base, grid (ceil(max_labels / 256), batch); work per base is its own run.  No workspace.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, length or max_labels < 1, classes < 2, a negative row
+ * stride, an unknown input_kind or stat, qscale not finite and positive, qbias not finite.  WN_ERR_UNSUPPORTED: classes > 64,
+ * length > 2^24, max_labels > length, batch > 65535, or a grid of 2^32 threads or more (256 ceil(max_labels / 256) batch).
+ * Then WN_ERR_NULL. */
+int wn_ctc_base_quality(const float* x, long long sb, long long sc, long long st, int input_kind,
+                        const long long* input_lengths /* may be NULL */, const int* labels, long long labels_stride,
+                        const int* frames, long long frames_stride, const int* lengths, int batch, int classes, int length,
+                        int max_labels, int blank, int stat /* 0 mean, 1 best */, float qscale, float qbias,
+                        float* error /* may be NULL */, unsigned char* qual /* may be NULL */, int* dwell /* may be NULL */,
+                        float* read_error /* may be NULL */, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

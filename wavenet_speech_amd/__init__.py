@@ -14,8 +14,9 @@ from .modules import (CausalConv1d, NonCausalConv1d, RawCTCNet, ResidualBlock, W
 from .modules.block import freeze_for_inference, set_precision  # noqa: F401
 from ._flags import check_device_flags  # noqa: F401
 from .graphs import GraphedStep  # noqa: F401
-from .decoding import (CTCAlignment, CTCBeamDecoder, PairwiseAlignment, ctc_beam_decode, ctc_forced_align,  # noqa: F401
-                       ctc_greedy_decode, edit_distance, format_alignment, labels_to_strings, pairwise_align)
+from .decoding import (BaseQualities, CTCAlignment, CTCBeamDecoder, PairwiseAlignment, ctc_base_qualities,  # noqa: F401
+                       ctc_beam_decode, ctc_forced_align, ctc_greedy_decode, edit_distance, fastq_records, format_alignment,
+                       labels_to_strings, pairwise_align)
 from .functional_half import check_fp16_overflow  # noqa: F401
 from .basecalling import Basecaller, Basecalls, ChunkPlan, chunk_plan, receptive_field  # noqa: F401
 from .normalise import read_med_mad, read_normalisation, read_order_statistics, read_quantiles  # noqa: F401

@@ -10,6 +10,7 @@ and nothing is averaged.
     out = bc(signal, signal_lengths, decode="greedy")     # signal [B, 1, Lpad] or [B, Lpad], fp32 or int16 DAC counts
     out = bc(raw_int16, signal_lengths, normalise="medmad")             # per-read median / MAD on the device (normalise.py)
     out.logits, out.frame_lengths, out.labels, out.label_lengths
+    q = bc.qualities(out)                                 # Phred quality per base, mean error per read (decoding.py)
 
 What a basecall is: the logits of read b (n samples) are the T_b = n + feature_kwidth - 1 frames of the model's forward on the
 read FOLLOWED BY ZEROS, model(F.pad(read, (0, p)))[..., :T_b] for any p >= right -- what training on zero-padded ragged
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _flags, _lib, series
-from .decoding import ctc_beam_decode, ctc_greedy_decode
+from .decoding import ctc_base_qualities, ctc_beam_decode, ctc_greedy_decode
 from .modules.block import freeze_for_inference
 from .modules.raw_ctcnet import RawCTCNet
 from .normalise import read_normalisation
@@ -334,3 +335,18 @@ class Basecaller(object):
                 labels, label_lengths, scores, frames = ctc_beam_decode(logits, beam_width, input_lengths=frame_lengths,
                                                                         input="probs" if self.model.softmax else "logits")
         return Basecalls(logits if want_logits else None, frame_lengths, labels, label_lengths, frames, scores)
+
+    def qualities(self, calls, **kw):
+        """Per-base qualities of a decoded Basecalls (decoding.ctc_base_qualities, whose keyword arguments pass through: stat,
+        qscale, qbias, blank): the labels of a greedy decode, or the best beam of a beam search, against the logits they were
+        decoded from -- read as probabilities when the model applies its own softmax.  Returns BaseQualities."""
+        what = "wavenet_speech_amd.Basecaller.qualities"
+        if calls.logits is None:
+            raise ValueError("%s: the Basecalls carry no logits (they were made with want_logits=False)" % what)
+        if calls.labels is None:
+            raise ValueError("%s: the Basecalls carry no labels (they were made without decode=)" % what)
+        labels, lengths, frames = calls.labels, calls.label_lengths, calls.frames
+        if labels.dim() == 3:                                         # beam search: [B, W, T], the best beam first
+            labels, lengths, frames = labels[:, 0], lengths[:, 0], frames[:, 0]
+        kw.setdefault("input", "probs" if self.model.softmax else "logits")
+        return ctc_base_qualities(calls.logits, labels, lengths, frames, input_lengths=calls.frame_lengths, **kw)

@@ -18,6 +18,11 @@ step the reference's evaluation notebook hands to EMBOSS needle,
     edit_distance(targets, target_lengths, labels, lengths)          # Levenshtein distance, int32 [B]
     print("\n".join(format_alignment(targets[0], labels[0], r.ops[0])))
 
+and per-base quality scores (csrc/wn_quality.hip): how much to trust each decoded base when the truth is not known,
+
+    q = ctc_base_qualities(logits, labels, lengths, frames)          # q.error, q.qual, q.dwell, q.read_error, q.mean_qscore
+    print("".join(fastq_records(names, labels, lengths, q.qual)))    # host: "@name\nSEQ\n+\nQUAL\n" per read
+
 Results stay on the device (int32 labels / frames / lengths, fp32 scores); nothing is copied to the host.  Scores are the
 natural log probability of each prefix summed over the alignments the search kept (higher is better), sorted descending.
 There is no CPU fallback: CPU tensors raise.
@@ -314,6 +319,107 @@ def format_alignment(ref_row, query_row, ops_row, alphabet=DEFAULT_ALPHABET):
         else:
             raise ValueError("format_alignment: op code %r" % (op,))
     return "".join(top), "".join(mid), "".join(bottom)
+
+
+QUALITY_STATS = {"mean": 0, "best": 1}
+MAX_QUAL = 93                       # the highest Phred value FASTQ can print ('~')
+
+BaseQualities = namedtuple("BaseQualities", "error qual dwell read_error mean_qscore")
+BaseQualities.__doc__ = """error [B, Lmax] fp32: the error probability of every base; qual [B, Lmax] uint8: its Phred quality in
+[0, 93] (the FASTQ character is qual + 33); dwell [B, Lmax] int32: the frames of its run; read_error [B] fp32: the mean error of
+the read's bases (NaN for an empty read); mean_qscore [B] fp32: qscale (-10 log10 read_error) + qbias.  All on the device."""
+
+
+def _label_rows(rows, B, what, name):
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
+    if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 2 or rows.shape[0] != B:
+        raise ValueError("wavenet_speech_amd.%s: %s must be int32 or int64 of shape (%d, Lmax), got %s %s"
+                         % (what, name, B, rows.dtype, tuple(rows.shape)))
+    rows = rows.detach()
+    if rows.dtype != torch.int32:
+        rows = rows.to(torch.int32)
+    if rows.shape[1] > 1 and rows.stride(1) != 1 or rows.stride(0) < 0:
+        rows = rows.contiguous()                                     # a row stride is read in place: labels[:, 0] of a beam search
+    return rows
+
+
+def ctc_base_qualities(x, labels, lengths, frames, input_lengths=None, blank=0, input="logits", layout="BCT", stat="mean",
+                       qscale=1.0, qbias=0.0):
+    """A Phred quality for every decoded base and a mean error per read.
+    x, input, layout, input_lengths: as ctc_beam_decode -- the tensor the labels were decoded from.  labels, frames [B, Lmax]
+    (int32 or int64, Lmax <= T) and lengths [B]: what ctc_greedy_decode returned, or one beam of ctc_beam_decode
+    (labels[:, 0], frames[:, 0], lengths[:, 0]: read in place through their row stride).
+    The run of a base is its emission frame and the frames after it, up to the next base's, for as long as the frame argmax
+    stays its label.  The error of a frame is the softmax mass of every OTHER class (formed directly, never 1 - p); the error
+    of the base is the mean over its run (stat="mean") or the least of it (stat="best").  Q = qscale (-10 log10 error) + qbias,
+    rounded and clamped to [0, 93]; qscale / qbias are where a calibration against known reads goes.
+    Returns BaseQualities; entries at and past lengths[b] are NaN / 0 / 0.  A base with a label outside [0, C) or equal to the
+    blank, or a frame outside its utterance or not above its predecessor's, has error NaN, qual 0, dwell 0, makes its read's
+    read_error NaN, and is reported through check_device_flags()."""
+    what = "ctc_base_qualities"
+    if input not in INPUT_KINDS:
+        raise ValueError("wavenet_speech_amd.%s: input must be one of %s, got %r" % (what, sorted(INPUT_KINDS), input))
+    if stat not in QUALITY_STATS:
+        raise ValueError("wavenet_speech_amd.%s: stat must be one of %s, got %r" % (what, sorted(QUALITY_STATS), stat))
+    qscale, qbias = float(qscale), float(qbias)
+    if not (0.0 < qscale < float("inf")) or not (-float("inf") < qbias < float("inf")):
+        raise ValueError("wavenet_speech_amd.%s: need a finite qscale > 0 and a finite qbias, got %r and %r" % (what, qscale, qbias))
+    x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, what)
+    if not 0 <= int(blank) < C:
+        raise ValueError("wavenet_speech_amd.%s: blank must be in [0, %d), got %d" % (what, C, int(blank)))
+    labels, frames = _label_rows(labels, B, what, "labels"), _label_rows(frames, B, what, "frames")
+    if labels.device != x.device or frames.device != x.device or labels.shape != frames.shape:
+        raise ValueError("wavenet_speech_amd.%s: labels and frames must have one shape, on the device of the input" % what)
+    lmax = width = int(labels.shape[1])
+    if lmax > T:
+        raise ValueError("wavenet_speech_amd.%s: at most one label per frame: Lmax = %d, T = %d" % (what, lmax, T))
+    lengths = torch.as_tensor(lengths)
+    if lengths.is_floating_point() or lengths.dtype == torch.bool or lengths.shape != (B,):
+        raise ValueError("wavenet_speech_amd.%s: lengths must be integers of shape (%d,), got %s %s"
+                         % (what, B, lengths.dtype, tuple(lengths.shape)))
+    dev = x.device
+    lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    if lmax == 0:                                                    # the C ABI wants one column; no read may use it
+        lmax, labels, frames = 1, torch.zeros(B, 1, dtype=torch.int32, device=dev), torch.zeros(B, 1, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    from .functional import _p, _stream
+    with torch.cuda.device(dev):
+        error = torch.empty(B, lmax, dtype=torch.float32, device=dev)
+        qual = torch.empty(B, lmax, dtype=torch.uint8, device=dev)
+        dwell = torch.empty(B, lmax, dtype=torch.int32, device=dev)
+        read_error = torch.empty(B, dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_ctc_base_quality(_p(x), sb, sc, st, INPUT_KINDS[input], _p(in_len), _p(labels), labels.stride(0), _p(frames),
+                                           frames.stride(0), _p(lengths), B, C, T, lmax, int(blank), QUALITY_STATS[stat], qscale,
+                                           qbias, _p(error), _p(qual), _p(dwell), _p(read_error), _p(bad), _stream()),
+                   "wn_ctc_base_quality")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_base_qualities: %d base(s) or read(s) with a "
+                          "label outside [0, %d) or equal to the blank (%d), a frame outside its utterance or out of order, or a "
+                          "length out of range" % (n, C, blank), at_once=False)
+        mean_qscore = torch.log10(read_error) * (-10.0 * qscale) + qbias
+    return BaseQualities(error[:, :width], qual[:, :width], dwell[:, :width], read_error, mean_qscore)
+
+
+def fastq_records(names, labels, lengths, qual, alphabet=DEFAULT_ALPHABET):
+    """host helper: one FASTQ record "@name\nSEQ\n+\nQUAL\n" per read from label rows [N, L], their lengths [N] and the qual
+    rows [N, L] of ctc_base_qualities (device or host; each is copied once).  SEQ is labels_to_strings' text, QUAL the
+    characters chr(qual + 33); an empty read has empty SEQ and QUAL lines."""
+    names = [str(n) for n in names]
+    seqs = labels_to_strings(labels, lengths, alphabet)
+    rows = torch.as_tensor(labels).cpu().tolist()
+    quals = torch.as_tensor(qual).cpu().tolist()
+    ns = [int(n) for n in torch.as_tensor(lengths).cpu().reshape(-1).tolist()]
+    if not (len(names) == len(rows) == len(quals) == len(ns)):
+        raise ValueError("fastq_records: %d names, %d label rows, %d qual rows, %d lengths" % (len(names), len(rows), len(quals), len(ns)))
+    out = []
+    for name, seq, row, q, n in zip(names, seqs, rows, quals, ns):
+        if any(not 0 <= int(v) <= MAX_QUAL for v in q[:n]):
+            raise ValueError("fastq_records: a quality outside [0, %d] in read %r" % (MAX_QUAL, name))
+        text = "".join(chr(int(v) + 33) for v, lab in zip(q[:n], row[:n]) if int(lab) != 0)   # a blank prints nothing in SEQ either
+        out.append("@%s\n%s\n+\n%s\n" % (name, seq, text))
+    return out
 
 
 def labels_to_strings(labels, lengths=None, alphabet=DEFAULT_ALPHABET):
