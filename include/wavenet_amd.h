@@ -465,6 +465,47 @@ int wn_ctc_base_quality(const float* x, long long sb, long long sc, long long st
                         float* error /* may be NULL */, unsigned char* qual /* may be NULL */, int* dwell /* may be NULL */,
                         float* read_error /* may be NULL */, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Quality calibration tables and the error profile of aligned reads (wavenet_speech_amd.decoding.quality_profile,
+ * DESIGN.md section 7i): walks the ops wn_pair_align wrote for (ref, query) pairs, decides for every query base whether it was
+ * right, and tabulates that against the quality and the dwell claimed for it.  Integer arithmetic only.  ops: rows of
+ * ops_stride bytes with ops_len [B] int32; ref / query / their lengths: as wn_pair_align takes them; qual: rows of qual_stride
+ * bytes, the uncalibrated qual of wn_ctc_base_quality; dwell: int32 rows of dwell_stride elements.  All pointers are DEVICE
+ * pointers.  For pair b, column c of its ops:
+ *     i_c, j_c   the number of ops in [0, c) with a code in {1, 2, 3} / in {1, 2, 4}: the reference / query index of the column
+ *     lo, hi     the first / last column whose op is 1 or 2.  With count_ends = 0 the columns outside [lo, hi] -- every column
+ *                when there is no such column -- are END COLUMNS (the unaligned heads and tails an end-gap-free alignment
+ *                leaves); with count_ends = 1 there are none
+ *   outcome    [B][max_query_len] bytes   of query base j, from its column: 1 match, 2 mismatch, 3 insertion (op 4, not an end
+ *                                         column), 4 end (op 4 in an end column); 0 for j >= query_lengths[b]
+ *   ref_index  [B][max_query_len] int32   i_c for outcomes 1 and 2, -1 otherwise
+ *   read_counts [B][5] int32              matches, mismatches, insertions, deletions (op 3, not an end column), end columns:
+ *                                         they sum to ops_len[b]
+ *   q_counts   [94][3] int64              row qual[b][j], column outcome - 1, for outcomes 1-3          (given with qual)
+ *   dwell_counts [33][3] int64            row min(dwell[b][j], 32), the same columns                     (given with dwell)
+ *   confusion  [classes + 1][classes + 1] int64, index `classes` = the gap: [ref[i]][query[j]] for match and mismatch columns,
+ *                                         [classes][query[j]] for insertions, [ref[i]][classes] for deletions
+ * The three tables are ADDED INTO (64-bit integer adds), never cleared: the caller zeroes them or carries them from batch to
+ * batch.  End columns enter no table.  Any output may be NULL, not all.  Two runs are bitwise identical.
+ * Checked on the device.  A pair is bad when ops_len[b] is outside [0, max_ops] or a length outside its range; an op in
+ * [0, ops_len) is not 1..4; the ops do not consume exactly ref_lengths[b] and query_lengths[b] labels; an op 1 lies where the
+ * labels differ or an op 2 where they are equal; a label they consume is outside [0, classes); a qual they consume is above 93
+ * or a dwell negative (end columns included).  Its outcome row is 0, its ref_index row -1, its read_counts -1, it adds nothing
+ * to any table and counts once in *bad (DEVICE int, caller-zeroed, may be NULL).  A poisoned pair of wn_pair_align (ops_len 0,
+ * a length out of range) is such a pair.  No bad value is used as an index.
+ * One workgroup per pair, two passes over its ops; no workspace.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_ref_len, max_query_len, max_ops or classes < 1, a
+ * negative stride, count_ends not 0 or 1.  WN_ERR_UNSUPPORTED: classes > 64, max_query_len > 8192, max_ref_len > 65535,
+ * max_ops > max_ref_len + max_query_len, batch > 65535.  WN_ERR_NULL: ops, ops_len, ref, ref_lengths, query or query_lengths;
+ * q_counts without qual or qual without q_counts, likewise dwell_counts and dwell; every output NULL. */
+int wn_quality_profile(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* ref, long long ref_stride,
+                       const int* ref_lengths, const int* query, long long query_stride, const int* query_lengths,
+                       const unsigned char* qual /* may be NULL */, long long qual_stride, const int* dwell /* may be NULL */,
+                       long long dwell_stride, int batch, int max_ref_len, int max_query_len, int max_ops, int classes,
+                       int count_ends, long long* q_counts /* with qual */, long long* dwell_counts /* with dwell */,
+                       long long* confusion /* may be NULL */, int* read_counts /* may be NULL */,
+                       unsigned char* outcome /* may be NULL */, int* ref_index /* may be NULL */, int* bad /* may be NULL */,
+                       wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -14,9 +14,10 @@ from .modules import (CausalConv1d, NonCausalConv1d, RawCTCNet, ResidualBlock, W
 from .modules.block import freeze_for_inference, set_precision  # noqa: F401
 from ._flags import check_device_flags  # noqa: F401
 from .graphs import GraphedStep  # noqa: F401
-from .decoding import (BaseQualities, CTCAlignment, CTCBeamDecoder, PairwiseAlignment, ctc_base_qualities,  # noqa: F401
-                       ctc_beam_decode, ctc_forced_align, ctc_greedy_decode, edit_distance, fastq_records, format_alignment,
-                       labels_to_strings, pairwise_align)
+from .decoding import (BaseQualities, CTCAlignment, CTCBeamDecoder, PairwiseAlignment, QualityCalibration,  # noqa: F401
+                       QualityProfile, ctc_base_qualities, ctc_beam_decode, ctc_forced_align, ctc_greedy_decode, edit_distance,
+                       fastq_records, fit_quality_calibration, format_alignment, labels_to_strings, pairwise_align,
+                       quality_profile)
 from .functional_half import check_fp16_overflow  # noqa: F401
 from .basecalling import Basecaller, Basecalls, ChunkPlan, chunk_plan, receptive_field  # noqa: F401
 from .normalise import read_med_mad, read_normalisation, read_order_statistics, read_quantiles  # noqa: F401

@@ -173,6 +173,9 @@ SIGNATURES = {
     "wn_ctc_base_quality": (c_int, [c_float_p, c_longlong, c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_longlong, c_void_p,
                                     c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float_p,
                                     c_void_p, c_void_p, c_float_p, c_void_p, c_void_p]),
+    "wn_quality_profile": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p,
+                                   c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wn_nll_partials":(c_size_t, [c_int, c_int]),
     "wn_nll_forward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wn_nll_backward": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_void_p]),

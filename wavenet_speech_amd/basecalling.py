@@ -11,6 +11,7 @@ and nothing is averaged.
     out = bc(raw_int16, signal_lengths, normalise="medmad")             # per-read median / MAD on the device (normalise.py)
     out.logits, out.frame_lengths, out.labels, out.label_lengths
     q = bc.qualities(out)                                 # Phred quality per base, mean error per read (decoding.py)
+    prof = bc.calibrate(out, truth, truth_lengths)        # calls against known truth: calibration tables, error profile
 
 What a basecall is: the logits of read b (n samples) are the T_b = n + feature_kwidth - 1 frames of the model's forward on the
 read FOLLOWED BY ZEROS, model(F.pad(read, (0, p)))[..., :T_b] for any p >= right -- what training on zero-padded ragged
@@ -29,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _flags, _lib, series
-from .decoding import ctc_base_qualities, ctc_beam_decode, ctc_greedy_decode
+from .decoding import ctc_base_qualities, ctc_beam_decode, ctc_greedy_decode, pairwise_align, quality_profile
 from .modules.block import freeze_for_inference
 from .modules.raw_ctcnet import RawCTCNet
 from .normalise import read_normalisation
@@ -350,3 +351,18 @@ class Basecaller(object):
             labels, lengths, frames = labels[:, 0], lengths[:, 0], frames[:, 0]
         kw.setdefault("input", "probs" if self.model.softmax else "logits")
         return ctc_base_qualities(calls.logits, labels, lengths, frames, input_lengths=calls.frame_lengths, **kw)
+
+    def calibrate(self, calls, truth, truth_lengths, into=None, **align_kw):
+        """The calls of reads whose true bases are known, tabulated for fit_quality_calibration (decoding.quality_profile): the
+        uncalibrated qualities and dwells of the calls (qscale=1, qbias=0), pairwise_align(truth, truth_lengths, the calls'
+        labels, their lengths, **align_kw) -- needle's defaults unless align_kw says otherwise; return_ops=False raises -- and quality_profile over the
+        classes of the logits.  into: the QualityProfile of earlier batches, accumulated in place.  Returns QualityProfile."""
+        q = self.qualities(calls)
+        labels, lengths = calls.labels, calls.label_lengths
+        if labels.dim() == 3:
+            labels, lengths = labels[:, 0], lengths[:, 0]
+        if not align_kw.pop("return_ops", True):
+            raise ValueError("wavenet_speech_amd.Basecaller.calibrate: the profile walks the ops; return_ops=False cannot be honoured")
+        alignment = pairwise_align(truth, truth_lengths, labels, lengths, return_ops=True, **align_kw)
+        return quality_profile(alignment, truth, truth_lengths, labels, lengths, qual=q.qual, dwell=q.dwell,
+                               classes=int(calls.logits.shape[1]), into=into)

@@ -402,6 +402,185 @@ def ctc_base_qualities(x, labels, lengths, frames, input_lengths=None, blank=0, 
     return BaseQualities(error[:, :width], qual[:, :width], dwell[:, :width], read_error, mean_qscore)
 
 
+QUAL_ROWS = MAX_QUAL + 1            # rows of q_counts
+DWELL_ROWS = 33                     # rows of dwell_counts: dwell 0..31, and 32 for everything above
+OUT_NONE, OUT_MATCH, OUT_MISMATCH, OUT_INSERTION, OUT_END = 0, 1, 2, 3, 4
+
+
+class QualityProfile(namedtuple("QualityProfile", "q_counts dwell_counts confusion read_counts outcome ref_index")):
+    """q_counts [94, 3] int64: per claimed quality the (matches, mismatches, insertions) among the query bases; dwell_counts
+    [33, 3] int64: the same per dwell (row 32 = 32 and above); confusion [C + 1, C + 1] int64: [true label][called label], index C
+    = the gap (row C: insertions, column C: deletions); read_counts [B, 5] int32: matches, mismatches, insertions, deletions,
+    end columns per read; outcome [B, M] uint8: 1 match, 2 mismatch, 3 insertion, 4 end, 0 past the read; ref_index [B, M] int32:
+    the reference position of a matched or mismatched base, -1 otherwise.  q_counts / dwell_counts are None when no qual / dwell
+    went in.  All on the device; the ratios below are torch ops on the device too."""
+    __slots__ = ()
+
+    @staticmethod
+    def _rate(table):
+        t = table.double()
+        return (t[:, 1] + t[:, 2]) / t.sum(1)
+
+    @property
+    def error_by_quality(self):
+        """[94] float64: (mismatches + insertions) / bases per claimed quality, NaN for an empty row"""
+        return self._rate(self.q_counts)
+
+    @property
+    def error_by_dwell(self):
+        """[33] float64: (mismatches + insertions) / bases per dwell, NaN for an empty row"""
+        return self._rate(self.dwell_counts)
+
+    @property
+    def substitution_rates(self):
+        """[C, C] float64: row t = the share of each called label among the aligned bases whose true label is t (NaN for a
+        label never seen); the diagonal is the per-class accuracy of the aligned bases"""
+        t = self.confusion[:-1, :-1].double()
+        return t / t.sum(1, keepdim=True)
+
+    @property
+    def rates(self):
+        """[B, 4] float64: mismatches, insertions, deletions per aligned column (end columns left out), and the identity
+        matches / aligned columns; NaN for a read without aligned columns or a bad read"""
+        c = self.read_counts.double()
+        cols = c[:, :4].sum(1)
+        cols = torch.where((cols > 0) & (c[:, 0] >= 0), cols, torch.full_like(cols, float("nan")))
+        return torch.stack([c[:, 1], c[:, 2], c[:, 3], c[:, 0]], 1) / cols[:, None]
+
+
+def _profile_rows(rows, B, M, dtype, what, name):
+    if rows is None:
+        return None
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
+    if rows.dtype != dtype or rows.dim() != 2 or rows.shape[0] != B or rows.shape[1] < M:
+        raise ValueError("wavenet_speech_amd.%s: %s must be %s of shape (%d, >= %d), got %s %s"
+                         % (what, name, dtype, B, M, rows.dtype, tuple(rows.shape)))
+    rows = rows.detach()
+    if rows.shape[1] == 0:                                           # a query without columns: one unused column, as _pair_rows
+        rows = torch.zeros(B, 1, dtype=dtype, device=rows.device)
+    if rows.shape[1] > 1 and rows.stride(1) != 1 or rows.stride(0) < 0:
+        rows = rows.contiguous()
+    return rows
+
+
+def _profile_table(into, field, shape, dev, what):
+    t = getattr(into, field) if into is not None else None
+    if t is None:
+        return torch.zeros(shape, dtype=torch.int64, device=dev)
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int64 tensor of shape %s on %s" % (what, field, shape, dev))
+    return t
+
+
+def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None, dwell=None, classes=5, count_ends=False,
+                    into=None):
+    """Walks each alignment of `pairwise_align(ref, ref_lengths, query, query_lengths)` and tabulates, for every query base,
+    whether it was right against the quality and the dwell claimed for it: the input of
+    fit_quality_calibration, and the error profile of a basecaller -- confusion matrix, insertions and deletions, error by dwell.
+    alignment: a PairwiseAlignment with ops; ref / query and their lengths: what it was made from; qual [B, >= M] uint8 and dwell
+    [B, >= M] int32: BaseQualities.qual (made with qscale=1, qbias=0) and .dwell of the query, either may be left out; classes:
+    labels lie in [0, classes).
+    End columns -- the unaligned head and tail that an alignment with end_gaps_free=True leaves before the first and after the last
+    match-or-mismatch column -- are no basecall errors and enter no table unless count_ends=True.  Deletions carry no quality:
+    they enter the confusion matrix and the per-read counts, not the quality or dwell tables.
+    into: an earlier QualityProfile whose three tables are accumulated in place (and returned); its per-read fields are replaced.
+    Returns QualityProfile.  A pair whose ops do not fit its labels (a poisoned pair of pairwise_align, a label outside [0, classes),
+    a qual above 93, a negative dwell, ...) has outcome 0, ref_index -1, read_counts -1, adds nothing to the tables and is
+    reported through check_device_flags()."""
+    what = "quality_profile"
+    if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
+        raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
+    ops, ops_len = alignment.ops, alignment.ops_len
+    if not isinstance(ops, torch.Tensor) or not ops.is_cuda or not isinstance(ops_len, torch.Tensor) or not ops_len.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: the alignment must be on the GPU (there is no CPU fallback)" % what)
+    width = int(query.shape[1]) if isinstance(query, torch.Tensor) and query.dim() == 2 else 0
+    ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
+    query, query_lengths = _pair_rows(query, query_lengths, what, "query")
+    B, N, M = int(ref.shape[0]), int(ref.shape[1]), int(query.shape[1])
+    dev = ref.device
+    C = int(classes)
+    if not 1 <= C <= MAX_CLASSES:
+        raise ValueError("wavenet_speech_amd.%s: classes must be in [1, %d], got %d" % (what, MAX_CLASSES, C))
+    if B < 1 or query.shape[0] != B or query.device != dev or ops.device != dev or ops_len.device != dev:
+        raise ValueError("wavenet_speech_amd.%s: ref, query and the alignment must hold the same rows (at least one) on one device" % what)
+    if N > MAX_PAIR_REF or M > MAX_PAIR_QUERY:
+        raise ValueError("wavenet_speech_amd.%s: at most %d reference and %d query labels per pair, got %d and %d"
+                         % (what, MAX_PAIR_REF, MAX_PAIR_QUERY, N, M))
+    if ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] != B or ops_len.dtype != torch.int32 or ops_len.shape != (B,):
+        raise ValueError("wavenet_speech_amd.%s: alignment.ops must be uint8 of shape (%d, n) and ops_len int32 of shape (%d,)" % (what, B, B))
+    max_ops = min(int(ops.shape[1]), N + M)
+    if max_ops < 1:                                                  # both sides without columns: one unused column
+        ops, max_ops = torch.zeros(B, 1, dtype=torch.uint8, device=dev), 1
+    if ops.shape[1] > 1 and ops.stride(1) != 1 or ops.stride(0) < 0:
+        ops = ops.contiguous()
+    ops_len = ops_len.contiguous()
+    qual = _profile_rows(qual, B, width, torch.uint8, what, "qual")
+    dwell = _profile_rows(dwell, B, width, torch.int32, what, "dwell")
+    if (qual is not None and qual.device != dev) or (dwell is not None and dwell.device != dev):
+        raise ValueError("wavenet_speech_amd.%s: qual and dwell must be on the device of the labels" % what)
+    if into is not None and not isinstance(into, QualityProfile):
+        raise ValueError("wavenet_speech_amd.%s: into must be a QualityProfile, got %s" % (what, type(into).__name__))
+    if into is not None and ((into.q_counts is None) != (qual is None) or (into.dwell_counts is None) != (dwell is None)):
+        raise ValueError("wavenet_speech_amd.%s: into carries a table for which no qual / dwell is given, or the reverse" % what)
+    lib = _lib.load()
+    from .functional import _p, _stream
+    with torch.cuda.device(dev):
+        q_counts = _profile_table(into, "q_counts", (QUAL_ROWS, 3), dev, what) if qual is not None else None
+        dwell_counts = _profile_table(into, "dwell_counts", (DWELL_ROWS, 3), dev, what) if dwell is not None else None
+        confusion = _profile_table(into, "confusion", (C + 1, C + 1), dev, what)
+        read_counts = torch.empty(B, 5, dtype=torch.int32, device=dev)
+        outcome = torch.empty(B, M, dtype=torch.uint8, device=dev)
+        ref_index = torch.empty(B, M, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_quality_profile(_p(ops), ops.stride(0), _p(ops_len), _p(ref), ref.stride(0), _p(ref_lengths), _p(query),
+                                          query.stride(0), _p(query_lengths), _p(qual), qual.stride(0) if qual is not None else 0,
+                                          _p(dwell), dwell.stride(0) if dwell is not None else 0, B, N, M, max_ops, C,
+                                          int(bool(count_ends)), _p(q_counts), _p(dwell_counts), _p(confusion), _p(read_counts),
+                                          _p(outcome), _p(ref_index), _p(bad), _stream()), "wn_quality_profile")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n, C=C: "wavenet_speech_amd.quality_profile: %d pair(s) whose ops do not fit their labels: a "
+                          "length out of range, an op outside 1..4, labels consumed or compared wrongly, a label outside [0, %d), a "
+                          "qual above %d or a negative dwell" % (n, C, MAX_QUAL), at_once=False)
+    return QualityProfile(q_counts, dwell_counts, confusion, read_counts, outcome[:, :width], ref_index[:, :width])
+
+
+QualityCalibration = namedtuple("QualityCalibration", "qscale qbias bins_used bases_used q_empirical")
+QualityCalibration.__doc__ = """qscale, qbias: Python floats, the slope and intercept that go into ctc_base_qualities /
+Basecaller.qualities; bins_used: how many quality values carried at least min_count bases; bases_used: the bases in them;
+q_empirical [94] float64 on the device of the table: the empirical Phred quality of each used bin, NaN elsewhere."""
+
+
+def fit_quality_calibration(q_counts, min_count=100):
+    """A straight line through the binned empirical error: for every claimed quality q with at least
+    min_count bases, p_q = (mismatches + insertions + 0.5) / (bases + 1) and Qe_q = -10 log10 p_q; qscale and qbias are the least
+    squares line Qe = qscale q + qbias over the used bins, weighted by their bases.  q_counts: QualityProfile.q_counts ([94, 3]
+    int64), made from qualities with qscale=1, qbias=0.  float64 torch ops on the table's device; one read-back at the end.
+    Raises ValueError for fewer than two used bins or a slope that is not finite and positive.  Returns QualityCalibration."""
+    what = "fit_quality_calibration"
+    if not isinstance(q_counts, torch.Tensor) or tuple(q_counts.shape) != (QUAL_ROWS, 3) or q_counts.is_floating_point():
+        raise ValueError("wavenet_speech_amd.%s: q_counts must be an integer tensor of shape (%d, 3)" % (what, QUAL_ROWS))
+    if int(min_count) < 1:
+        raise ValueError("wavenet_speech_amd.%s: min_count must be at least 1, got %r" % (what, min_count))
+    t = q_counts.double()
+    n = t.sum(1)
+    used = n >= float(int(min_count))
+    w = torch.where(used, n, torch.zeros_like(n))
+    qe = -10.0 * torch.log10((t[:, 1] + t[:, 2] + 0.5) / (n + 1.0))
+    q = torch.arange(QUAL_ROWS, dtype=torch.float64, device=t.device)
+    total = w.sum()
+    q_mean, qe_mean = (w * q).sum() / total, (w * qe).sum() / total
+    slope = (w * (q - q_mean) * (qe - qe_mean)).sum() / (w * (q - q_mean) ** 2).sum()
+    bias = qe_mean - slope * q_mean
+    slope, bias, bins, bases = torch.stack([slope, bias, used.sum().double(), total]).tolist()       # the one read-back
+    if bins < 2:
+        raise ValueError("wavenet_speech_amd.%s: %d quality value(s) with at least %d bases; a line needs two" % (what, int(bins), int(min_count)))
+    if not (0.0 < slope < float("inf")) or not (-float("inf") < bias < float("inf")):
+        raise ValueError("wavenet_speech_amd.%s: the fitted line (slope %r, intercept %r) is no calibration: the error does not fall "
+                         "as the claimed quality rises" % (what, slope, bias))
+    return QualityCalibration(slope, bias, int(bins), int(bases), torch.where(used, qe, torch.full_like(qe, float("nan"))))
+
+
 def fastq_records(names, labels, lengths, qual, alphabet=DEFAULT_ALPHABET):
     """host helper: one FASTQ record "@name\nSEQ\n+\nQUAL\n" per read from label rows [N, L], their lengths [N] and the qual
     rows [N, L] of ctc_base_qualities (device or host; each is copied once).  SEQ is labels_to_strings' text, QUAL the
