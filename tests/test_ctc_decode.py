@@ -1,11 +1,14 @@
 """CPU: the plain-Python CTC decoders of tests/ctc_decode_ref.py (the reference the GPU decoders are held to, test_gpu_decode.py)
 against ground truth -- exact enumeration of every alignment, the CTC loss oracle as an upper bound, argmax + collapse -- and the
-host-side pieces of wavenet_speech_amd.decoding (argument checks, string helpers) that run without a GPU."""
+host-side pieces of wavenet_speech_amd.decoding (argument checks, string helpers) that run without a GPU.  Also the tie-group
+matcher of ctc_decode_ref (what it accepts and what it rejects) and, on the reference alone, the conditions the inputs of
+test_gpu_decode_edges.py (tests/ctc_decode_cases.py) must meet: at least 90 % of the finite beams of every case are checked."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import ctc_oracle as CO
+from tests import ctc_decode_cases as K
 from tests import ctc_decode_ref as R
 
 
@@ -149,3 +152,172 @@ def test_label_strings():
     assert S.labels2strings(torch.tensor([[1, 0, 2, 2, 0, 4]])) == ["AGGT"]  # no collapse: blanks are ''
     logits = torch.randn(2, 7, 5)
     assert torch.equal(S.argmax_decode(logits), logits.max(dim=2)[1])
+
+
+# ---- the tie-group matcher the GPU decoders are compared through (ctc_decode_ref.match_beams)
+
+def _matcher_fixture():
+    """one utterance, W = 8, T = 4: scores with a clear rank 0, a run of three (ranks 1-3), a clear rank 4, a run of two (5-6),
+    and rank 7 dead"""
+    scores = np.array([[-1.0, -2.0, -2.0005, -2.001, -3.0, -4.0, -4.0008, -np.inf]])
+    rows = [(1,), (2, 1), (1, 2), (3,), (1, 1), (2,), (2, 2), ()]
+    labels = np.zeros((1, 8, 4), dtype=np.int64)
+    lengths = np.zeros((1, 8), dtype=np.int64)
+    for w, r in enumerate(rows):
+        labels[0, w, :len(r)] = r
+        lengths[0, w] = len(r)
+    return labels, lengths, scores
+
+
+def _swap(result, u, v):
+    labels, lengths, scores = (a.copy() for a in result)
+    labels[0, [u, v]] = labels[0, [v, u]]
+    lengths[0, [u, v]] = lengths[0, [v, u]]
+    return labels, lengths, scores
+
+
+def test_tie_runs_split_at_gaps_above_the_threshold():
+    assert R.tie_runs(np.array([-1.0, -2.0, -2.0005, -2.001, -3.0, -4.0, -4.0008])) == [(0, 1), (1, 4), (4, 5), (5, 7)]
+    assert R.tie_runs(np.array([])) == [] and R.tie_runs(np.array([-5.0])) == [(0, 1)]
+    assert R.tie_runs(np.array([-1.0, -1.0 - 1e-3 * 1.01])) == [(0, 1), (1, 2)]
+
+
+def test_matcher_accepts_the_reference_and_a_swap_inside_a_run():
+    want = _matcher_fixture()
+    assert R.match_beams(want, want, 4) == 1.0                       # 7 finite ranks of 8: nothing was pruned, no run is open
+    assert R.match_beams(want, _swap(want, 1, 3), 4) == 1.0
+    assert R.match_beams(want, _swap(want, 5, 6), 4) == 1.0
+
+
+def test_matcher_leaves_only_the_run_at_the_pruning_edge_unchecked():
+    labels, lengths, scores = _matcher_fixture()
+    full = (labels[:, :7], lengths[:, :7], scores[:, :7])            # W = 7: every rank finite, the run 5-6 holds the last kept rank
+    assert R.match_beams(full, full, 4) == pytest.approx(5 / 7)
+    other = tuple(a.copy() for a in full)
+    other[0][0, 6, :2] = (3, 1)                                      # another member of the open run: accepted, in range
+    assert R.match_beams(full, other, 4) == pytest.approx(5 / 7)
+    assert R.match_beams(full, other, 4, next_scores=np.array([-4.0012])) == pytest.approx(5 / 7)   # the pruned one is as close
+    with pytest.raises(AssertionError):
+        R.match_beams(full, other, 4, next_scores=np.array([-4.5]))  # the pruned candidate is clear of the run: the run is closed
+    assert R.match_beams(full, full, 4, next_scores=np.array([-4.5])) == 1.0
+    assert R.match_beams(full, full, 4, next_scores=np.array([-np.inf])) == 1.0
+    for bad_row, bad_len in (((4, 1), 2), ((0, 1), 2), ((1, 1, 1, 1), 5)):   # label >= classes, the blank, longer than T
+        broken = tuple(a.copy() for a in full)
+        broken[0][0, 6, :len(bad_row)] = bad_row
+        broken[1][0, 6] = bad_len
+        with pytest.raises(AssertionError):
+            R.match_beams(full, broken, 4)
+
+
+def test_matcher_rejects_what_is_wrong():
+    want = _matcher_fixture()
+    one_label = tuple(a.copy() for a in want)
+    one_label[0][0, 4, 1] = 2                                        # clear rank 4: (1, 1) -> (1, 2)
+    with pytest.raises(AssertionError, match="ranks 4..4"):
+        R.match_beams(want, one_label, 4)
+    with pytest.raises(AssertionError, match="labellings"):
+        R.match_beams(want, _swap(want, 3, 4), 4)                    # across two runs
+    with pytest.raises(AssertionError, match="labellings"):
+        R.match_beams(want, _swap(want, 0, 1), 4)
+    off = tuple(a.copy() for a in want)
+    off[2][0, 2] += 1e-2
+    with pytest.raises(AssertionError, match="score off"):
+        R.match_beams(want, off, 4)
+    dead = tuple(a.copy() for a in want)
+    dead[2][0, 6] = -np.inf
+    with pytest.raises(AssertionError, match="finite ranks"):
+        R.match_beams(want, dead, 4)
+    alive = tuple(a.copy() for a in want)
+    alive[2][0, 7] = -5.0
+    with pytest.raises(AssertionError, match="finite ranks"):
+        R.match_beams(want, alive, 4)
+    nan = tuple(a.copy() for a in want)
+    nan[2][0, 7] = np.nan
+    with pytest.raises(AssertionError):
+        R.match_beams(want, nan, 4)
+
+
+def test_matcher_scores_are_held_to_the_relative_bound():
+    labels, lengths, scores = _matcher_fixture()
+    far = (labels, lengths, scores * 1000.0)                         # -1000 ... -4000.8: every rank clear
+    near = (labels, lengths, far[2] + 0.09)                          # within 1e-4 |s| + 1e-3 of -1000
+    assert R.match_beams(far, near, 4) == 1.0
+    with pytest.raises(AssertionError, match="score off"):
+        R.match_beams(far, (labels, lengths, far[2] + 0.11), 4)
+
+
+def test_the_pruned_score_is_the_next_beam_of_a_wider_search():
+    rng = np.random.default_rng(11)
+    x = rng.normal(size=(4, 3)) * 1.5                                # T = 3: 16 beams prune nothing, so they are the exact order
+    wide = R.beam_decode(x, 64)
+    beams, pruned = R.beam_decode(x, len(wide), with_next=True)
+    assert pruned == -np.inf and beams == wide
+    l, f, n, s, nxt = R.beam_decode_batch(x[None], 64, with_next=True)
+    assert nxt.tolist() == [-np.inf] and R.beam_decode_batch(x[None], 64)[3].tolist() == s.tolist()
+    # one frame: the candidates are (), (1,), (2,), (3,) with scores log y: the first pruned one of W = 2 is the third largest
+    y = np.sort(R.log_probs(x[:, :1])[:, 0])[::-1]
+    assert R.beam_decode(x[:, :1], 2, with_next=True)[1] == pytest.approx(y[2], abs=1e-12)
+
+
+# ---- the inputs of tests/test_gpu_decode_edges.py: conditions that the reference alone decides
+
+@pytest.mark.parametrize("name", sorted(K.BEAM_CASES))
+def test_edge_cases_leave_few_beams_unchecked(name):
+    c = K.beam_case(name)
+    want, nxt = c.want()
+    share = R.match_beams(want, want, c.C, c.blank, nxt, c.input_lengths)
+    assert share >= K.MIN_SHARE, share
+    assert np.isfinite(want[2]).any()
+    if c.truth is not None and name.startswith("blank"):
+        assert tuple(want[0][0, 0, :want[1][0, 0]].tolist()) == c.truth and 0 in c.truth
+
+
+def test_edge_cases_hold_what_their_tests_rely_on():
+    (l, n, s), _ = K.beam_case("limits_peaked").want()
+    seen = set(l[0][np.arange(l.shape[2])[None, :] < n[0][:, None]].tolist())
+    assert 63 in seen and len(seen) >= 56 and min(seen) >= 1         # labels far above 4 on the kept beams, the top class among them
+    (l, n, s), _ = K.beam_case("long_flat").want()
+    assert -3400.0 < s[0, 0] < -3200.0
+    for kind in ("probs", "log_probs"):
+        c = K.beam_case("zeros_%s" % kind)
+        (l, n, s), _ = c.want()
+        assert np.isneginf(s[3]).all() and (n[3] == 0).all()         # nothing survives the all-zero frame
+        assert np.isfinite(s[[0, 1, 4]]).all()
+        live = int(np.isfinite(s[2]).sum())
+        assert 1 < live < c.W and (n[2, live:] == 0).all()           # fewer live prefixes than beams
+        assert (c.x[0, 0] == (0.0 if kind == "probs" else -np.inf)).all()
+    c = K.beam_case("ragged")
+    assert (np.abs(c.x[0]) >= 30.0).all() and c.input_lengths.tolist() == list(K.RAGGED_LENGTHS)
+    a, b = K.beam_case("fixed_point"), K.beam_case("fixed_point_shifted")
+    assert np.array_equal(b.x.astype(np.float64) - K.SHIFT, a.x.astype(np.float64))   # the shift is exact in fp32
+    a, b = K.beam_case("integers"), K.beam_case("integers_shifted")
+    assert np.array_equal(b.x.astype(np.float64) - K.SHIFT, a.x.astype(np.float64)) and np.array_equal(a.x, np.round(a.x))
+
+
+def test_exact_tie_case_ties_bitwise_and_nowhere_else():
+    """classes 2 and 3 share their columns: after every step the only score gaps of at most TIE_GAP are exact zeros, between
+    labellings that are each other's 2 <-> 3 swap -- so the order of the tied ranks is the candidate-key rule's alone"""
+    c = K.beam_case("exact_ties")
+    swap = {1: 1, 2: 3, 3: 2}
+    ties = 0
+    for b in range(c.B):
+        for tb in (1, 2, 3):
+            beams, pruned = R.beam_decode(c.x[b], c.W, input_length=tb, with_next=True)
+            assert pruned == -np.inf                                 # nothing is pruned
+            scores = np.array([s for _, _, s in beams])
+            for lo, hi in R.tie_runs(scores):
+                assert scores[lo] == scores[hi - 1]                  # a run is an exact tie ...
+                group = {beams[w][0] for w in range(lo, hi)}
+                assert group == {tuple(swap[v] for v in p) for p in group}    # ... closed under the swap
+                ties += hi - lo > 1
+    assert ties >= 20
+
+
+def test_greedy_boundary_case_is_what_it_says():
+    x, lens, blank, path = K.greedy_boundaries()
+    assert np.array_equal(np.argmax(x, axis=1), path)
+    labels, frames, n = R.greedy_decode_batch(x, blank, lens)
+    assert labels[0, :n[0]].tolist() == [2, 0, 4, 1] and frames[0, :n[0]].tolist() == [62, 100, 254, 511]
+    assert [int(v) for v in n] == [4, 3, 3, 4, 3, 3]
+    assert frames[3, :4].tolist() == [62, 100, 250, 256]             # the blank at 255 splits label 1 in two emissions
+    assert frames[1, :3].tolist() == [62, 100, 254] and frames[4, :3].tolist() == [62, 100, 250]
