@@ -697,6 +697,43 @@ int wn_hconv_backward_weights(const wn_conv_shape* s, int precision, const void*
                               float* dweight, float* dbias /* may be NULL */, const float* dyn_inv_scale /* may be NULL */,
                               void* workspace, size_t workspace_bytes, wn_stream_t stream);
 
+/* ---- the fp32 convolutions AROUND the block stack kept in the series layout (reference modules/wavenet.py:54,67-71,93,103:
+ * entry_conv1d and output_stack): the entry conv writes the stack's input series, the output block reads the stack's result
+ * as a series, and LeakyReLU rides in the epilogues -- no dense round trips and no stand-alone activation passes between them.
+ *   wn_skipsum_forward_series     out = leaky_relu(sum_l W_skip_l z_l + bias_total) as a series (one group: nblocks <=
+ *                                 WN_MAX_STACK_GROUP), the activated input of the output block's first conv
+ *   wn_conv_forward_series        y = leaky_relu(conv(x) + b), series in, series out (wn_conv_forward is the form without activation)
+ *   wn_conv_backward_data_series  dx = (W^T dy) * leaky_relu'(act); act = the conv's stored (activated) input, shaped like dx;
+ *                                 NULL = no activation (wn_conv_backward_data)
+ * The activation is torch's rule v > 0 ? v : v * slope, its derivative act > 0 ? 1 : slope (act == 0 takes the slope): for
+ * slope >= 0 the stored leaky_relu(v) has the sign of v, so results are bitwise those of the separate torch passes. */
+int wn_skipsum_forward_series(const wn_skipsum_shape* s, const void* packed, const float* const* z, float* out_series,
+                              float leaky_slope, wn_stream_t stream);
+int wn_conv_forward_series(const wn_conv_shape* s, const void* packed, const float* x, float* y, float leaky_slope,
+                           wn_stream_t stream);
+int wn_conv_backward_data_series(const wn_conv_shape* s, const void* packed, const float* dy, const float* act,
+                                 float leaky_slope, float* dx, wn_stream_t stream);
+
+/* ---- every fp32 weight-pack job of a stack in ONE launch: the fp32 counterpart of wn_hstack_pack_*.
+ * The table covers each block's four arrangements (the image wn_block_pack writes), with_skipsum != 0 the long-K skips_sum
+ * weights of each group of WN_MAX_STACK_GROUP blocks (the image wn_skipsum_pack writes from the blocks' w_skip;
+ * skip_bias_total, [Ms] or NULL, is the bias of group 0) and `convs`, stand-alone convs around the stack (the image
+ * wn_conv_pack writes).  Images are byte-identical to those of the per-object entry points and start at
+ * packed + block_offsets[l] / skipsum_offsets[g] / conv_offsets[c] (multiples of 256).  wn_stack_pack_table_build is host-only:
+ * it fills `table_host` (wn_stack_pack_table_bytes(nblocks, nconvs) bytes), which the caller copies to the device once and
+ * keeps; each step wn_stack_pack_run(table_dev, ...) packs into `packed` (*packed_total bytes, may be another allocation every
+ * time).  `dynamic` (<= 3 ranges): sources inside one of these address ranges are stored as offsets and each run supplies
+ * the ranges' current bases, in the same order.  Rebuild the table when any other pointer or a shape changes. */
+typedef struct wn_pack_conv { wn_conv_shape shape; const float* weight /*[Co][Ci][k]*/; const float* bias /*[Co] or NULL*/; } wn_pack_conv;
+size_t wn_stack_pack_table_bytes(int nblocks, int nconvs);
+int wn_stack_pack_table_build(const wn_block_shape* shapes, const wn_block_params* params, int nblocks, int with_skipsum,
+                              const float* skip_bias_total, const wn_pack_conv* convs, int nconvs,
+                              const wn_mem_range* dynamic, int ndynamic, void* table_host, size_t table_bytes,
+                              size_t* block_offsets, size_t* skipsum_offsets, size_t* conv_offsets, size_t* packed_total,
+                              int* njobs, int* launch_blocks);
+int wn_stack_pack_run(const void* table_dev, int njobs, int launch_blocks, const void* const* dynamic_bases, int ndynamic,
+                      void* packed, wn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

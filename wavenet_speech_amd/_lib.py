@@ -50,6 +50,11 @@ class ConvShape(Structure):
                 ("kernel_width", c_int), ("dilation", c_int), ("causal", c_int), ("ld", c_int), ("halo", c_int)]
 
 
+class PackConv(Structure):
+    """wn_pack_conv"""
+    _fields_ = [("shape", ConvShape), ("weight", c_float_p), ("bias", c_float_p)]
+
+
 # every symbol include/wavenet_amd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "wn_version": (c_int, []),
@@ -79,6 +84,14 @@ SIGNATURES = {
     "wn_conv_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvShape)]),
     "wn_conv_backward_weights": (c_int, [POINTER(ConvShape), c_float_p, c_float_p, c_float_p, c_float_p,
                                          c_void_p, c_size_t, c_void_p]),
+    "wn_skipsum_forward_series": (c_int, [POINTER(SkipSumShape), c_void_p, POINTER(c_void_p), c_float_p, c_float, c_void_p]),
+    "wn_conv_forward_series": (c_int, [POINTER(ConvShape), c_void_p, c_float_p, c_float_p, c_float, c_void_p]),
+    "wn_conv_backward_data_series": (c_int, [POINTER(ConvShape), c_void_p, c_float_p, c_float_p, c_float, c_float_p, c_void_p]),
+    "wn_stack_pack_table_bytes": (c_size_t, [c_int, c_int]),
+    "wn_stack_pack_table_build": (c_int, [POINTER(BlockShape), POINTER(BlockParams), c_int, c_int, c_float_p, POINTER(PackConv), c_int,
+                                          POINTER(MemRange), c_int, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_size_t),
+                                          POINTER(c_size_t), POINTER(c_size_t), POINTER(c_int), POINTER(c_int)]),
+    "wn_stack_pack_run": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_void_p]),
     "wn_hseries_layout": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "wn_hseries_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wn_hseries_residual_scale": (c_float, []),

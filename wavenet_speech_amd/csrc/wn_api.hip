@@ -366,17 +366,12 @@ size_t wn_block_packed_bytes(const wn_block_shape* s) {
     return plan_block(s).total;
 }
 
-int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packed, wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_block(s, off);
-    if (rc != WN_OK) return rc;
-    if (!p || !packed || !p->w_tanh || !p->w_sigmoid || !p->w_res || !p->w_skip || !p->w_proj) return WN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    const BlockPlan bp = plan_block(s);
+namespace {
+// the four pack jobs of one block (gate, res+skip, dz, dx arrangements), destinations relative to `packed`
+void block_pack_jobs(const wn_block_shape* s, const wn_block_params* p, const BlockPlan& bp, void* packed, PackArgs (&out)[4]) {
     const int Ci = s->in_channels, Co = s->out_channels, Ms = s->skip_rows, k = s->kernel_width;
-    ProfScope prof(KC_PACK, 0.0, st);
-    PackArgs a;
     {   // FA
+        PackArgs& a = out[0];
         const GemmPlan& g = bp.fa;
         fill_pack_common(a, g, packed, bp.off_fa);
         for (int j = 0; j < k; ++j) {
@@ -392,9 +387,9 @@ int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packe
                 a.tile[sl * g.MT + m].set = m & 1;
                 a.tile[sl * g.MT + m].row0 = pair < pairs ? 32 * pair : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(gate)");
     }
     {   // FB
+        PackArgs& a = out[1];
         const GemmPlan& g = bp.fb;
         fill_pack_common(a, g, packed, bp.off_fb);
         a.set[0].seg[0] = mk_src(p->w_res, Co, Co, Co, 1);
@@ -409,9 +404,9 @@ int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packe
                 a.tile[sl * g.MT + m].set = skip ? 1 : 0;
                 a.tile[sl * g.MT + m].row0 = row0 < (skip ? Ms : Co) ? row0 : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(res+skip)");
     }
     {   // KA: rows = z channel c ; seg0 cols = skip row m : w_skip[m][c] ; seg1 cols = r row m : w_res[m][c]
+        PackArgs& a = out[2];
         const GemmPlan& g = bp.ka;
         fill_pack_common(a, g, packed, bp.off_ka);
         a.set[0].seg[0] = mk_src(p->w_skip, Co, Ms, 1, Co);
@@ -422,9 +417,9 @@ int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packe
                 a.tile[sl * g.MT + m].set = 0;
                 a.tile[sl * g.MT + m].row0 = row0 < Co ? row0 : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(dz)");
     }
     {   // KB: rows = input channel ci ; cols = output channel co
+        PackArgs& a = out[3];
         const GemmPlan& g = bp.kb;
         fill_pack_common(a, g, packed, bp.off_kb);
         for (int j = 0; j < k; ++j) {
@@ -438,8 +433,25 @@ int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packe
                 a.tile[sl * g.MT + m].set = 0;
                 a.tile[sl * g.MT + m].row0 = row0 < Ci ? row0 : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(dx)");
     }
+}
+inline bool block_params_complete(const wn_block_params* p) {
+    return p && p->w_tanh && p->w_sigmoid && p->w_res && p->w_skip && p->w_proj;
+}
+}  // namespace
+
+int wn_block_pack(const wn_block_shape* s, const wn_block_params* p, void* packed, wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_block(s, off);
+    if (rc != WN_OK) return rc;
+    if (!packed || !block_params_complete(p)) return WN_ERR_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    const BlockPlan bp = plan_block(s);
+    ProfScope prof(KC_PACK, 0.0, st);
+    PackArgs jobs[4];
+    block_pack_jobs(s, p, bp, packed, jobs);
+    static const char* const what[4] = {"pack(gate)", "pack(res+skip)", "pack(dz)", "pack(dx)"};
+    for (int i = 0; i < 4; ++i) WN_HIP(launch_pack(jobs[i], st), what[i]);
     return WN_OK;
 }
 
@@ -557,6 +569,21 @@ size_t wn_skipsum_packed_bytes(const wn_skipsum_shape* s) {
     return plan_skipsum(s).bytes();
 }
 
+namespace {
+void skipsum_pack_job(const wn_skipsum_shape* s, const GemmPlan& g, const float* const* w_skip, const float* bias_total,
+                      void* packed, PackArgs& a) {
+    fill_pack_common(a, g, packed, 0);
+    for (int l = 0; l < s->nblocks; ++l) a.set[0].seg[l] = mk_src(w_skip[l], s->skip_rows, s->channels[l], s->channels[l], 1);
+    a.set[0].bias0 = bias_total; a.set[0].bias_rows = s->skip_rows;
+    for (int sl = 0; sl < g.nslab; ++sl)
+        for (int m = 0; m < g.MT; ++m) {
+            const int row0 = g.slab_row0[sl] + 32 * m;
+            a.tile[sl * g.MT + m].set = 0;
+            a.tile[sl * g.MT + m].row0 = row0 < s->skip_rows ? row0 : -1;
+        }
+}
+}  // namespace
+
 int wn_skipsum_pack(const wn_skipsum_shape* s, const float* const* w_skip, const float* bias_total, void* packed,
                     wn_stream_t stream) {
     int rc = check_skipsum(s);
@@ -567,21 +594,14 @@ int wn_skipsum_pack(const wn_skipsum_shape* s, const float* const* w_skip, const
     const GemmPlan g = plan_skipsum(s);
     ProfScope prof(KC_PACK, 0.0, st);
     PackArgs a;
-    fill_pack_common(a, g, packed, 0);
-    for (int l = 0; l < s->nblocks; ++l) a.set[0].seg[l] = mk_src(w_skip[l], s->skip_rows, s->channels[l], s->channels[l], 1);
-    a.set[0].bias0 = bias_total; a.set[0].bias_rows = s->skip_rows;
-    for (int sl = 0; sl < g.nslab; ++sl)
-        for (int m = 0; m < g.MT; ++m) {
-            const int row0 = g.slab_row0[sl] + 32 * m;
-            a.tile[sl * g.MT + m].set = 0;
-            a.tile[sl * g.MT + m].row0 = row0 < s->skip_rows ? row0 : -1;
-        }
+    skipsum_pack_job(s, g, w_skip, bias_total, packed, a);
     WN_HIP(launch_pack(a, st), "pack(skipsum)");
     return WN_OK;
 }
 
-int wn_skipsum_forward(const wn_skipsum_shape* s, const void* packed, const float* const* z, float* skip, int accumulate,
-                       wn_stream_t stream) {
+namespace {
+int skipsum_forward(const wn_skipsum_shape* s, const void* packed, const float* const* z, float* skip, int accumulate,
+                    bool leaky, float slope, wn_stream_t stream) {
     int rc = check_skipsum(s);
     if (rc != WN_OK) return rc;
     if (!packed || !z || !skip) return WN_ERR_NULL;
@@ -593,9 +613,21 @@ int wn_skipsum_forward(const wn_skipsum_shape* s, const void* packed, const floa
     double ksum = 0;
     for (int l = 0; l < s->nblocks; ++l) { set_seg(a, l, z[l], s->channels[l], 0, g.seg_nkb[l]); ksum += s->channels[l]; }
     a.dst[0].base = skip; a.dst[0].cp = cp8(s->skip_rows); a.dst[0].rows = s->skip_rows; a.dst[0].accumulate = accumulate ? 1 : 0;
+    a.slope = slope;
     ProfScope prof(KC_SKIP_GEMM, 2.0 * s->skip_rows * ksum * (double)s->batch * s->length, st);
-    WN_HIP(launch_gemm(g.MT, accumulate ? EPI_ACCUM : EPI_LINEAR, a, st), "series_gemm<skipsum>");
+    WN_HIP(launch_gemm(g.MT, leaky ? EPI_LEAKY : (accumulate ? EPI_ACCUM : EPI_LINEAR), a, st), "series_gemm<skipsum>");
     return WN_OK;
+}
+}  // namespace
+
+int wn_skipsum_forward(const wn_skipsum_shape* s, const void* packed, const float* const* z, float* skip, int accumulate,
+                       wn_stream_t stream) {
+    return skipsum_forward(s, packed, z, skip, accumulate, false, 1.0f, stream);
+}
+
+int wn_skipsum_forward_series(const wn_skipsum_shape* s, const void* packed, const float* const* z, float* out_series,
+                              float leaky_slope, wn_stream_t stream) {
+    return skipsum_forward(s, packed, z, out_series, 0, true, leaky_slope, stream);
 }
 
 // ---- weight gradients --------------------------------------------------------------------------
@@ -756,17 +788,12 @@ size_t wn_conv_packed_bytes(const wn_conv_shape* s) {
     return plan_conv(s).total;
 }
 
-int wn_conv_pack(const wn_conv_shape* s, const float* weight, const float* bias, void* packed, wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_conv(s, off);
-    if (rc != WN_OK) return rc;
-    if (!weight || !packed) return WN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    const ConvPlan cp = plan_conv(s);
+namespace {
+void conv_pack_jobs(const wn_conv_shape* s, const ConvPlan& cp, const float* weight, const float* bias, void* packed,
+                    PackArgs (&out)[2]) {
     const int Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
-    ProfScope prof(KC_PACK, 0.0, st);
-    PackArgs a;
     {
+        PackArgs& a = out[0];
         const GemmPlan& g = cp.cf;
         fill_pack_common(a, g, packed, cp.off_cf);
         for (int j = 0; j < k; ++j) a.set[0].seg[j] = mk_src(weight + j, Co, Ci, Ci * k, k);
@@ -777,9 +804,9 @@ int wn_conv_pack(const wn_conv_shape* s, const float* weight, const float* bias,
                 a.tile[sl * g.MT + m].set = 0;
                 a.tile[sl * g.MT + m].row0 = row0 < Co ? row0 : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(conv fwd)");
     }
     {
+        PackArgs& a = out[1];
         const GemmPlan& g = cp.cb;
         fill_pack_common(a, g, packed, cp.off_cb);
         for (int j = 0; j < k; ++j) a.set[0].seg[j] = mk_src(weight + j, Ci, Co, k, Ci * k);
@@ -789,12 +816,159 @@ int wn_conv_pack(const wn_conv_shape* s, const float* weight, const float* bias,
                 a.tile[sl * g.MT + m].set = 0;
                 a.tile[sl * g.MT + m].row0 = row0 < Ci ? row0 : -1;
             }
-        WN_HIP(launch_pack(a, st), "pack(conv bwd)");
     }
+}
+}  // namespace
+
+int wn_conv_pack(const wn_conv_shape* s, const float* weight, const float* bias, void* packed, wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_conv(s, off);
+    if (rc != WN_OK) return rc;
+    if (!weight || !packed) return WN_ERR_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    const ConvPlan cp = plan_conv(s);
+    ProfScope prof(KC_PACK, 0.0, st);
+    PackArgs jobs[2];
+    conv_pack_jobs(s, cp, weight, bias, packed, jobs);
+    WN_HIP(launch_pack(jobs[0], st), "pack(conv fwd)");
+    WN_HIP(launch_pack(jobs[1], st), "pack(conv bwd)");
     return WN_OK;
 }
 
-int wn_conv_forward(const wn_conv_shape* s, const void* packed, const float* x, float* y, wn_stream_t stream) {
+// ------------------------------------------------------------------------------------------
+// every pack job of an fp32 stack (and of the convs around it) from one launch of a device-resident table
+// ------------------------------------------------------------------------------------------
+namespace {
+inline int stack_pack_max_jobs(int nblocks, int nconvs) { return 4 * nblocks + cdiv(nblocks, WN_MAX_STACK_GROUP) + 2 * nconvs; }
+
+// destinations become byte offsets (the job was built against a NULL buffer + image offset); sources inside a dynamic
+// range become offsets from that range's base
+bool finish_pack_job(PackJob& j, const wn_mem_range* dyn, int ndyn) {
+    auto rel = [&](const float*& p, signed char& mark) {
+        mark = -1;
+        if (!p) return;
+        const uintptr_t v = reinterpret_cast<uintptr_t>(p);
+        for (int i = 0; i < ndyn; ++i) {
+            const uintptr_t b = reinterpret_cast<uintptr_t>(dyn[i].base);
+            if (v >= b && v < b + dyn[i].bytes) {
+                p = reinterpret_cast<const float*>(v - b);
+                mark = (signed char)i;
+                return;
+            }
+        }
+    };
+    for (int set = 0; set < 2; ++set) {
+        for (int sg = 0; sg < kMaxSeg; ++sg) rel(j.a.set[set].seg[sg].ptr, j.seg_dyn[set][sg]);
+        rel(j.a.set[set].bias0, j.bias_dyn[set][0]);
+        rel(j.a.set[set].bias1, j.bias_dyn[set][1]);
+    }
+    return true;
+}
+}  // namespace
+
+size_t wn_stack_pack_table_bytes(int nblocks, int nconvs) {
+    if (nblocks < 0 || nconvs < 0 || nblocks + nconvs == 0) return 0;
+    return (size_t)stack_pack_max_jobs(nblocks, nconvs) * sizeof(PackJob);
+}
+
+int wn_stack_pack_table_build(const wn_block_shape* shapes, const wn_block_params* params, int nblocks, int with_skipsum,
+                              const float* skip_bias_total, const wn_pack_conv* convs, int nconvs,
+                              const wn_mem_range* dynamic, int ndynamic, void* table_host, size_t table_bytes,
+                              size_t* block_offsets, size_t* skipsum_offsets, size_t* conv_offsets, size_t* packed_total,
+                              int* njobs, int* launch_blocks) {
+    if (nblocks < 0 || nconvs < 0 || nblocks + nconvs == 0 || ndynamic < 0) return WN_ERR_BAD_SHAPE;
+    if (ndynamic > kMaxPackDyn) return WN_ERR_UNSUPPORTED;
+    if (!table_host || !packed_total || !njobs || !launch_blocks) return WN_ERR_NULL;
+    if ((nblocks && (!shapes || !params || !block_offsets)) || (nconvs && (!convs || !conv_offsets))) return WN_ERR_NULL;
+    if (ndynamic && !dynamic) return WN_ERR_NULL;
+    if (with_skipsum && nblocks && !skipsum_offsets) return WN_ERR_NULL;
+    if (table_bytes < wn_stack_pack_table_bytes(nblocks, nconvs)) return WN_ERR_WORKSPACE;
+    PackJob* jobs = reinterpret_cast<PackJob*>(table_host);
+    int nj = 0;
+    long long blocks = 0;
+    size_t total = 0;
+    auto push = [&](const PackArgs& a) {
+        PackJob& j = jobs[nj];
+        std::memset(&j, 0, sizeof(j));
+        j.a = a;
+        j.first_block = (int)blocks;
+        finish_pack_job(j, dynamic, ndynamic);
+        blocks += pack_job_blocks(a);
+        ++nj;
+    };
+    int off[WN_MAX_TAPS];
+    for (int l = 0; l < nblocks; ++l) {
+        int rc = check_block(&shapes[l], off);
+        if (rc != WN_OK) return rc;
+        if (!block_params_complete(&params[l])) return WN_ERR_NULL;
+        const BlockPlan bp = plan_block(&shapes[l]);
+        PackArgs a[4];
+        block_pack_jobs(&shapes[l], &params[l], bp, reinterpret_cast<void*>(total), a);
+        for (int i = 0; i < 4; ++i) push(a[i]);
+        block_offsets[l] = total;
+        total += bp.total;
+    }
+    if (with_skipsum) {
+        for (int g0 = 0, gi = 0; g0 < nblocks; g0 += WN_MAX_STACK_GROUP, ++gi) {
+            wn_skipsum_shape ss;
+            std::memset(&ss, 0, sizeof(ss));
+            ss.batch = shapes[0].batch; ss.length = shapes[0].length; ss.skip_rows = shapes[0].skip_rows;
+            ss.ld = shapes[0].ld; ss.halo = shapes[0].halo;
+            ss.nblocks = std::min(WN_MAX_STACK_GROUP, nblocks - g0);
+            const float* w[WN_MAX_STACK_GROUP];
+            for (int i = 0; i < ss.nblocks; ++i) {
+                if (shapes[g0 + i].skip_rows != ss.skip_rows) return WN_ERR_BAD_SHAPE;
+                ss.channels[i] = shapes[g0 + i].out_channels;
+                w[i] = params[g0 + i].w_skip;
+            }
+            int rc = check_skipsum(&ss);
+            if (rc != WN_OK) return rc;
+            const GemmPlan g = plan_skipsum(&ss);
+            PackArgs a;
+            skipsum_pack_job(&ss, g, w, g0 == 0 ? skip_bias_total : nullptr, reinterpret_cast<void*>(total), a);
+            push(a);
+            skipsum_offsets[gi] = total;
+            total += g.bytes();
+        }
+    }
+    for (int c = 0; c < nconvs; ++c) {
+        int rc = check_conv(&convs[c].shape, off);
+        if (rc != WN_OK) return rc;
+        if (!convs[c].weight) return WN_ERR_NULL;
+        const ConvPlan cp = plan_conv(&convs[c].shape);
+        PackArgs a[2];
+        conv_pack_jobs(&convs[c].shape, cp, convs[c].weight, convs[c].bias, reinterpret_cast<void*>(total), a);
+        push(a[0]);
+        push(a[1]);
+        conv_offsets[c] = total;
+        total += cp.total;
+    }
+    if (blocks > 0x7fffffffLL) return WN_ERR_UNSUPPORTED;
+    *packed_total = total;
+    *njobs = nj;
+    *launch_blocks = (int)blocks;
+    return WN_OK;
+}
+
+int wn_stack_pack_run(const void* table_dev, int njobs, int launch_blocks, const void* const* dynamic_bases, int ndynamic,
+                      void* packed, wn_stream_t stream) {
+    if (njobs <= 0 || launch_blocks <= 0 || ndynamic < 0) return WN_ERR_BAD_SHAPE;
+    if (ndynamic > kMaxPackDyn) return WN_ERR_UNSUPPORTED;
+    if (!table_dev || !packed || (ndynamic && !dynamic_bases)) return WN_ERR_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    PackBases bases;
+    std::memset(&bases, 0, sizeof(bases));
+    for (int i = 0; i < ndynamic; ++i) {
+        if (!dynamic_bases[i]) return WN_ERR_NULL;
+        bases.b[i] = reinterpret_cast<const char*>(dynamic_bases[i]);
+    }
+    ProfScope prof(KC_PACK, 0.0, st);
+    WN_HIP(launch_pack_table(reinterpret_cast<const PackJob*>(table_dev), njobs, launch_blocks, bases, packed, st), "pack(stack)");
+    return WN_OK;
+}
+
+namespace {
+int conv_forward(const wn_conv_shape* s, const void* packed, const float* x, float* y, bool leaky, float slope, wn_stream_t stream) {
     int off[WN_MAX_TAPS];
     int rc = check_conv(s, off);
     if (rc != WN_OK) return rc;
@@ -806,12 +980,14 @@ int wn_conv_forward(const wn_conv_shape* s, const void* packed, const float* x, 
     fill_gemm_common(a, g, packed, cp.off_cf, 0, g.nslab, s->batch, s->length, s->ld, s->halo);
     for (int j = 0; j < s->kernel_width; ++j) set_seg(a, j, x, s->in_channels, off[j], g.seg_nkb[j]);
     a.dst[0].base = y; a.dst[0].cp = cp8(s->out_channels); a.dst[0].rows = s->out_channels; a.dst[0].accumulate = 0;
+    a.slope = slope;
     ProfScope prof(KC_CONV_FWD, 2.0 * s->out_channels * (double)(s->kernel_width * s->in_channels) * s->batch * s->length, st);
-    WN_HIP(launch_gemm(g.MT, EPI_LINEAR, a, st), "series_gemm<conv fwd>");
+    WN_HIP(launch_gemm(g.MT, leaky ? EPI_LEAKY : EPI_LINEAR, a, st), "series_gemm<conv fwd>");
     return WN_OK;
 }
 
-int wn_conv_backward_data(const wn_conv_shape* s, const void* packed, const float* dy, float* dx, wn_stream_t stream) {
+int conv_backward_data(const wn_conv_shape* s, const void* packed, const float* dy, const float* act, float slope, float* dx,
+                       wn_stream_t stream) {
     int off[WN_MAX_TAPS];
     int rc = check_conv(s, off);
     if (rc != WN_OK) return rc;
@@ -824,9 +1000,29 @@ int wn_conv_backward_data(const wn_conv_shape* s, const void* packed, const floa
     a.bias = nullptr;
     for (int j = 0; j < s->kernel_width; ++j) set_seg(a, j, dy, s->out_channels, -off[j], g.seg_nkb[j]);
     a.dst[0].base = dx; a.dst[0].cp = cp8(s->in_channels); a.dst[0].rows = s->in_channels; a.dst[0].accumulate = 0;
+    a.mask = act; a.slope = slope;
     ProfScope prof(KC_CONV_BWD_DATA, 2.0 * s->in_channels * (double)(s->kernel_width * s->out_channels) * s->batch * s->length, st);
-    WN_HIP(launch_gemm(g.MT, EPI_LINEAR, a, st), "series_gemm<conv bwd>");
+    WN_HIP(launch_gemm(g.MT, act ? EPI_DMASK : EPI_LINEAR, a, st), "series_gemm<conv bwd>");
     return WN_OK;
+}
+}  // namespace
+
+int wn_conv_forward(const wn_conv_shape* s, const void* packed, const float* x, float* y, wn_stream_t stream) {
+    return conv_forward(s, packed, x, y, false, 1.0f, stream);
+}
+
+int wn_conv_forward_series(const wn_conv_shape* s, const void* packed, const float* x, float* y, float leaky_slope,
+                           wn_stream_t stream) {
+    return conv_forward(s, packed, x, y, true, leaky_slope, stream);
+}
+
+int wn_conv_backward_data(const wn_conv_shape* s, const void* packed, const float* dy, float* dx, wn_stream_t stream) {
+    return conv_backward_data(s, packed, dy, nullptr, 1.0f, dx, stream);
+}
+
+int wn_conv_backward_data_series(const wn_conv_shape* s, const void* packed, const float* dy, const float* act, float leaky_slope,
+                                 float* dx, wn_stream_t stream) {
+    return conv_backward_data(s, packed, dy, act, leaky_slope, dx, stream);
 }
 
 namespace {

@@ -301,6 +301,68 @@ __global__ __launch_bounds__(64, WPS) void series_gemm_kernel(const GemmArgs a) 
             }
             __builtin_amdgcn_sched_barrier(0);
         }
+    } else if constexpr (EPI == EPI_LEAKY) {
+        // dst = leaky_relu(acc): torch's rule v > 0 ? v : v * slope, so the stored value is bitwise F.leaky_relu of the sum
+        const GemmDst d = a.dst[sl.dst];
+        const float slope = a.slope;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = sl.row0 + 32 * m + rowof(r, h);
+                if (row < d.rows) {
+                    float* p = d.base + ((long)b * d.cp + row) * ld + colbase;
+                    breg_t v;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const float x = acc[m][t][r];
+                        v[t] = x > 0.0f ? x : x * slope;
+                    }
+                    *reinterpret_cast<breg_t*>(p) = clip(v);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else if constexpr (EPI == EPI_DMASK) {
+        // dst = acc * leaky_relu'(mask): torch's backward rule m > 0 ? g : g * slope (m == 0 takes the slope), with the conv's
+        // stored input activation as m.  The mask rows are fetched a batch ahead of use, like EPI_ACCUM's old values.
+        const GemmDst d = a.dst[sl.dst];
+        const float slope = a.slope;
+        constexpr int RB = 8, BPT = 16 / RB, NBATCH = MT * BPT;
+        breg_t msk[2][RB];
+        const long tile_off = (long)b * d.cp * ld + colbase;
+        float* const tile = d.base + tile_off;
+        const float* const mtile = a.mask + tile_off;
+        auto fetch = [&](int bi, breg_t (&dst)[RB]) {
+            const int m = bi / BPT, r0 = (bi % BPT) * RB;
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                row = row < d.rows ? row : d.rows - 1;   // rows past the end are never stored: clamp, don't branch
+                dst[i] = *reinterpret_cast<const breg_t*>(mtile + (long)row * ld);
+            }
+        };
+        fetch(0, msk[0]);
+#pragma unroll
+        for (int bi = 0; bi < NBATCH; ++bi) {
+            if (bi + 1 < NBATCH) fetch(bi + 1, msk[(bi + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            const int m = bi / BPT, r0 = (bi % BPT) * RB;
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                const int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                if (row < d.rows) {
+                    breg_t v;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const float g = acc[m][t][r0 + i];
+                        v[t] = msk[bi & 1][i][t] > 0.0f ? g : g * slope;
+                    }
+                    *reinterpret_cast<breg_t*>(tile + (long)row * ld) = clip(v);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
     } else {  // EPI_DGATE: acc = dz ; da = dz*sg*(1-ta^2), dg = dz*ta*sg*(1-sg) with ta = z / sg
         // z/sg come from HBM: issue a whole batch of rows (up to 32 x 16 B per lane in flight) before using any of
         // them -- row-by-row load->use chains cost 55 us of a 186 us wave (tools/block_stamps.py).
@@ -411,6 +473,8 @@ hipError_t launch_gemm(int MT, int epi, const GemmArgs& a, hipStream_t st) {
         case EPI_GATE: return launch_epi<EPI_GATE>(MT, a, st);
         case EPI_DGATE: return launch_epi<EPI_DGATE>(MT, a, st);
         case EPI_ACCUM: return launch_epi<EPI_ACCUM>(MT, a, st);
+        case EPI_LEAKY: return launch_epi<EPI_LEAKY>(MT, a, st);
+        case EPI_DMASK: return launch_epi<EPI_DMASK>(MT, a, st);
     }
     return hipErrorInvalidValue;
 }

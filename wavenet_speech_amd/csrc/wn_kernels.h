@@ -65,9 +65,13 @@ struct GemmArgs {
     int tiles_per_row;  // ceil(L / column tile)
     int ncol;           // B * tiles_per_row
     unsigned long long* stamps;  // diagnostic build (-DWN_STAMPS) only: 8 words per workgroup
+    // LeakyReLU epilogues (appended: the fields above keep their kernel-argument offsets)
+    const float* mask;  // EPI_DMASK: the stored activation the product's gradient is masked by, a series shaped like dst
+    float slope;        // EPI_LEAKY / EPI_DMASK: negative slope
 };
 
-enum { EPI_LINEAR = 0, EPI_GATE = 1, EPI_DGATE = 2, EPI_ACCUM = 3 };  // ACCUM: dst += result (+ bias)
+// ACCUM: dst += result (+ bias);  LEAKY: dst = leaky_relu(result + bias);  DMASK: dst = result * leaky_relu'(mask)
+enum { EPI_LINEAR = 0, EPI_GATE = 1, EPI_DGATE = 2, EPI_ACCUM = 3, EPI_LEAKY = 4, EPI_DMASK = 5 };
 
 // ---------------------------------------------------------------------------------------------
 // weight packing: logical matrix element (slab, tile m, row i, seg, c) -> source tensors
@@ -97,6 +101,18 @@ struct PackArgs {
     float* bias;
     long long total;               // packed weight floats
 };
+
+// One entry of a device-resident pack table (wn_stack_pack_*): every pack job of a stack runs from ONE launch.
+//   a.wpacked / a.bias hold BYTE OFFSETS into the packed buffer the launch supplies;
+//   a source pointer whose *_dyn entry is i >= 0 holds a byte offset from dynamic base i of the launch (-1: absolute).
+constexpr int kMaxPackDyn = 3;
+struct PackJob {
+    PackArgs a;
+    int first_block;                   // first workgroup of the launch that belongs to this job
+    signed char seg_dyn[2][kMaxSeg];
+    signed char bias_dyn[2][2];
+};
+struct PackBases { const char* b[kMaxPackDyn]; };
 
 // ---------------------------------------------------------------------------------------------
 // weight-gradient kernel: out_p[M x N] = sum_{b,t} A_p[b][m][t] * B_p[b][n][t + off_p]
@@ -150,6 +166,9 @@ static_assert(sizeof(ReduceArgs) <= 4096 && sizeof(WgradArgs) <= 4096, "kernel a
 // launchers (defined in the .hip files)
 hipError_t launch_gemm(int MT, int epi, const GemmArgs& a, hipStream_t st);
 hipError_t launch_pack(const PackArgs& a, hipStream_t st);
+long long pack_job_blocks(const PackArgs& a);   // workgroups one pack job needs
+hipError_t launch_pack_table(const PackJob* jobs_dev, int njobs, int launch_blocks, const PackBases& bases, void* packed,
+                             hipStream_t st);
 hipError_t launch_wgrad(int WT, const WgradArgs& a, hipStream_t st);
 hipError_t launch_wgrad_reduce(const ReduceArgs& a, hipStream_t st);
 hipError_t launch_nll_forward(const float* logits, const long long* target, float* lse, float* partial, int* bad_targets, int B,

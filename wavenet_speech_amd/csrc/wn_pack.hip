@@ -9,8 +9,11 @@
 
 namespace wn {
 
-__global__ __launch_bounds__(256) void pack_kernel(const PackArgs a) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+// One output float (and one packed bias) per thread.  `src(set, seg)`, `bias0(set)`, `bias1(set)` resolve the job's source
+// pointers: as stored for pack_kernel, relative to the launch's dynamic bases for pack_table_kernel.
+template <class SrcFn, class Bias0Fn, class Bias1Fn>
+__device__ __forceinline__ void pack_element(const PackArgs& a, long long idx, float* wpacked, float* bias, SrcFn src,
+                                             Bias0Fn bias0, Bias1Fn bias1) {
     if (idx < a.total) {
         // locate the slab
         int slab = 0;
@@ -27,37 +30,81 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackArgs a) {
         const PackTile t = a.tile[slab * a.MT + m];
         float v = 0.0f;
         if (t.row0 >= 0) {
-            const PackSrc src = a.set[t.set].seg[s];
+            const PackSrc& ps = a.set[t.set].seg[s];
+            const float* ptr = src(t.set, s);
             const int r = t.row0 + (lane & 31);
-            if (src.ptr && r < src.rows && c < src.cols) v = src.ptr[(long long)r * src.stride_r + (long long)c * src.stride_c];
+            if (ptr && r < ps.rows && c < ps.cols) v = ptr[(long long)r * ps.stride_r + (long long)c * ps.stride_c];
         }
-        a.wpacked[idx] = v;
+        wpacked[idx] = v;
     }
     // bias: [slab][MT*32]
     const long long nb = (long long)a.nslab * a.MT * 32;
-    if (idx < nb && a.bias) {
+    if (idx < nb && bias) {
         const int slab = (int)(idx / (a.MT * 32));
         const int rr = (int)(idx % (a.MT * 32));
         const PackTile t = a.tile[slab * a.MT + rr / 32];
         float v = 0.0f;
         if (t.row0 >= 0) {
-            const PackSet& ps = a.set[t.set];
             const int r = t.row0 + (rr & 31);
-            if (r < ps.bias_rows) {
-                if (ps.bias0) v += ps.bias0[r];
-                if (ps.bias1) v += ps.bias1[r];
+            if (r < a.set[t.set].bias_rows) {
+                const float* p0 = bias0(t.set);
+                const float* p1 = bias1(t.set);
+                if (p0) v += p0[r];
+                if (p1) v += p1[r];
             }
         }
-        a.bias[a.slab_boff[slab] + rr] = v;
+        bias[a.slab_boff[slab] + rr] = v;
     }
 }
 
-hipError_t launch_pack(const PackArgs& a, hipStream_t st) {
+__global__ __launch_bounds__(256) void pack_kernel(const PackArgs a) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    pack_element(a, idx, a.wpacked, a.bias,
+                 [&](int set, int seg) { return a.set[set].seg[seg].ptr; },
+                 [&](int set) { return a.set[set].bias0; }, [&](int set) { return a.set[set].bias1; });
+}
+
+// every job of a table in one launch: workgroups [first_block, first_block of the next job) belong to one job
+__global__ __launch_bounds__(256) void pack_table_kernel(const PackJob* __restrict__ jobs, int njobs, const PackBases bases,
+                                                         char* packed) {
+    int lo = 0, hi = njobs - 1;   // the last job whose first_block <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const PackJob& j = jobs[lo];
+    const PackArgs& a = j.a;
+    const long long idx = (long long)((int)blockIdx.x - j.first_block) * 256 + threadIdx.x;
+    // a dynamic source is never NULL (only existing sources are marked): its pointer field holds the offset from its base
+    auto dynp = [&](const float* p, int dyn) -> const float* {
+        return dyn < 0 ? p : reinterpret_cast<const float*>(bases.b[dyn] + reinterpret_cast<size_t>(p));
+    };
+    pack_element(a, idx, reinterpret_cast<float*>(packed + reinterpret_cast<size_t>(a.wpacked)),
+                 reinterpret_cast<float*>(packed + reinterpret_cast<size_t>(a.bias)),
+                 [&](int set, int seg) { return dynp(a.set[set].seg[seg].ptr, j.seg_dyn[set][seg]); },
+                 [&](int set) { return dynp(a.set[set].bias0, j.bias_dyn[set][0]); },
+                 [&](int set) { return dynp(a.set[set].bias1, j.bias_dyn[set][1]); });
+}
+
+long long pack_job_blocks(const PackArgs& a) {
     long long n = a.total;
     const long long nb = (long long)a.nslab * a.MT * 32;
     if (nb > n) n = nb;
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    return n <= 0 ? 0 : (n + 255) / 256;
+}
+
+hipError_t launch_pack(const PackArgs& a, hipStream_t st) {
+    const long long nblk = pack_job_blocks(a);
+    if (nblk <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nblk), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_table(const PackJob* jobs_dev, int njobs, int launch_blocks, const PackBases& bases, void* packed,
+                             hipStream_t st) {
+    if (njobs <= 0 || launch_blocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pack_table_kernel, dim3((unsigned)launch_blocks), dim3(256), 0, st, jobs_dev, njobs, bases,
+                       reinterpret_cast<char*>(packed));
     return hipGetLastError();
 }
 

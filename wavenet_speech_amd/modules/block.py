@@ -149,8 +149,8 @@ def set_precision(module, precision):
 
 def freeze_for_inference(module, on=True):
     """Keep the packed weights and the folded bottlenecks of the residual stacks of `module` across no_grad forwards (by
-    default every forward packs the current weights again: one launch per stack in the half-precision modes, four small
-    launches per block in the fp32 mode).  The cache is emptied when a parameter's autograd version changes (optimizer step,
+    default every forward packs the current weights again: one launch per stack, from a device-resident job table, in every
+    mode).  The cache is emptied when a parameter's autograd version changes (optimizer step,
     load_state_dict, p.mul_()) or a parameter moves; updates written through `p.data` are NOT seen -- call
     freeze_for_inference(module) again after such an update to drop the cache."""
     n = 0
@@ -169,18 +169,21 @@ def freeze_for_inference(module, on=True):
 
 
 def fusable_head(head, precision):
-    """(slopes, parameters) of an output block that can run inside the half-precision stack function, in the series layout:
-    exactly LeakyReLU, Conv1d 1x1, LeakyReLU, Conv1d 1x1 (every reference model's output_stack / output_block), in a half mode
-    whose head convs follow the stack (head_precision).  None otherwise: the caller then evaluates the block itself."""
+    """(slopes, parameters) of an output block that can run inside the stack function, in the series layout: exactly LeakyReLU,
+    Conv1d 1x1, LeakyReLU, Conv1d 1x1 (every reference model's output_stack / output_block), in "f32" or in a half mode whose
+    head convs follow the stack (head_precision).  None otherwise: the caller then evaluates the block itself."""
     import os
     import torch.nn as nn
     if head is None or os.environ.get("WN_SERIES_HEAD", "1") == "0":
         return None
-    if precision == "f32" or head_precision(precision) != precision:
+    if head_precision(precision) != precision:
         return None
     mods = list(head)
     if len(mods) != 4 or not (isinstance(mods[0], nn.LeakyReLU) and isinstance(mods[2], nn.LeakyReLU)):
         return None
+    if precision == "f32" and any(m._forward_pre_hooks or m._forward_hooks for m in mods + [head]):
+        return None          # a fused block never calls its modules: hooks on them would silently not run.  In "f32" the op-by-op
+                             # form computes bitwise the same, so the hooks keep their meaning at no cost in results
     for c in (mods[1], mods[3]):
         if not isinstance(c, nn.Conv1d) or c.kernel_size != (1,) or c.stride != (1,) or c.padding != (0,) or c.groups != 1 \
                 or c.bias is None:
@@ -221,12 +224,29 @@ def fusable_front(front, precision, x):
     return (mods[1].negative_slope, mods[3].negative_slope), [c0.weight, c0.bias, c1.weight, c1.bias]
 
 
+def fusable_entry(conv, precision, x):
+    """(geometry, parameters) of a model's entry conv (a conv_ops.CausalConv1d / NonCausalConv1d in front of the stack) that can
+    run inside the fp32 stack function: its output is then written as the stack's input series and its gradient comes back as a
+    series, with no dense tensor between the two.  None otherwise (a half mode, WN_SERIES_FRONT=0, an input that is not a float32
+    device tensor [B, C, L]): the caller then runs the conv itself."""
+    import os
+    from .conv_ops import _DilatedConv1d
+    if precision != "f32" or os.environ.get("WN_SERIES_FRONT", "1") == "0":
+        return None
+    if not isinstance(conv, _DilatedConv1d) or conv.precision != "f32":
+        return None
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32:
+        return None
+    return (conv.kernel_width, conv.dilation, conv.causal), [conv.conv1d.weight, conv.conv1d.bias]
+
+
 def run_stack(out, blocks, bottlenecks, state=None, head=None, front=None, pool=1):
     """skips_sum over `blocks` (reference modules/wavenet.py:98-100) through the fused HIP stack path.
     `pool` > 1: AvgPool1d(pool) of `out` fused into the load of the stack's input (WaveNetClassifier.mean_pool).
-    `front`: the result of fusable_front() (the feature layer then runs inside the function and `out` is the raw signal).
-    With `head` (the model's output block) returns (tensor, head_done): in the half modes the output block runs inside the same
-    function, in the series layout (no dense fp32 skips_sum, no separate LeakyReLU passes), and `tensor` is its output."""
+    `front`: the result of fusable_front() (half modes: the feature layer then runs inside the function and `out` is the raw
+    signal) or of fusable_entry() ("f32": the entry conv runs inside the function and `out` is its input).
+    With `head` (the model's output block) returns (tensor, head_done): where fusable_head() allows it the output block runs inside
+    the same function, in the series layout (no dense fp32 skips_sum, no separate LeakyReLU passes), and `tensor` is its output."""
     specs, flat = [], []
     out_dim = bottlenecks[0].out_channels
     blocks, bottlenecks = list(blocks), list(bottlenecks)

@@ -8,7 +8,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as HF
-from .block import ResidualBlock, StackState, run_stack, pointwise_precision, head_precision
+from .block import ResidualBlock, StackState, run_stack, pointwise_precision, head_precision, fusable_entry
 from .conv_ops import CausalConv1d
 from .pointwise import run_sequential
 
@@ -54,11 +54,13 @@ class WaveNet(nn.Module):
         return self._after_entry(out)
 
     def forward(self, signal):
-        out = self.entry_conv1d(signal)
-        return self._after_entry(out)
+        # "f32": the entry conv runs inside the stack function and hands its output over as a series (block.fusable_entry)
+        front = fusable_entry(self.entry_conv1d, self.stack_state.precision, signal)
+        out = signal if front is not None else self.entry_conv1d(signal)
+        return self._after_entry(out, front)
 
-    def _after_entry(self, out):
-        skips_sum, done = run_stack(out, self.convolutions, self.bottlenecks, self.stack_state, head=self.output_stack)
+    def _after_entry(self, out, front=None):
+        skips_sum, done = run_stack(out, self.convolutions, self.bottlenecks, self.stack_state, head=self.output_stack, front=front)
         output_seq = skips_sum if done else run_sequential(self.output_stack, skips_sum, head_precision(self.stack_state.precision))
         if not self.softmax:
             return output_seq
