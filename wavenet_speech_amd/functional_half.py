@@ -10,6 +10,7 @@ torch.autograd.Function shape as functional._ResidualStackFn, driving the wn_h* 
 Activations live in the "half series" layout of include/wavenet_amd.h; torch supplies device memory (series.Lease with a
 half dtype), the stream and autograd bookkeeping.  There is no CPU path.
 """
+import collections
 import ctypes
 import os
 
@@ -17,7 +18,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _flags, _lib
-from .functional import PARAMS_PER_BLOCK, _on_device_of_first_tensor, _p, _params_struct, _prep_params, _require_device, _stream
+from .functional import (PARAMS_PER_BLOCK, _alloc_block_grads, _alloc_bytes, _check_stack, _head_shapes, _on_device_of_first_tensor,
+                         _p, _pack_blocks, _PackTable, _params_struct, _pooled_length, _prep_params, _require_device, _shape, _skipsum_groups,
+                         _split_flat, _stream, _unpool, _workspace)
 from .series import Lease
 
 # The cotangent is scaled by a power of two so that max|d skips_sum| lands in [0.125, 0.25]: gradients may then grow by 2^18
@@ -56,11 +59,6 @@ def _hlease(mode, batch, channels, layout, device):
     return Lease(batch, channels, layout, device, dtype=mode.dtype, rows=mode.planes * g, pitch=layout.ld * 8)
 
 
-def _shape(spec, batch, layout):
-    return _lib.BlockShape(batch, layout.length, spec.ci, spec.co, spec.ms, spec.k, spec.d, int(spec.causal),
-                           layout.ld, layout.halo)
-
-
 _OVERFLOW_MSG = ("wavenet_speech_amd: fp16 overflow in the %s of the half-precision stack (a value beyond +-65504 after the "
                  "built-in 1/16 residual scaling); use precision='f32' or 'bf16' for this model")
 
@@ -91,56 +89,71 @@ def _grad_scale(cotangent, mode):
     return out[0:1], out[1:2]
 
 
+# what every step of one call shares: _Call's fields, the arithmetic mode, the fp16 overflow flag (None in bf16), the residual scale
+_HCall = collections.namedtuple("_HCall", "lib batch layout dev mode flag rs")
+
+
+def _hcall(lib, batch, layout, dev, mode):
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if mode.dtype == torch.float16 else None
+    return _HCall(lib, batch, layout, dev, mode, flag, float(lib.wn_hseries_residual_scale()))
+
+
+def _lease(c, channels):
+    return _hlease(c.mode, c.batch, channels, c.layout, c.dev)
+
+
 def _load(lib, mode, dense, lease, layout, scale, dyn, flag):
     B, C, L = dense.shape
     _lib.check(lib.wn_hseries_load(mode.code, _p(dense), _p(lease), B, C, L, layout.ld, layout.halo, ctypes.c_float(scale),
                                    _p(dyn), _p(flag), _stream()), "wn_hseries_load")
 
 
-class StackPackTable(object):
-    """Device-resident table of every weight-pack job of a stack (wn_hstack_pack_*): built once per (shapes, precision, pointers),
-    then ONE launch per training step packs all blocks and the long-K skips_sum weights.  Parameters computed anew every step
-    (anything that is not an nn.Parameter: the folded bottleneck x skip products) are declared dynamic -- the table holds their offsets inside their
-    storages and each run supplies the storages' current addresses -- so steady-state training never rebuilds it."""
-    MAX_DYNAMIC = 3
+def _pack_hconv(c, shape, w, b):
+    packed = _alloc_bytes(c.lib.wn_hconv_packed_bytes(ctypes.byref(shape), c.mode.code), "wn_hconv_packed_bytes", c.dev,
+                          -1 if shape.kernel_width <= _lib.MAX_TAPS else -2)
+    _lib.check(c.lib.wn_hconv_pack(ctypes.byref(shape), c.mode.code, _p(w), _p(b), ctypes.c_float(c.rs), _p(packed), _stream()),
+               "wn_hconv_pack")
+    return packed
 
-    @staticmethod
-    def dynamic_storages(flat):
-        """distinct storages of the tensors that are not nn.Parameters (recomputed every step), in first-seen order; None if too many"""
-        seen = []
-        for t in flat:
-            if not isinstance(t, torch.nn.Parameter):
-                st = t.untyped_storage()
-                if all(st.data_ptr() != q.data_ptr() for q in seen):
-                    seen.append(st)
-        return seen if len(seen) <= StackPackTable.MAX_DYNAMIC else None
+
+def _hconv_wgrad(c, shape, xin, dy, wshape, has_bias, dyn_inv):
+    """(dW, db) of a half conv whose input and output gradient are series already"""
+    dw = torch.empty(wshape, dtype=torch.float32, device=c.dev)
+    db = torch.empty(wshape[0], dtype=torch.float32, device=c.dev) if has_bias else None
+    ws_bytes = c.lib.wn_hconv_wgrad_workspace_bytes(ctypes.byref(shape), c.mode.code)
+    ws = _workspace(ws_bytes, c.dev)
+    _lib.check(c.lib.wn_hconv_backward_weights(ctypes.byref(shape), c.mode.code, _p(xin), _p(dy), ctypes.c_float(c.rs), _p(dw), _p(db),
+                                               _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hconv_backward_weights")
+    return dw, db
+
+
+def plan_switches():
+    """the per-call switches that change the packed layout of a half block (plan_hblock in csrc/wn_half_api.hip reads them at every
+    call): whatever holds offsets into packed weights, or the weights themselves, is keyed by their current values"""
+    return (os.environ.get("WN_FUSED_FWD"), os.environ.get("WN_COL_BWD"))
+
+
+class StackPackTable(_PackTable):
+    """Device-resident table of every weight-pack job of a half-mode stack (wn_hstack_pack_*): ONE launch per training step packs
+    all blocks and the long-K skips_sum weights."""
 
     @staticmethod
     def key_of(specs, mode, B, layout, prepped, storages, skipsum):
-        dyn = [(st.data_ptr(), st.nbytes()) for st in storages]
-
-        def rel(t):
-            p = t.data_ptr()
-            for i, (b, n) in enumerate(dyn):
-                if b <= p < b + n:
-                    return ("d", i, p - b)
-            return p
-        return (mode.name, B, layout.key(), bool(skipsum), tuple(n for _, n in dyn),
-                tuple((s.ci, s.co, s.ms, s.k, s.d, s.causal) for s in specs), tuple(rel(t) for blk in prepped for t in blk))
+        sizes, rel = _PackTable.relative(storages)
+        return (mode.name, B, layout.key(), bool(skipsum), sizes, tuple(s.key() for s in specs),
+                tuple(rel(t) for blk in prepped for t in blk)) + plan_switches()
 
     def __init__(self, lib, specs, mode, B, layout, prepped, storages, skipsum, device):
         n = len(specs)
         shapes = (_lib.BlockShape * n)(*[_shape(s, B, layout) for s in specs])
         params = (_lib.BlockParams * n)(*[_params_struct(blk) for blk in prepped])
-        dyn = (_lib.MemRange * max(1, len(storages)))(*[_lib.MemRange(st.data_ptr(), st.nbytes()) for st in storages])
         nbytes = lib.wn_hstack_pack_table_bytes(n)
         host = ctypes.create_string_buffer(nbytes)
         offs = (ctypes.c_size_t * n)()
-        ngroups = (n + _lib.MAX_STACK_GROUP - 1) // _lib.MAX_STACK_GROUP
-        soffs = (ctypes.c_size_t * ngroups)()
+        soffs = (ctypes.c_size_t * ((n + _lib.MAX_STACK_GROUP - 1) // _lib.MAX_STACK_GROUP))()
         total, njobs, nblocks = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0)
-        rc = lib.wn_hstack_pack_table_build(shapes, params, n, mode.code, 1 if skipsum else 0, dyn, len(storages), host, nbytes,
-                                            offs, soffs, ctypes.byref(total), ctypes.byref(njobs), ctypes.byref(nblocks))
+        rc = lib.wn_hstack_pack_table_build(shapes, params, n, mode.code, 1 if skipsum else 0, self.mem_ranges(storages), len(storages),
+                                            host, nbytes, offs, soffs, ctypes.byref(total), ctypes.byref(njobs), ctypes.byref(nblocks))
         if rc == -2:
             raise NotImplementedError("layout not covered by the pack-job table")   # WN_ERR_UNSUPPORTED: per-block packing instead
         _lib.check(rc, "wn_hstack_pack_table_build")
@@ -153,9 +166,8 @@ class StackPackTable(object):
     def run(self, lib, storages, device, flag=None):
         """pack everything into a fresh buffer; returns it (block l at data_ptr() + block_offsets[l])"""
         packed = torch.empty(self.total, dtype=torch.uint8, device=device)
-        bases = (ctypes.c_void_p * max(1, self.ndyn))(*[st.data_ptr() for st in storages])
-        _lib.check(lib.wn_hstack_pack_run(_p(self.table), self.nblk, self.njobs, self.launch_blocks, bases, self.ndyn, _p(packed),
-                                          _p(flag), _stream()), "wn_hstack_pack_run")
+        _lib.check(lib.wn_hstack_pack_run(_p(self.table), self.nblk, self.njobs, self.launch_blocks, self.bases(storages), self.ndyn,
+                                          _p(packed), _p(flag), _stream()), "wn_hstack_pack_run")
         return packed
 
 
@@ -203,212 +215,360 @@ def wgrad_groups(lib, shapes, precision_code, cap=None):
 _WGRAD_GROUPS = {}   # wgrad_groups results by (precision, WN_WGRAD_GROUP, WN_HWGRAD_COMPOSITE, block shapes)
 
 
+def _wgrad_plan(lib, mode, shapes):
+    """(blocks whose weight gradients run in a group launch, blocks that close their group) for the BlockShapes of a stack.
+    Small blocks (<= 128 channels) are two or three gradient tiles each -- their operands are kept and several blocks go into ONE
+    split-K launch + ONE reduction (wn_hblocks_backward_weights); WN_WGRAD_GROUP=1 = per block.  The groups come from every
+    block's own shape (wgrad_groups), in the order backward reaches the blocks: top first."""
+    env_group = os.environ.get("WN_WGRAD_GROUP")
+    order = list(range(len(shapes) - 1, -1, -1))
+    top_down = [shapes[l] for l in order]
+    gkey = (mode.code, env_group, os.environ.get("WN_HWGRAD_COMPOSITE"),
+            tuple(tuple(getattr(s, f) for f, _ in s._fields_) for s in top_down))
+    groups = _WGRAD_GROUPS.get(gkey)
+    if groups is None:           # (the plan depends on the shapes only: planned once per stack geometry)
+        groups = wgrad_groups(lib, top_down, mode.code, int(env_group) if env_group else None)
+        if len(_WGRAD_GROUPS) >= 64:
+            _WGRAD_GROUPS.clear()
+        _WGRAD_GROUPS[gkey] = groups
+    grouped, group_end = set(), set()
+    for is_group, pos in groups:
+        if is_group:
+            grouped.update(order[p] for p in pos)
+            group_end.add(order[pos[-1]])
+    return grouped, group_end
+
+
+def _flush_wgrad(c, pending, dS, dyn_inv):
+    """ONE weight-gradient launch for the blocks in `pending` = [(shape, x, z, da, dg, dr, grads)], which it empties: their operands
+    stay leased until here"""
+    m = len(pending)
+    if not pending:
+        return
+    shapes = (_lib.BlockShape * m)(*[e[0] for e in pending])
+    arr = lambda i: (ctypes.c_void_p * m)(*[(e[i].ptr if e[i] is not None else None) for e in pending])
+    dsk = (ctypes.c_void_p * m)(*[dS.ptr] * m)
+    gs = (_lib.BlockParams * m)(*[_params_struct(e[6]) for e in pending])
+    ws_bytes = c.lib.wn_hblocks_wgrad_workspace_bytes(shapes, m, c.mode.code)
+    ws = _alloc_bytes(ws_bytes, "wn_hblocks_wgrad_workspace_bytes", c.dev)
+    _lib.check(c.lib.wn_hblocks_backward_weights(shapes, m, c.mode.code, arr(1), arr(2), arr(3), arr(4), arr(5), dsk, gs,
+                                                 _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hblocks_backward_weights")
+    del pending[:]
+
+
+# ---- the steps of the half stack function, in the order forward and backward run them -------------------------------------------------
+def _input_series(c, x, pool, front, front_params):
+    """The stack's input as a half series: x itself, AvgPool1d(pool) of x (reference modules/classifier.py:53,102) fused into the
+    load, or the feature layer `front` = (slope0, slope1) of the raw signal x: leaky(conv k) (elementwise kernel) -> leaky(conv 1x1).
+    Returns (series, what the feature layer's backward needs or None)."""
+    lib, mode, lay = c.lib, c.mode, c.layout
+    B, Cx, Lx = x.shape
+    xd = x.detach().contiguous()
+    if front is None:
+        cur = _lease(c, Cx)
+        if pool > 1:
+            _lib.check(lib.wn_hseries_load_pooled(mode.code, _p(xd), _p(cur), B, Cx, Lx, int(pool), lay.ld, lay.halo,
+                                                  ctypes.c_float(c.rs), None, _p(c.flag), _stream()), "wn_hseries_load_pooled")
+        else:
+            _load(c.lib, c.mode, xd, cur, c.layout, c.rs, None, c.flag)
+        return cur, None
+    fw0, fb0, fw1, fb1 = front_params
+    F0, k0 = fw0.shape[0], fw0.shape[2]
+    cur = _lease(c, fw1.shape[0])
+    f1 = _lease(c, F0)
+    _lib.check(lib.wn_hfeature_forward(mode.code, _p(xd), _p(fw0), _p(fb0), _p(f1), B, Lx, F0, k0, lay.ld, lay.halo,
+                                       ctypes.c_float(c.rs), ctypes.c_float(front[0]), _p(c.flag), _stream()), "wn_hfeature_forward")
+    fsh = _lib.ConvShape(B, lay.length, F0, fw1.shape[0], 1, 1, 1, lay.ld, lay.halo)
+    fpk = _pack_hconv(c, fsh, fw1, fb1)
+    _lib.check(lib.wn_hconv_forward_series(ctypes.byref(fsh), mode.code, _p(fpk), _p(f1), _p(cur), ctypes.c_float(c.rs),
+                                           ctypes.c_float(front[1]), _p(c.flag), _stream()), "wn_hconv_forward_series")
+    return cur, (front, xd, f1, fsh, fpk, Lx, [tuple(t.shape) for t in front_params])
+
+
+def _pack_stack(c, pack_cache, frozen, specs, prepped, flat, training):
+    """Every packed image of the stack: (buffer that owns them or None, per block, per skips_sum group or None).
+    All pack jobs (5 per block + in training the long-K skips_sum weights) come from ONE launch of a device-resident job table
+    (StackPackTable); a frozen model keeps its packed weights instead; WN_PACK_TABLE=0 or a layout that the table does not cover
+    (e.g. skip biases that are not equally spaced) falls back to the per-block entry points."""
+    table = None
+    if pack_cache is not None and not frozen and os.environ.get("WN_PACK_TABLE", "1") != "0":
+        storages = StackPackTable.dynamic_storages(flat)
+        if storages is not None:
+            key = StackPackTable.key_of(specs, c.mode, c.batch, c.layout, prepped, storages, training)
+            table = pack_cache.table(key, lambda: StackPackTable(c.lib, specs, c.mode, c.batch, c.layout, prepped, storages, training,
+                                                                 c.dev))
+    if table is None:
+        return None, _pack_blocks(c, pack_cache, frozen, specs, lambda l, shape: _pack_block(c, shape, prepped[l])), None
+    packed_all = table.run(c.lib, storages, c.dev, c.flag)
+    base = packed_all.data_ptr()
+    return packed_all, [base + o for o in table.block_offsets], [base + o for o in table.skipsum_offsets]
+
+
+def _pack_block(c, shape, params):
+    packed = _alloc_bytes(c.lib.wn_hblock_packed_bytes(ctypes.byref(shape), c.mode.code), "wn_hblock_packed_bytes", c.dev)
+    ps = _params_struct(params)
+    _lib.check(c.lib.wn_hblock_pack_checked(ctypes.byref(shape), c.mode.code, ctypes.byref(ps), _p(packed), _p(c.flag), _stream()),
+               "wn_hblock_pack_checked")
+    return packed
+
+
+def _forward_blocks(c, specs, blocks_packed, series, S, training):
+    """the block loop over the input `series` (a one-element list, emptied here); returns what backward needs of every block,
+    [(x, sg, z, packed, shape)] (empty unless training)"""
+    lib, mode = c.lib, c.mode
+    cur = series.pop()
+    saved = []
+    zbuf = None
+    for l, (spec, packed) in enumerate(zip(specs, blocks_packed)):
+        shape = _shape(spec, c.batch, c.layout)
+        r = _lease(c, spec.co) if l + 1 < len(specs) else None
+        if training:
+            sg, z = (_lease(c, spec.co) for _ in range(2))   # kept for backward; tanh = z / sg
+        elif lib.wn_hblock_forward_is_fused(ctypes.byref(shape), mode.code):
+            sg = z = None                  # inference through the fused kernel: z stays on the chip
+        else:
+            sg = None
+            if zbuf is None or zbuf.channels != spec.co:
+                zbuf = _lease(c, spec.co)
+            z = zbuf
+        _lib.check(lib.wn_hblock_forward(ctypes.byref(shape), mode.code, _p(packed), _p(cur), _p(r),
+                                         None if training else _p(S), 0 if l == 0 else 1, _p(sg), _p(z),
+                                         _p(c.flag), _stream()), "wn_hblock_forward")
+        if training:
+            saved.append((cur, sg, z, packed, shape))
+        cur = r
+    return saved
+
+
+def _skips_sum(c, specs, saved, prepped, groups, S):
+    """The long-K skips_sum products of a training forward, their weights packed here where no table has done it: into the dense
+    S, or, with S None (the head takes leaky(S) as a series: one group), not run -- the group's (shape, z pointers, packed
+    weights) are returned for wn_hskipsum_forward_series."""
+    lib, mode = c.lib, c.mode
+    bias_total = torch.stack([p[7] for p in prepped]).sum(0).contiguous() if groups is None else None
+    for gi, idx, shape, zptrs in _skipsum_groups(specs, [sv[2] for sv in saved], c.batch, c.layout):
+        if groups is not None:
+            packed = groups[gi]
+        else:
+            packed = _alloc_bytes(lib.wn_hskipsum_packed_bytes(ctypes.byref(shape), mode.code), "wn_hskipsum_packed_bytes", c.dev)
+            wptrs = (ctypes.c_void_p * len(idx))(*[prepped[l][6].data_ptr() for l in idx])
+            _lib.check(lib.wn_hskipsum_pack(ctypes.byref(shape), mode.code, wptrs, _p(bias_total) if gi == 0 else None,
+                                            _p(packed), _stream()), "wn_hskipsum_pack")
+        if S is not None:
+            _lib.check(lib.wn_hskipsum_forward(ctypes.byref(shape), mode.code, _p(packed), zptrs, _p(S),
+                                               0 if gi == 0 else 1, _stream()), "wn_hskipsum_forward")
+    return shape, zptrs, packed
+
+
+def _head_forward(c, head, head_params, S, series):
+    """Output block in the series layout: leaky(S) -> conv1 -> leaky -> conv2 (dense fp32 out).  Its input is the dense S, or with
+    `series` (_skips_sum's return) the long-K skips_sum product writes leaky(S) / 16 straight into the series: no dense fp32 S at all.
+    Returns (y, what backward needs)."""
+    lib, mode = c.lib, c.mode
+    sh1, sh2 = _head_shapes(head_params, S.shape[1], c.batch, c.layout)
+    pk = [_pack_hconv(c, sh1, head_params[0], head_params[1]), _pack_hconv(c, sh2, head_params[2], head_params[3])]
+    h0 = _lease(c, sh1.in_channels)
+    if series is not None:
+        skshape, zptrs, skpacked = series
+        _lib.check(lib.wn_hskipsum_forward_series(ctypes.byref(skshape), mode.code, _p(skpacked), zptrs, _p(h0),
+                                                  ctypes.c_float(c.rs), ctypes.c_float(head[0]), _p(c.flag), _stream()),
+                   "wn_hskipsum_forward_series")
+    else:
+        _load(c.lib, c.mode, torch.nn.functional.leaky_relu(S, head[0]), h0, c.layout, c.rs, None, c.flag)
+    h1 = _lease(c, sh1.out_channels)
+    _lib.check(lib.wn_hconv_forward_series(ctypes.byref(sh1), mode.code, _p(pk[0]), _p(h0), _p(h1), ctypes.c_float(c.rs),
+                                           ctypes.c_float(head[1]), _p(c.flag), _stream()), "wn_hconv_forward_series")
+    y = torch.empty(c.batch, sh2.out_channels, c.layout.length, dtype=torch.float32, device=c.dev)
+    _lib.check(lib.wn_hconv_forward(ctypes.byref(sh2), mode.code, _p(pk[1]), _p(h1), _p(y), _stream()), "wn_hconv_forward")
+    return y, (head, sh1, sh2, pk, h0, h1, [tuple(t.shape) for t in head_params])
+
+
+def _head_backward(c, ctx, d_out, dyn, dyn_inv):
+    """output block, backwards, in the series: d_out is the cotangent of its OUTPUT.  Returns (dS, [dw1, db1, dw2, db2])."""
+    lib, mode = c.lib, c.mode
+    (slope1, slope2), sh1, sh2, pk, h0, h1, hshapes = ctx.head
+    dY = _lease(c, sh2.out_channels)
+    _load(c.lib, c.mode, d_out, dY, c.layout, 1.0, dyn, c.flag)
+    dh1 = _lease(c, sh1.out_channels)
+    _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(sh2), mode.code, _p(pk[1]), _p(dY), _p(h1), ctypes.c_float(slope2),
+                                                 _p(dh1), _p(c.flag), _stream()), "wn_hconv_backward_data_series")
+    dS = _lease(c, sh1.in_channels)
+    _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(sh1), mode.code, _p(pk[0]), _p(dh1), _p(h0), ctypes.c_float(slope1),
+                                                 _p(dS), _p(c.flag), _stream()), "wn_hconv_backward_data_series")
+    grads = _hconv_wgrad(c, sh1, h0, dh1, hshapes[0], True, dyn_inv) + _hconv_wgrad(c, sh2, h1, dY, hshapes[2], True, dyn_inv)
+    ctx.head = None
+    return dS, list(grads)
+
+
+# The backward-data forms of a block.  dz is pointwise in time and its dr is the dx of the block above: where two consecutive blocks
+# both take the column-owner kernels, dx of the upper and dz of the lower run as ONE launch (wn_hblock_backward_pair): the chain is
+# then dz(top), [dx(l) + dz(l - 1)] ..., dx(bottom) -- n + 1 launches instead of 2 n.
+BWD_TOP_PAIR = "dz of the top of a pair chain (no dx destination), then the pair launch"
+BWD_PAIR = "pair launch: this block's dx + the dz of the block below"
+BWD_INPUT = "bottom of a chain: the input gradient alone (series, masked by the feature layer's LeakyReLU, or dense)"
+BWD_NOTHING = "bottom of a chain whose input needs no gradient: its dz (da, dg) is all that was needed"
+BWD_MASKED = "dz + dx, the feature layer's LeakyReLU backward in the dx epilogue"
+BWD_PLAIN = "dz + dx"
+
+
+def backward_data_form(paired, have_dz, want_dx, want_dxd, masked):
+    """The backward-data form of a block.  paired: it and the block below take the pair launch; have_dz: the pair launch above has
+    produced its (da, dg) already; want_dx / want_dxd: its input gradient is wanted as a series / as a dense tensor;
+    masked: its input is leaky(feature conv), whose backward rides in this block's dx epilogue."""
+    if paired:
+        return BWD_PAIR if have_dz else BWD_TOP_PAIR
+    if have_dz:
+        return BWD_INPUT if (want_dx or want_dxd) else BWD_NOTHING
+    return BWD_MASKED if masked else BWD_PLAIN
+
+
+def _backward_data(c, form, blk, below, dr, dS, gates, dx, dxd, dyn_inv, mask_slope):
+    """launch `form` for the block blk = (x, sg, z, packed, shape) with gates = (da, dg); `below` is the block under it (pair forms).
+    Returns the (da, dg) that a pair launch has produced for the block below, else None."""
+    lib, code, flag = c.lib, c.mode.code, c.flag
+    x, sg, z, packed, shape = blk
+    da, dg = gates
+    if form is BWD_TOP_PAIR or form is BWD_PLAIN:
+        top = form is BWD_TOP_PAIR
+        _lib.check(lib.wn_hblock_backward_data(ctypes.byref(shape), code, _p(packed), _p(dr), _p(dS), _p(z), _p(sg), _p(da), _p(dg),
+                                               None if top else _p(dx), None if top else _p(dxd), _p(dyn_inv), _p(flag), _stream()),
+                   "wn_hblock_backward_data")
+    if form is BWD_TOP_PAIR or form is BWD_PAIR:
+        _xl, sgl, zl, packedl, shapel = below
+        dal, dgl = _lease(c, shapel.out_channels), _lease(c, shapel.out_channels)
+        _lib.check(lib.wn_hblock_backward_pair(ctypes.byref(shape), _p(packed), ctypes.byref(shapel), _p(packedl), code,
+                                               _p(dr), _p(da), _p(dg), _p(dS), _p(zl), _p(sgl), _p(dx), _p(dal), _p(dgl),
+                                               _p(flag), _stream()), "wn_hblock_backward_pair")
+        return dal, dgl
+    if form is BWD_INPUT:
+        masked = mask_slope is not None
+        _lib.check(lib.wn_hblock_backward_input(ctypes.byref(shape), code, _p(packed), _p(dr), _p(da), _p(dg), _p(dx), _p(dxd),
+                                                _p(dyn_inv), _p(x) if masked else None, ctypes.c_float(mask_slope if masked else 1.0),
+                                                _p(flag), _stream()), "wn_hblock_backward_input")
+    elif form is BWD_MASKED:
+        # (x = the stored activation is the mask)
+        _lib.check(lib.wn_hblock_backward_data_masked(ctypes.byref(shape), code, _p(packed), _p(dr), _p(dS), _p(z), _p(sg),
+                                                      _p(da), _p(dg), _p(dx), _p(x), ctypes.c_float(mask_slope), _p(flag),
+                                                      _stream()), "wn_hblock_backward_data_masked")
+    return None
+
+
+def _block_wgrad(c, blk, gates, dr, dS, grads, dyn_inv):
+    """the weight gradients of one block on its own launch"""
+    x, _sg, z, _packed, shape = blk
+    ws_bytes = c.lib.wn_hblock_wgrad_workspace_bytes(ctypes.byref(shape), c.mode.code)
+    ws = _workspace(ws_bytes, c.dev)
+    gs = _params_struct(grads)
+    _lib.check(c.lib.wn_hblock_backward_weights(ctypes.byref(shape), c.mode.code, _p(x), _p(z), _p(gates[0]), _p(gates[1]), _p(dr),
+                                                _p(dS), ctypes.byref(gs), _p(dyn_inv), _p(ws), ws_bytes, _stream()),
+               "wn_hblock_backward_weights")
+
+
+def _backward_chain(c, ctx, dS, dyn_inv):
+    """the blocks, top to bottom; returns (gradient series of the stack's input or None, its dense gradient or None, the blocks'
+    gradients, flat)"""
+    specs, saved = ctx.specs, ctx.saved
+    grads_flat = [None] * (len(specs) * PARAMS_PER_BLOCK)
+    grouped, group_end = _wgrad_plan(c.lib, c.mode, [sv[4] for sv in saved])
+    pending = []          # blocks of a weight-gradient group whose launch is still to come
+    dr = dx0 = None
+    gates = None          # (da, dg) of the block about to be processed, if the pair launch above it has produced them
+    for l in range(len(specs) - 1, -1, -1):
+        spec, blk = specs[l], saved[l]
+        have_dz = gates is not None
+        da, dg = gates if have_dz else (_lease(c, spec.co), _lease(c, spec.co))
+        dx = dxd = None
+        if l > 0 or ctx.front is not None:
+            dx = _lease(c, spec.ci)
+        elif ctx.needs_input_grad[0]:
+            dxd = dx0 = torch.empty(c.batch, spec.ci, c.layout.length, dtype=torch.float32, device=c.dev)
+        paired = l > 0 and c.lib.wn_hblock_backward_pair_is_fused(ctypes.byref(blk[4]), ctypes.byref(saved[l - 1][4]), c.mode.code) == 1
+        masked = l == 0 and ctx.front is not None
+        form = backward_data_form(paired, have_dz, dx is not None, dxd is not None, masked)
+        next_gates = _backward_data(c, form, blk, saved[l - 1] if paired else None, dr, dS, (da, dg), dx, dxd, dyn_inv,
+                                    ctx.front[0][1] if masked else None)
+        grads = _alloc_block_grads(spec, dr, c.dev)
+        if l in grouped:
+            pending.append((blk[4], blk[0], blk[2], da, dg, dr, grads))
+            if l in group_end:
+                _flush_wgrad(c, pending, dS, dyn_inv)
+        else:
+            _block_wgrad(c, blk, (da, dg), dr, dS, grads, dyn_inv)
+        grads_flat[l * PARAMS_PER_BLOCK:(l + 1) * PARAMS_PER_BLOCK] = grads
+        dr, gates = dx, next_gates
+        saved[l] = None
+    _flush_wgrad(c, pending, dS, dyn_inv)
+    return dr, dx0, grads_flat
+
+
+def _front_backward(c, ctx, dr, dyn_inv):
+    """feature layer, backwards: dr is the (masked) gradient of the stack's input, in the series; returns [dw0, db0, dw1, db1]"""
+    lib, mode, lay = c.lib, c.mode, c.layout
+    (slope0, _slope1), xd, f1, fsh, fpk, L_in, fshapes = ctx.front
+    F0, k0 = fsh.in_channels, fshapes[0][2]
+    df1 = _lease(c, F0)
+    _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(fsh), mode.code, _p(fpk), _p(dr), _p(f1), ctypes.c_float(slope0),
+                                                 _p(df1), _p(c.flag), _stream()), "wn_hconv_backward_data_series")
+    dw1, db1 = _hconv_wgrad(c, fsh, f1, dr, fshapes[2], True, dyn_inv)
+    dw0 = torch.empty(fshapes[0], dtype=torch.float32, device=c.dev)
+    db0 = torch.empty(fshapes[1], dtype=torch.float32, device=c.dev)
+    ws_bytes = lib.wn_hfeature_wgrad_workspace_bytes(c.batch, L_in, F0, k0)
+    ws0 = _workspace(ws_bytes, c.dev)
+    _lib.check(lib.wn_hfeature_backward_weights(mode.code, _p(xd), _p(df1), ctypes.c_float(1.0), _p(dw0), _p(db0), c.batch, L_in, F0, k0,
+                                                lay.ld, lay.halo, _p(dyn_inv), _p(ws0), ws_bytes, _stream()),
+               "wn_hfeature_backward_weights")
+    ctx.front = None
+    return [dw0, db0, dw1, db1]
+
+
 class _HalfStackFn(torch.autograd.Function):
     """skips_sum of a stack (modules/wavenet.py:98-100 with folded bottlenecks) on the half-precision MFMAs"""
 
     @staticmethod
     @_on_device_of_first_tensor
     def forward(ctx, x, specs, mode, grad_enabled, pack_cache, head, front, pool, *flat):
-        """head: None, or (slope1, slope2) of an output block LeakyReLU(slope1), Conv1d 1x1, LeakyReLU(slope2), Conv1d 1x1
-        (modules/wavenet.py:67-71, raw_ctcnet.py:89-93) whose parameters (w1, b1, w2, b2) are the last four tensors of `flat`:
-        the block then runs inside this function, in the half series, and the function returns its output instead of skips_sum."""
+        """arguments as residual_stack's; head and front = their slopes, their parameters at the end of `flat` (_split_flat)"""
         lib = _lib.load()
         _require_device(x, "input")
         _flags.WATCH.poll()
         n = len(specs)
-        head_params = front_params = None
-        if front is not None:      # (slope0, slope1): RawCTCNet.feature_layer = Conv1d(1 -> F, k, padding k - 1), LeakyReLU, Conv1d 1x1, LeakyReLU
-            front_params = [t.detach().contiguous() for t in flat[-4:]]   # parameters w0, b0, w1, b1: the LAST four tensors of flat
-            flat = flat[:-4]
-        if head is not None:       # its parameters (w1, b1, w2, b2) come right before the front's
-            head_params = [t.detach().contiguous() for t in flat[-4:]]
-            flat = flat[:-4]
-        assert len(flat) == n * PARAMS_PER_BLOCK
+        flat, head_params, front_params = _split_flat(flat, n, head is not None, 0 if front is None else 4)
         B, C0, L = x.shape
         ctx.pool, ctx.in_length = int(pool), L
-        if pool > 1:               # AvgPool1d(pool) of x (reference modules/classifier.py:53,102) fused into the load of the input series
-            if front is not None:
-                raise RuntimeError("wavenet_speech_amd: pooling and a feature layer in front of one stack are not combined")
-            L = L // pool
-            if L < 1:
-                raise RuntimeError("wavenet_speech_amd: sequence shorter than the pooling window")
+        L = _pooled_length(L, pool, front, "feature layer")
         if front is not None:
-            fw0, fb0, fw1, fb1 = front_params
+            fw0, fw1 = front_params[0], front_params[2]
             if C0 != 1 or fw0.shape[1] != 1 or fw1.shape[2] != 1 or fw1.shape[1] != fw0.shape[0]:
                 raise RuntimeError("wavenet_speech_amd: feature layer shapes %s, %s do not fit a one-channel signal" %
                                    (tuple(fw0.shape), tuple(fw1.shape)))
-            L_in, L = L, L + fw0.shape[2] - 1     # padding k - 1 on both sides lengthens the sequence (raw_ctcnet.py:57-61)
+            L = L + fw0.shape[2] - 1     # padding k - 1 on both sides lengthens the sequence (raw_ctcnet.py:57-61)
             C0 = fw1.shape[0]
-        if C0 != specs[0].ci:
-            raise RuntimeError("wavenet_speech_amd: input has %d channels, first block expects %d" % (C0, specs[0].ci))
-        for l in range(1, n):
-            if specs[l].ci != specs[l - 1].co:
-                raise RuntimeError("wavenet_speech_amd: block %d expects %d input channels but block %d produces %d"
-                                   % (l, specs[l].ci, l - 1, specs[l - 1].co))
-        dev = x.device
-        layout = HalfLayout(L, max(s.reach() for s in specs))
+        ms = _check_stack(specs, C0)
         training = bool(grad_enabled) and any(ctx.needs_input_grad)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev) if mode.dtype == torch.float16 else None
-        rs = float(lib.wn_hseries_residual_scale())
-        cur = _hlease(mode, B, C0, layout, dev)
-        ctx.front = None
-        if front is None and pool > 1:
-            _lib.check(lib.wn_hseries_load_pooled(mode.code, _p(x.detach().contiguous()), _p(cur), B, C0, ctx.in_length, int(pool),
-                                                  layout.ld, layout.halo, ctypes.c_float(rs), None, _p(flag), _stream()),
-                       "wn_hseries_load_pooled")
-        elif front is None:
-            _load(lib, mode, x.detach().contiguous(), cur, layout, rs, None, flag)
-        else:
-            # ---- feature layer in the series layout: the raw signal -> leaky(conv k) (elementwise kernel) -> leaky(conv 1x1) --------
-            F0, k0 = fw0.shape[0], fw0.shape[2]
-            xd = x.detach().contiguous()
-            f1 = _hlease(mode, B, F0, layout, dev)
-            _lib.check(lib.wn_hfeature_forward(mode.code, _p(xd), _p(fw0), _p(fb0), _p(f1), B, L_in, F0, k0, layout.ld, layout.halo,
-                                               ctypes.c_float(rs), ctypes.c_float(front[0]), _p(flag), _stream()), "wn_hfeature_forward")
-            fsh = _lib.ConvShape(B, L, F0, C0, 1, 1, 1, layout.ld, layout.halo)
-            nbytes = lib.wn_hconv_packed_bytes(ctypes.byref(fsh), mode.code)
-            if nbytes == 0:
-                _lib.check(-1, "wn_hconv_packed_bytes")
-            fpk = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.wn_hconv_pack(ctypes.byref(fsh), mode.code, _p(fw1), _p(fb1), ctypes.c_float(rs), _p(fpk), _stream()),
-                       "wn_hconv_pack")
-            _lib.check(lib.wn_hconv_forward_series(ctypes.byref(fsh), mode.code, _p(fpk), _p(f1), _p(cur), ctypes.c_float(rs),
-                                                   ctypes.c_float(front[1]), _p(flag), _stream()), "wn_hconv_forward_series")
-            if training:
-                ctx.front = (front, xd, f1, fsh, fpk, L_in, [tuple(t.shape) for t in front_params])
-        ms = specs[0].ms
-        S = torch.empty(B, ms, L, dtype=torch.float32, device=dev)
-        saved, skip_w, skip_b = [], [], []
-        zbuf = None
-        for spec in specs:
-            if spec.ms != ms:
-                raise RuntimeError("wavenet_speech_amd: all blocks of a stack must share out_dim")
+        c = _hcall(lib, B, HalfLayout(L, max(s.reach() for s in specs)), x.device, mode)
+        cur, front_saved = _input_series(c, x, pool, front, front_params)
+        ctx.front = front_saved if training else None
+        S = torch.empty(B, ms, L, dtype=torch.float32, device=x.device)
         prepped = [_prep_params(flat[l * PARAMS_PER_BLOCK:(l + 1) * PARAMS_PER_BLOCK], spec) for l, spec in enumerate(specs)]
-        # every pack job of the stack (5 per block + in training the long-K skips_sum weights) from ONE launch of a device-resident
-        # job table (StackPackTable); WN_PACK_TABLE=0 or an unsupported layout falls back to the per-block entry points
-        table = packed_all = None
         frozen = pack_cache is not None and pack_cache.frozen and not grad_enabled
-        if pack_cache is not None and not frozen and os.environ.get("WN_PACK_TABLE", "1") != "0":
-            storages = StackPackTable.dynamic_storages(flat)
-            if storages is not None:
-                key = StackPackTable.key_of(specs, mode, B, layout, prepped, storages, training)
-                table = pack_cache.tables.get(key)
-                if table is None:
-                    try:
-                        table = StackPackTable(lib, specs, mode, B, layout, prepped, storages, training, dev)
-                    except NotImplementedError:
-                        table = False          # e.g. skip biases that are not equally spaced: per-block packing
-                    if len(pack_cache.tables) >= 8:
-                        pack_cache.tables.clear()
-                    pack_cache.tables[key] = table
-                if table:
-                    packed_all = table.run(lib, storages, dev, flag)
-                else:
-                    table = None
-        for l, spec in enumerate(specs):
-            shape = _shape(spec, B, layout)
-            params = prepped[l]
-            if table is not None:
-                packed = packed_all.data_ptr() + table.block_offsets[l]
-            else:
-                packed = pack_cache.get(l, layout, B) if (pack_cache is not None and pack_cache.frozen and not grad_enabled) else None
-            if packed is None:
-                nbytes = lib.wn_hblock_packed_bytes(ctypes.byref(shape), mode.code)
-                if nbytes == 0:
-                    _lib.check(-1, "wn_hblock_packed_bytes")
-                packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                ps = _params_struct(params)
-                _lib.check(lib.wn_hblock_pack_checked(ctypes.byref(shape), mode.code, ctypes.byref(ps), _p(packed), _p(flag), _stream()),
-                           "wn_hblock_pack_checked")
-                if pack_cache is not None and pack_cache.frozen and not grad_enabled:
-                    pack_cache.put(l, layout, B, packed)
-            r = _hlease(mode, B, spec.co, layout, dev) if l + 1 < n else None
-            if training:
-                sg, z = (_hlease(mode, B, spec.co, layout, dev) for _ in range(2))   # kept for backward; tanh = z / sg
-            elif lib.wn_hblock_forward_is_fused(ctypes.byref(shape), mode.code):
-                sg = z = None                  # inference through the fused kernel: z stays on the chip
-            else:
-                sg = None
-                if zbuf is None or zbuf.channels != spec.co:
-                    zbuf = _hlease(mode, B, spec.co, layout, dev)
-                z = zbuf
-            _lib.check(lib.wn_hblock_forward(ctypes.byref(shape), mode.code, _p(packed), _p(cur), _p(r),
-                                             None if training else _p(S), 0 if l == 0 else 1, _p(sg), _p(z),
-                                             _p(flag), _stream()), "wn_hblock_forward")
-            if training:
-                saved.append((cur, sg, z, packed, shape))
-                skip_w.append(params[6])
-                skip_b.append(params[7])
-            cur = r
+        # the blocks' packed weights live in ctx.packed_all until backward has run
+        ctx.packed_all, blocks_packed, groups = _pack_stack(c, pack_cache, frozen, specs, prepped, flat, training)
+        series = [cur]       # handed over: the loop drops each block's input once nothing needs it any more
+        del cur
+        saved = _forward_blocks(c, specs, blocks_packed, series, S, training)
         series_head = head is not None and training and n <= _lib.MAX_STACK_GROUP
-        ctx.skipsum_packed = None
+        ctx.skipsum_packed = sk = None
         if training:
-            G = _lib.MAX_STACK_GROUP
-            bias_total = torch.stack(skip_b).sum(0).contiguous() if table is None else None
-            for gi, g0 in enumerate(range(0, n, G)):
-                idx = range(g0, min(g0 + G, n))
-                m = len(idx)
-                shape = _lib.SkipSumShape(B, L, ms, m, layout.ld, layout.halo)
-                for i, l in enumerate(idx):
-                    shape.channels[i] = specs[l].co
-                zptrs = (ctypes.c_void_p * m)(*[saved[l][2].ptr for l in idx])
-                if table is not None:
-                    packed = packed_all.data_ptr() + table.skipsum_offsets[gi]
-                else:
-                    nbytes = lib.wn_hskipsum_packed_bytes(ctypes.byref(shape), mode.code)
-                    if nbytes == 0:
-                        _lib.check(-1, "wn_hskipsum_packed_bytes")
-                    packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                    wptrs = (ctypes.c_void_p * m)(*[skip_w[l].data_ptr() for l in idx])
-                    _lib.check(lib.wn_hskipsum_pack(ctypes.byref(shape), mode.code, wptrs, _p(bias_total) if g0 == 0 else None,
-                                                    _p(packed), _stream()), "wn_hskipsum_pack")
-                if series_head:
-                    ctx.skipsum_packed = packed            # the head below writes leaky(S) as a series: no dense S
-                else:
-                    _lib.check(lib.wn_hskipsum_forward(ctypes.byref(shape), mode.code, _p(packed), zptrs, _p(S),
-                                                       0 if g0 == 0 else 1, _stream()), "wn_hskipsum_forward")
-        ctx.packed_all = packed_all       # the blocks' packed weights live here until backward has run
+            sk = _skips_sum(c, specs, saved, prepped, groups, None if series_head else S)
+            if series_head:
+                ctx.skipsum_packed = sk[2]
         ctx.head = None
         if head is not None:
-            # ---- output block in the series layout: leaky(S) -> conv1 -> leaky -> conv2 (dense fp32 out) ------------------------
-            w1, b1, w2, b2 = head_params
-            c1, c2 = w1.shape[0], w2.shape[0]
-            if w1.shape[1] != ms or w2.shape[1] != c1 or w1.shape[2] != 1 or w2.shape[2] != 1:
-                raise RuntimeError("wavenet_speech_amd: output block shapes %s, %s do not follow a stack of out_dim %d"
-                                   % (tuple(w1.shape), tuple(w2.shape), ms))
-            sh1 = _lib.ConvShape(B, L, ms, c1, 1, 1, 1, layout.ld, layout.halo)
-            sh2 = _lib.ConvShape(B, L, c1, c2, 1, 1, 1, layout.ld, layout.halo)
-            pk = []
-            for sh, w, b_ in ((sh1, w1, b1), (sh2, w2, b2)):
-                nbytes = lib.wn_hconv_packed_bytes(ctypes.byref(sh), mode.code)
-                if nbytes == 0:
-                    _lib.check(-1, "wn_hconv_packed_bytes")
-                p_ = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                _lib.check(lib.wn_hconv_pack(ctypes.byref(sh), mode.code, _p(w), _p(b_), ctypes.c_float(rs), _p(p_), _stream()),
-                           "wn_hconv_pack")
-                pk.append(p_)
-            h0 = _hlease(mode, B, ms, layout, dev)
-            if series_head:
-                # the long-K skips_sum product writes leaky(S) / 16 straight into the series: no dense fp32 S at all
-                skshape = _lib.SkipSumShape(B, L, ms, n, layout.ld, layout.halo)
-                for i in range(n):
-                    skshape.channels[i] = specs[i].co
-                zptrs = (ctypes.c_void_p * n)(*[saved[l][2].ptr for l in range(n)])
-                _lib.check(lib.wn_hskipsum_forward_series(ctypes.byref(skshape), mode.code, _p(ctx.skipsum_packed), zptrs, _p(h0),
-                                                          ctypes.c_float(rs), ctypes.c_float(head[0]), _p(flag), _stream()),
-                           "wn_hskipsum_forward_series")
-            else:
-                _load(lib, mode, torch.nn.functional.leaky_relu(S, head[0]), h0, layout, rs, None, flag)
-            h1 = _hlease(mode, B, c1, layout, dev)
-            _lib.check(lib.wn_hconv_forward_series(ctypes.byref(sh1), mode.code, _p(pk[0]), _p(h0), _p(h1), ctypes.c_float(rs),
-                                                   ctypes.c_float(head[1]), _p(flag), _stream()), "wn_hconv_forward_series")
-            y = torch.empty(B, c2, L, dtype=torch.float32, device=dev)
-            _lib.check(lib.wn_hconv_forward(ctypes.byref(sh2), mode.code, _p(pk[1]), _p(h1), _p(y), _stream()), "wn_hconv_forward")
+            S, head_saved = _head_forward(c, head, head_params, S, sk if series_head else None)
             if training:
-                ctx.head = (head, sh1, sh2, pk, h0, h1, [tuple(t.shape) for t in head_params])
-            S = y
-        _flags.WATCH.note(flag, _OVERFLOW_MSG % "forward pass", at_once=not training)
-        ctx.specs, ctx.saved, ctx.layout, ctx.batch, ctx.mode = specs, saved, layout, B, mode
+                ctx.head = head_saved
+        _flags.WATCH.note(c.flag, _OVERFLOW_MSG % "forward pass", at_once=not training)
+        ctx.specs, ctx.saved, ctx.layout, ctx.batch, ctx.mode = specs, saved, c.layout, B, mode
         ctx.param_shapes = [tuple(t.shape) for t in flat]
         return S
 
@@ -418,172 +578,21 @@ class _HalfStackFn(torch.autograd.Function):
     def backward(ctx, d_skips):
         lib = _lib.load()
         _flags.WATCH.poll()
-        specs, layout, B, mode = ctx.specs, ctx.layout, ctx.batch, ctx.mode
-        dev = d_skips.device
         d_skips = d_skips.contiguous()
-        flag = torch.zeros(1, dtype=torch.int32, device=dev) if mode.dtype == torch.float16 else None
-        dyn, dyn_inv = _grad_scale(d_skips, mode)
-        head_grads = []
+        c = _hcall(lib, ctx.batch, ctx.layout, d_skips.device, ctx.mode)
+        dyn, dyn_inv = _grad_scale(d_skips, c.mode)
+        head_grads, front_grads = [], []
         if ctx.head is None:
-            dS = _hlease(mode, B, specs[0].ms, layout, dev)
-            _load(lib, mode, d_skips, dS, layout, 1.0, dyn, flag)
+            dS = _lease(c, ctx.specs[0].ms)
+            _load(c.lib, c.mode, d_skips, dS, c.layout, 1.0, dyn, c.flag)
         else:
-            # ---- output block, backwards, in the series: d_skips is the cotangent of its OUTPUT here ----------------------------
-            (slope1, slope2), sh1, sh2, pk, h0, h1, hshapes = ctx.head
-            rs = float(lib.wn_hseries_residual_scale())
-            c1, c2 = sh1.out_channels, sh2.out_channels
-            dY = _hlease(mode, B, c2, layout, dev)
-            _load(lib, mode, d_skips, dY, layout, 1.0, dyn, flag)
-            dh1 = _hlease(mode, B, c1, layout, dev)
-            _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(sh2), mode.code, _p(pk[1]), _p(dY), _p(h1), ctypes.c_float(slope2),
-                                                         _p(dh1), _p(flag), _stream()), "wn_hconv_backward_data_series")
-            dS = _hlease(mode, B, specs[0].ms, layout, dev)
-            _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(sh1), mode.code, _p(pk[0]), _p(dh1), _p(h0), ctypes.c_float(slope1),
-                                                         _p(dS), _p(flag), _stream()), "wn_hconv_backward_data_series")
-            for sh, xin, dy_, shp_w, shp_b in ((sh1, h0, dh1, hshapes[0], hshapes[1]), (sh2, h1, dY, hshapes[2], hshapes[3])):
-                dw = torch.empty(shp_w, dtype=torch.float32, device=dev)
-                db = torch.empty(shp_b, dtype=torch.float32, device=dev)
-                ws_bytes = lib.wn_hconv_wgrad_workspace_bytes(ctypes.byref(sh), mode.code)
-                ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-                _lib.check(lib.wn_hconv_backward_weights(ctypes.byref(sh), mode.code, _p(xin), _p(dy_), ctypes.c_float(rs), _p(dw), _p(db),
-                                                         _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hconv_backward_weights")
-                head_grads += [dw, db]
-            ctx.head = None
-        dr = None
-        dx0 = None
-        grads_flat = [None] * (len(specs) * PARAMS_PER_BLOCK)
-        # weight gradients: small blocks (<= 128 channels) are two or three gradient tiles each -- their operands are kept and
-        # several blocks go into ONE split-K launch + ONE reduction (wn_hblocks_backward_weights); WN_WGRAD_GROUP=1 = per block.
-        # The groups come from every block's own shape (wgrad_groups), in the order the loop below reaches the blocks.
-        env_group = os.environ.get("WN_WGRAD_GROUP")
-        order = list(range(len(specs) - 1, -1, -1))
-        shapes = [ctx.saved[l][4] for l in order]
-        gkey = (mode.code, env_group, os.environ.get("WN_HWGRAD_COMPOSITE"), tuple(tuple(getattr(s, f) for f, _ in s._fields_) for s in shapes))
-        groups = _WGRAD_GROUPS.get(gkey)
-        if groups is None:           # (the plan depends on the shapes only: planned once per stack geometry)
-            groups = wgrad_groups(lib, shapes, mode.code, int(env_group) if env_group else None)
-            if len(_WGRAD_GROUPS) >= 64:
-                _WGRAD_GROUPS.clear()
-            _WGRAD_GROUPS[gkey] = groups
-        grouped, group_end = set(), set()
-        for is_group, pos in groups:
-            if is_group:
-                grouped.update(order[p] for p in pos)
-                group_end.add(order[pos[-1]])
-        pending = []          # (l, shape, x, z, da, dg, dr, grads) of blocks whose weight gradients are not launched yet
-
-        def flush():
-            if not pending:
-                return
-            m = len(pending)
-            shapes = (_lib.BlockShape * m)(*[e[1] for e in pending])
-            arr = lambda i: (ctypes.c_void_p * m)(*[(e[i].ptr if e[i] is not None else None) for e in pending])
-            dsk = (ctypes.c_void_p * m)(*[dS.ptr] * m)
-            gs = (_lib.BlockParams * m)(*[_params_struct(e[7]) for e in pending])
-            ws_bytes = lib.wn_hblocks_wgrad_workspace_bytes(shapes, m, mode.code)
-            if ws_bytes == 0:
-                _lib.check(-1, "wn_hblocks_wgrad_workspace_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.wn_hblocks_backward_weights(shapes, m, mode.code, arr(2), arr(3), arr(4), arr(5), arr(6), dsk, gs,
-                                                       _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hblocks_backward_weights")
-            del pending[:]
-
-        # dz is pointwise in time and its dr is the dx of the block above: where two consecutive blocks both take the column-owner
-        # kernels, dx of the upper and dz of the lower run as ONE launch (wn_hblock_backward_pair): the chain is then
-        # dz(top), [dx(l) + dz(l - 1)] ..., dx(bottom) -- n + 1 launches instead of 2 n.
-        gates = None          # (da, dg) of the block about to be processed, if the pair launch above it has produced them
-        for l in range(len(specs) - 1, -1, -1):
-            spec = specs[l]
-            x, sg, z, packed, shape = ctx.saved[l]
-            have_dz = gates is not None
-            da, dg = gates if have_dz else (_hlease(mode, B, spec.co, layout, dev), _hlease(mode, B, spec.co, layout, dev))
-            gates = None
-            dx = dxd = None
-            if l > 0 or ctx.front is not None:
-                dx = _hlease(mode, B, spec.ci, layout, dev)
-            elif ctx.needs_input_grad[0]:
-                dxd = dx0 = torch.empty(B, spec.ci, layout.length, dtype=torch.float32, device=dev)
-            paired = l > 0 and lib.wn_hblock_backward_pair_is_fused(ctypes.byref(shape), ctypes.byref(ctx.saved[l - 1][4]), mode.code) == 1
-            if paired and not have_dz:
-                # the top of a chain: its own dz first (dz only: no dx destination)
-                _lib.check(lib.wn_hblock_backward_data(ctypes.byref(shape), mode.code, _p(packed), _p(dr), _p(dS), _p(z), _p(sg),
-                                                       _p(da), _p(dg), None, None, _p(dyn_inv), _p(flag), _stream()),
-                           "wn_hblock_backward_data")
-                have_dz = True
-            if paired:
-                _xl, sgl, zl, packedl, shapel = ctx.saved[l - 1]
-                dal, dgl = _hlease(mode, B, specs[l - 1].co, layout, dev), _hlease(mode, B, specs[l - 1].co, layout, dev)
-                _lib.check(lib.wn_hblock_backward_pair(ctypes.byref(shape), _p(packed), ctypes.byref(shapel), _p(packedl), mode.code,
-                                                       _p(dr), _p(da), _p(dg), _p(dS), _p(zl), _p(sgl), _p(dx), _p(dal), _p(dgl),
-                                                       _p(flag), _stream()), "wn_hblock_backward_pair")
-                gates = (dal, dgl)
-            elif have_dz and dx is None and dxd is None:
-                pass          # the bottom of a chain whose input needs no gradient: its dz (da, dg) is all that was needed
-            elif have_dz:
-                # the bottom of a chain: the input gradient alone (series, masked by the feature layer's LeakyReLU, or dense)
-                masked = l == 0 and ctx.front is not None
-                _lib.check(lib.wn_hblock_backward_input(ctypes.byref(shape), mode.code, _p(packed), _p(dr), _p(da), _p(dg), _p(dx), _p(dxd),
-                                                        _p(dyn_inv), _p(x) if masked else None,
-                                                        ctypes.c_float(ctx.front[0][1] if masked else 1.0), _p(flag), _stream()),
-                           "wn_hblock_backward_input")
-            elif l == 0 and ctx.front is not None:
-                # the stack's input is leaky(feature conv): its LeakyReLU backward rides in this block's dx epilogue (x = the stored activation)
-                _lib.check(lib.wn_hblock_backward_data_masked(ctypes.byref(shape), mode.code, _p(packed), _p(dr), _p(dS), _p(z), _p(sg),
-                                                              _p(da), _p(dg), _p(dx), _p(x), ctypes.c_float(ctx.front[0][1]), _p(flag),
-                                                              _stream()), "wn_hblock_backward_data_masked")
-            else:
-                _lib.check(lib.wn_hblock_backward_data(ctypes.byref(shape), mode.code, _p(packed), _p(dr), _p(dS), _p(z), _p(sg),
-                                                       _p(da), _p(dg), _p(dx), _p(dxd), _p(dyn_inv), _p(flag), _stream()),
-                           "wn_hblock_backward_data")
-            k = spec.k
-            shapes = [(spec.co, spec.ci, k), (spec.co,), (spec.co, spec.ci, k), (spec.co,), (spec.co, spec.co), (spec.co,),
-                      (spec.ms, spec.co), (spec.ms,), (spec.co, spec.ci), (spec.co,)]
-            unused = (4, 5, 8, 9) if dr is None else ()
-            grads = [None if i in unused else torch.empty(s, dtype=torch.float32, device=dev) for i, s in enumerate(shapes)]
-            if l in grouped:
-                pending.append((l, shape, x, z, da, dg, dr, grads))
-                if l in group_end:
-                    flush()
-            else:
-                ws_bytes = lib.wn_hblock_wgrad_workspace_bytes(ctypes.byref(shape), mode.code)
-                ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-                gs = _params_struct(grads)
-                _lib.check(lib.wn_hblock_backward_weights(ctypes.byref(shape), mode.code, _p(x), _p(z), _p(da), _p(dg), _p(dr),
-                                                          _p(dS), ctypes.byref(gs), _p(dyn_inv), _p(ws), ws_bytes, _stream()),
-                           "wn_hblock_backward_weights")
-            grads_flat[l * PARAMS_PER_BLOCK:(l + 1) * PARAMS_PER_BLOCK] = grads
-            dr = dx
-            ctx.saved[l] = None
-        flush()
-        front_grads = []
+            dS, head_grads = _head_backward(c, ctx, d_skips, dyn, dyn_inv)
+        dr, dx0, grads_flat = _backward_chain(c, ctx, dS, dyn_inv)
         if ctx.front is not None:
-            # ---- feature layer, backwards: dr is now the (masked) gradient of the stack's input, in the series ---------------------
-            (slope0, slope1), xd, f1, fsh, fpk, L_in, fshapes = ctx.front
-            rs = float(lib.wn_hseries_residual_scale())
-            F0 = fsh.in_channels
-            df1 = _hlease(mode, B, F0, layout, dev)
-            _lib.check(lib.wn_hconv_backward_data_series(ctypes.byref(fsh), mode.code, _p(fpk), _p(dr), _p(f1), ctypes.c_float(slope0),
-                                                         _p(df1), _p(flag), _stream()), "wn_hconv_backward_data_series")
-            dw1 = torch.empty(fshapes[2], dtype=torch.float32, device=dev)
-            db1 = torch.empty(fshapes[3], dtype=torch.float32, device=dev)
-            ws_bytes = lib.wn_hconv_wgrad_workspace_bytes(ctypes.byref(fsh), mode.code)
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            _lib.check(lib.wn_hconv_backward_weights(ctypes.byref(fsh), mode.code, _p(f1), _p(dr), ctypes.c_float(rs), _p(dw1), _p(db1),
-                                                     _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hconv_backward_weights")
-            k0 = fshapes[0][2]
-            dw0 = torch.empty(fshapes[0], dtype=torch.float32, device=dev)
-            db0 = torch.empty(fshapes[1], dtype=torch.float32, device=dev)
-            ws_bytes = lib.wn_hfeature_wgrad_workspace_bytes(B, L_in, F0, k0)
-            ws0 = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            _lib.check(lib.wn_hfeature_backward_weights(mode.code, _p(xd), _p(df1), ctypes.c_float(1.0), _p(dw0), _p(db0), B, L_in, F0, k0,
-                                                        layout.ld, layout.halo, _p(dyn_inv), _p(ws0), ws_bytes, _stream()),
-                       "wn_hfeature_backward_weights")
-            front_grads = [dw0, db0, dw1, db1]
-            ctx.front = None
-        _flags.WATCH.note(flag, _OVERFLOW_MSG % "backward pass", at_once=False)
+            front_grads = _front_backward(c, ctx, dr, dyn_inv)
+        _flags.WATCH.note(c.flag, _OVERFLOW_MSG % "backward pass", at_once=False)
         grads_flat = [None if g is None else g.view(shp) for g, shp in zip(grads_flat, ctx.param_shapes)]
         if dx0 is not None and ctx.pool > 1:
-            from .functional import _unpool
             dx0 = _unpool(lib, dx0, ctx.in_length, ctx.pool)
         return (dx0, None, None, None, None, None, None, None) + tuple(grads_flat) + tuple(head_grads) + tuple(front_grads)
 
@@ -627,24 +636,18 @@ class _HalfConvFn(torch.autograd.Function):
         layout = HalfLayout(L, reach)
         shape = _lib.ConvShape(B, L, Ci, Co, k, int(dilation), int(bool(causal)), layout.ld, layout.halo)
         training = bool(grad_enabled) and any(ctx.needs_input_grad)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev) if mode.dtype == torch.float16 else None
-        rs = float(lib.wn_hseries_residual_scale())           # inputs are stored as x / 16 like the residual stream
-        nbytes = lib.wn_hconv_packed_bytes(ctypes.byref(shape), mode.code)
-        if nbytes == 0:
-            _lib.check(-1 if k <= _lib.MAX_TAPS else -2, "wn_hconv_packed_bytes")
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        c = _hcall(lib, B, layout, dev, mode)                 # (c.rs: inputs are stored as x / 16 like the residual stream)
         w = weight.detach().contiguous()
         b = bias.detach().contiguous() if bias is not None else None
-        _lib.check(lib.wn_hconv_pack(ctypes.byref(shape), mode.code, _p(w), _p(b), ctypes.c_float(rs), _p(packed), _stream()),
-                   "wn_hconv_pack")
-        xin = _hlease(mode, B, Ci, layout, dev)
-        _load(lib, mode, x.detach().contiguous(), xin, layout, rs, None, flag)
+        packed = _pack_hconv(c, shape, w, b)
+        xin = _lease(c, Ci)
+        _load(lib, mode, x.detach().contiguous(), xin, layout, c.rs, None, c.flag)
         y = torch.empty(B, Co, L, dtype=torch.float32, device=dev)
         _lib.check(lib.wn_hconv_forward(ctypes.byref(shape), mode.code, _p(packed), _p(xin), _p(y), _stream()), "wn_hconv_forward")
-        _flags.WATCH.note(flag, _OVERFLOW_MSG % "input of a conv", at_once=not training)
+        _flags.WATCH.note(c.flag, _OVERFLOW_MSG % "input of a conv", at_once=not training)
         if training:
             ctx.saved = (xin, packed, shape)
-        ctx.layout, ctx.dims, ctx.has_bias, ctx.mode, ctx.rs = layout, (B, Ci, Co, k), bias is not None, mode, rs
+        ctx.layout, ctx.dims, ctx.has_bias, ctx.mode, ctx.rs = layout, (B, Ci, Co, k), bias is not None, mode, c.rs
         return y
 
     @staticmethod
@@ -667,12 +670,7 @@ class _HalfConvFn(torch.autograd.Function):
             dx = torch.empty(B, Ci, layout.length, dtype=torch.float32, device=dev)
             _lib.check(lib.wn_hconv_backward_data(ctypes.byref(shape), mode.code, _p(packed), _p(dy), _p(dx), _p(dyn_inv), _stream()),
                        "wn_hconv_backward_data")
-        dw = torch.empty(Co, Ci, k, dtype=torch.float32, device=dev)
-        db = torch.empty(Co, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        ws_bytes = lib.wn_hconv_wgrad_workspace_bytes(ctypes.byref(shape), mode.code)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.wn_hconv_backward_weights(ctypes.byref(shape), mode.code, _p(xin), _p(dy), ctypes.c_float(ctx.rs), _p(dw),
-                                                 _p(db), _p(dyn_inv), _p(ws), ws_bytes, _stream()), "wn_hconv_backward_weights")
+        dw, db = _hconv_wgrad(_HCall(lib, B, layout, dev, mode, flag, ctx.rs), shape, xin, dy, (Co, Ci, k), ctx.has_bias, dyn_inv)
         _flags.WATCH.note(flag, _OVERFLOW_MSG % "gradient of a conv", at_once=False)
         ctx.saved = None
         return dx, dw, db, None, None, None, None

@@ -2,10 +2,13 @@
 Drop-in for the reference's modules/block.py::ResidualBlock (and GatedActivationUnit): identical constructor,
 attributes, parameter names/shapes/registration order; forward = one call into the HIP library.
 """
+import os
+
 import torch
 import torch.nn as nn
 
 from .. import functional as HF
+from ..functional_half import plan_switches
 from .conv_ops import CausalConv1d, NonCausalConv1d
 
 
@@ -117,7 +120,6 @@ def head_precision(precision):
     f16x3 included -- their rounding cannot reach skips_sum, the tensor whose LeakyReLU kinks made the f16x3 ENTRY conv fail a
     golden gradient (pointwise_precision); all golden fixtures hold at the 1e-4 bar with it (tests/test_gpu_half.py) and
     the cfg3 step gains 1.6 % (64.2 -> 63.2 ms).  WN_HEAD_F32=1 keeps them exact."""
-    import os
     if precision == "f16x3" and not os.environ.get("WN_HEAD_F32"):
         return "f16x3"
     return pointwise_precision(precision)
@@ -172,8 +174,6 @@ def fusable_head(head, precision):
     """(slopes, parameters) of an output block that can run inside the stack function, in the series layout: exactly LeakyReLU,
     Conv1d 1x1, LeakyReLU, Conv1d 1x1 (every reference model's output_stack / output_block), in "f32" or in a half mode whose
     head convs follow the stack (head_precision).  None otherwise: the caller then evaluates the block itself."""
-    import os
-    import torch.nn as nn
     if head is None or os.environ.get("WN_SERIES_HEAD", "1") == "0":
         return None
     if head_precision(precision) != precision:
@@ -197,8 +197,6 @@ def fusable_front(front, precision, x):
     """(slopes, parameters) of a feature layer that can run inside the half-precision stack function: exactly Conv1d(1 -> F, k,
     padding k - 1), LeakyReLU, Conv1d 1x1, LeakyReLU (RawCTCNet.feature_layer, reference modules/raw_ctcnet.py:57-61) on a raw signal
     that needs no gradient, in a mode whose entry convs follow the stack (pointwise_precision).  None otherwise."""
-    import os
-    import torch.nn as nn
     knob = os.environ.get("WN_SERIES_FRONT", "1")
     if front is None or knob == "0":
         return None
@@ -229,7 +227,6 @@ def fusable_entry(conv, precision, x):
     run inside the fp32 stack function: its output is then written as the stack's input series and its gradient comes back as a
     series, with no dense tensor between the two.  None otherwise (a half mode, WN_SERIES_FRONT=0, an input that is not a float32
     device tensor [B, C, L]): the caller then runs the conv itself."""
-    import os
     from .conv_ops import _DilatedConv1d
     if precision != "f32" or os.environ.get("WN_SERIES_FRONT", "1") == "0":
         return None
@@ -238,6 +235,12 @@ def fusable_entry(conv, precision, x):
     if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32:
         return None
     return (conv.kernel_width, conv.dilation, conv.causal), [conv.conv1d.weight, conv.conv1d.bias]
+
+
+def packed_weights_key(precision):
+    """what kept packed weights depend on besides the parameters (PackCache.validate's `extra`): the mode and, in a half mode, the
+    switches that its plan reads at every call and that change the packed layout"""
+    return (precision,) if precision == "f32" else (precision,) + plan_switches()
 
 
 def run_stack(out, blocks, bottlenecks, state=None, head=None, front=None, pool=1):
@@ -257,7 +260,7 @@ def run_stack(out, blocks, bottlenecks, state=None, head=None, front=None, pool=
         # those is updated in place (its _version changes) or moves to other storage
         params = [p for m in blocks + bottlenecks for p in m.parameters()]
         old_key = cache.key
-        cache.validate(params, (precision,))
+        cache.validate(params, packed_weights_key(precision))
         if state.folded is None or cache.key != old_key:
             state.folded = fold_bottlenecks(blocks, bottlenecks)
         wfs, bfs = state.folded
