@@ -24,6 +24,7 @@
 // float64 because a score near -5400 over 4096 frames carries 1e-3 of fp32 rounding while per-frame decision margins of random
 // logits go down to 4e-4.  States at or beyond S hold values that are never read by a state below S (moves only go up).
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -237,9 +238,6 @@ __global__ __launch_bounds__(kMulti ? kAlnMaxThreads : 64) void ctc_align_kernel
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-}
 using namespace wn;
 
 static int check_align(int batch, int classes, int length, int max_label_len) {
@@ -279,7 +277,6 @@ int wn_ctc_align(const float* x, long long sb, long long sc, long long st, int i
     hipStream_t s = (hipStream_t)stream;
     if (threads == 64) hipLaunchKernelGGL(ctc_align_kernel<false>, dim3(batch), dim3(64), lds, s, a);
     else hipLaunchKernelGGL(ctc_align_kernel<true>, dim3(batch), dim3(threads), lds, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_align");
+    WN_HIP(hipGetLastError(), "ctc_align");
     return WN_OK;
 }

@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 using namespace wn;
@@ -22,49 +22,11 @@ namespace wn { extern int g_debug_kc; }   // diagnostic build: which kernel clas
 #endif
 
 namespace {
-
 thread_local std::string g_hip_err;
-
-int hip_fail(hipError_t e, const char* what) {
-    g_hip_err = std::string(what) + ": " + hipGetErrorString(e);
-    return WN_ERR_HIP;
-}
-#define WN_HIP(call, what)                                  \
-    do {                                                    \
-        hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_fail(e__, what);  \
-    } while (0)
-
-}  // namespace
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what) { return hip_fail(e, what); }   // for the other host translation units
-}
-namespace {
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int tiles32(int c) { return cdiv(c, 32); }
-inline int cp8(int c) { return rup(c, 8); }
-inline int pick_mt(int ntiles) { return ntiles > 2 ? 4 : (ntiles == 2 ? 2 : 1); }
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------------------------------
 // profiling (HIP events on the launch stream)
 // ------------------------------------------------------------------------------------------
-enum KernelClass {   // the half-precision classes (KC_HLOAD...) are used by wn_half_api.hip, which repeats this order
-    KC_PACK = 0, KC_GATE_GEMM, KC_OUT_GEMM, KC_DZ_GEMM, KC_DX_GEMM, KC_WGRAD, KC_WGRAD_REDUCE,
-    KC_CONV_FWD, KC_CONV_BWD_DATA, KC_SKIP_GEMM, KC_HLOAD, KC_HGATE, KC_HRES, KC_HDZ, KC_HDX, KC_HSKIP, KC_HWGRAD, KC_EMBED,
-    KC_SYNTH, KC_CTC, KC_HFUSED, KC_HCONV_FWD, KC_HCONV_BWD_DATA, KC_HCOL_DZ, KC_HCOL_DX, KC_HCOL_DXDZ, KC_HCOL_SKIP,
-    KC_COUNT
-};
-const char* const kKernelNames[KC_COUNT] = {
-    "pack_kernel", "series_gemm_kernel<gate>", "series_gemm_kernel<res>", "series_gemm_kernel<dz,dgate>",
-    "series_gemm_kernel<dx>", "wgrad_kernel", "wgrad_reduce_kernel", "series_gemm_kernel<conv_fwd>",
-    "series_gemm_kernel<conv_bwd_data>", "series_gemm_kernel<skips_sum>", "hload_kernel", "hgemm_kernel<gate>",
-    "hgemm_kernel<res>", "hgemm_kernel<dz,dgate>", "hgemm_kernel<dx>", "hgemm_kernel<skips_sum>", "hwgrad_kernel",
-    "embed_kernel", "synth_kernel", "ctc_kernel", "hfused_fwd_kernel",
-    "hgemm_kernel<conv_fwd>", "hgemm_kernel<conv_bwd_data>", "hcol_kernel<dz,dgate>", "hcol_kernel<dx>", "hcol2_kernel<dx+dz>", "hcol_kernel<skips_sum>"};
-
-struct ProfRec { int kc; hipEvent_t e0, e1; double flops; };
 struct Prof {
     std::mutex mu;
     bool on = false;
@@ -74,55 +36,45 @@ struct Prof {
     long long n[KC_COUNT] = {0};
     double flops[KC_COUNT] = {0};
 } g_prof;
-
-struct ProfScope {
-    bool active = false;
-    ProfRec rec{};
-    hipStream_t st;
-    ProfScope(int kc, double flops, hipStream_t s) : st(s) {
-#ifdef WN_STAMPS
-        wn::g_debug_kc = kc;
-#endif
-        std::lock_guard<std::mutex> lk(g_prof.mu);
-        if (!g_prof.on) return;
-        auto get = [&]() {
-            hipEvent_t e;
-            if (!g_prof.pool.empty()) { e = g_prof.pool.back(); g_prof.pool.pop_back(); return e; }
-            if (hipEventCreate(&e) != hipSuccess) return (hipEvent_t) nullptr;
-            return e;
-        };
-        rec.kc = kc; rec.flops = flops; rec.e0 = get(); rec.e1 = get();
-        if (!rec.e0 || !rec.e1) return;
-        active = hipEventRecord(rec.e0, st) == hipSuccess;
-    }
-    ~ProfScope() {
-        if (!active) return;
-        (void)hipEventRecord(rec.e1, st);
-        std::lock_guard<std::mutex> lk(g_prof.mu);
-        g_prof.pending.push_back(rec);
-    }
-};
-
 }  // namespace
+
 namespace wn {
-struct ProfScopeShared {   // the same scope for wn_half_api.hip / wn_embed.hip
-    void* impl;
-    ProfScopeShared(int kc, double flops, hipStream_t st);
-    ~ProfScopeShared();
-};
-ProfScopeShared::ProfScopeShared(int kc, double flops, hipStream_t st) : impl(new ProfScope(kc, flops, st)) {}
-ProfScopeShared::~ProfScopeShared() { delete static_cast<ProfScope*>(impl); }
-}  // namespace wn
-namespace {
-// ------------------------------------------------------------------------------------------
-// geometry
-// ------------------------------------------------------------------------------------------
-int tap_offsets(int k, int d, int causal, int* off) {
-    const int p = causal ? (k - 1) * d : wn_autopad(k, d);
-    for (int j = 0; j < k; ++j) off[j] = j * d - p;
-    return 0;
+int hip_fail(hipError_t e, const char* what) {
+    g_hip_err = std::string(what) + ": " + hipGetErrorString(e);
+    return WN_ERR_HIP;
 }
 
+ProfScope::ProfScope(int kc, double flops, hipStream_t s) : st(s) {
+#ifdef WN_STAMPS
+    wn::g_debug_kc = kc;
+#endif
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    if (!g_prof.on) return;
+    auto get = [&]() {
+        hipEvent_t e;
+        if (!g_prof.pool.empty()) { e = g_prof.pool.back(); g_prof.pool.pop_back(); return e; }
+        if (hipEventCreate(&e) != hipSuccess) return (hipEvent_t) nullptr;
+        return e;
+    };
+    rec.kc = kc; rec.flops = flops; rec.e0 = get(); rec.e1 = get();
+    if (!rec.e0 || !rec.e1) return;
+    active = hipEventRecord(rec.e0, st) == hipSuccess;
+}
+ProfScope::~ProfScope() {
+    if (!active) return;
+    (void)hipEventRecord(rec.e1, st);
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    g_prof.pending.push_back(rec);
+}
+}  // namespace wn
+
+namespace {
+inline int tiles32(int c) { return cdiv(c, 32); }
+inline int pick_mt(int ntiles) { return ntiles > 2 ? 4 : (ntiles == 2 ? 2 : 1); }
+
+// ------------------------------------------------------------------------------------------
+// shape checks
+// ------------------------------------------------------------------------------------------
 int check_layout(int B, int L, int ld, int halo, int max_abs_off) {
     if (B <= 0 || L <= 0) return WN_ERR_BAD_SHAPE;
     if (halo < 0 || (halo & 3) || (ld & 3)) return WN_ERR_BAD_SHAPE;
@@ -135,15 +87,16 @@ int check_layout(int B, int L, int ld, int halo, int max_abs_off) {
 
 int check_block(const wn_block_shape* s, int* off) {
     if (!s) return WN_ERR_NULL;
-    if (s->in_channels <= 0 || s->out_channels <= 0 || s->skip_rows <= 0 || s->dilation <= 0) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width < 1) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width > WN_MAX_TAPS) return WN_ERR_UNSUPPORTED;
-    if (s->in_channels > WN_MAX_CHANNELS || s->out_channels > WN_MAX_CHANNELS || s->skip_rows > WN_MAX_CHANNELS)
-        return WN_ERR_UNSUPPORTED;
-    tap_offsets(s->kernel_width, s->dilation, s->causal, off);
     int mx = 0;
-    for (int j = 0; j < s->kernel_width; ++j) mx = std::max(mx, std::abs(off[j]));
-    return check_layout(s->batch, s->length, s->ld, s->halo, mx);
+    const int rc = check_taps(s->in_channels, s->out_channels, s->skip_rows, s->kernel_width, s->dilation, s->causal, off, &mx);
+    return rc != WN_OK ? rc : check_layout(s->batch, s->length, s->ld, s->halo, mx);
+}
+
+int check_conv(const wn_conv_shape* s, int* off) {
+    if (!s) return WN_ERR_NULL;
+    int mx = 0;
+    const int rc = check_taps(s->in_channels, s->out_channels, 1, s->kernel_width, s->dilation, s->causal, off, &mx);
+    return rc != WN_OK ? rc : check_layout(s->batch, s->length, s->ld, s->halo, mx);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -344,7 +297,8 @@ int wn_autopad(int k, int d) {
 int wn_tap_offsets(int k, int d, int causal, int* off) {
     if (!off) return WN_ERR_NULL;
     if (k < 1 || d < 1) return WN_ERR_BAD_SHAPE;
-    return tap_offsets(k, d, causal, off);
+    tap_offsets(k, d, causal, off);
+    return WN_OK;
 }
 
 int wn_series_layout(int length, int max_abs_offset, int* ld, int* halo) {
@@ -749,16 +703,6 @@ int wn_block_backward_weights(const wn_block_shape* s, const float* x, const flo
 // stand-alone dilated conv
 // ------------------------------------------------------------------------------------------
 namespace {
-int check_conv(const wn_conv_shape* s, int* off) {
-    if (!s) return WN_ERR_NULL;
-    if (s->in_channels <= 0 || s->out_channels <= 0 || s->dilation <= 0 || s->kernel_width < 1) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width > WN_MAX_TAPS) return WN_ERR_UNSUPPORTED;
-    if (s->in_channels > WN_MAX_CHANNELS || s->out_channels > WN_MAX_CHANNELS) return WN_ERR_UNSUPPORTED;
-    tap_offsets(s->kernel_width, s->dilation, s->causal, off);
-    int mx = 0;
-    for (int j = 0; j < s->kernel_width; ++j) mx = std::max(mx, std::abs(off[j]));
-    return check_layout(s->batch, s->length, s->ld, s->halo, mx);
-}
 struct ConvPlan { GemmPlan cf, cb; size_t off_cf = 0, off_cb = 0, total = 0; };
 ConvPlan plan_conv(const wn_conv_shape* s) {
     ConvPlan p;

@@ -19,6 +19,7 @@
 // No value of a plan row or of a length is used as an index before it is checked: a row that would read or write outside its
 // tensors is counted in *bad and gathers zeros / stitches nothing.  No LDS, no scratch, no loops with a data-dependent bound.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -98,8 +99,6 @@ __global__ __launch_bounds__(kChThreads) void chunk_stitch_kernel(const float* _
         y[(long long)n * stride_n + (long long)c * stride_c + (long long)(u_lo + i) * stride_t];
 }
 
-int hip_fail_shared(hipError_t e, const char* what);
-
 }  // namespace wn
 using namespace wn;
 
@@ -119,8 +118,7 @@ int wn_chunk_gather(const void* signal, int signal_is_int16, int batch, int ld, 
     else
         hipLaunchKernelGGL(chunk_gather_kernel<float>, grid, dim3(kChThreads), 0, (hipStream_t)stream,
                            reinterpret_cast<const float*>(signal), batch, ld, signal_lengths, scale, shift, plan, chunk, out, bad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "chunk_gather");
+    WN_HIP(hipGetLastError(), "chunk_gather");
     return WN_OK;
 }
 
@@ -135,7 +133,6 @@ int wn_chunk_stitch(const float* y, long long stride_n, long long stride_c, long
     const dim3 grid((unsigned)((y_frames + kChThreads - 1) / kChThreads), (unsigned)classes, (unsigned)n_chunks);
     hipLaunchKernelGGL(chunk_stitch_kernel, grid, dim3(kChThreads), 0, (hipStream_t)stream, y, stride_n, stride_c, stride_t, y_frames,
                        plan, batch, out, out_stride_b, out_stride_c, out_frames, frame_lengths, bad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "chunk_stitch");
+    WN_HIP(hipGetLastError(), "chunk_stitch");
     return WN_OK;
 }

@@ -17,6 +17,7 @@
 // the gradient at 4098 frames, tools/ctc_bench.py).  The passes are latency-bound chains (T steps), not roofline work:
 // measured next to torch's own ctc_loss in profiles/.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -272,12 +273,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const CtcArgs a, int step
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-struct ProfScopeShared { void* impl; ProfScopeShared(int kc, double flops, hipStream_t st); ~ProfScopeShared(); };
-}
 using namespace wn;
-static const int KC_CTC = 19;   // index into wn_api.hip's kernel-class table
 
 static int check_ctc(int batch, int classes, int length, int max_label_len, int blank) {
     if (batch <= 0 || classes <= 1 || length <= 0 || max_label_len <= 0) return WN_ERR_BAD_SHAPE;
@@ -313,25 +309,22 @@ int wn_ctc_loss(const float* logits, const long long* labels, const long long* l
     a.nll = reinterpret_cast<double*>(a.beta + rows * Sp);
     a.nll_out = nll; a.dx = dlogits; a.bad = bad_labels;
     a.B = batch; a.C = classes; a.T = length; a.Lmax = max_label_len; a.Sp = Sp; a.blank = blank;
-    ProfScopeShared prof(KC_CTC, 0.0, st);
+    ProfScope prof(KC_CTC, 0.0, st);
     hipLaunchKernelGGL(ctc_lse_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, w, batch, classes, length);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_lse");
+    WN_HIP(hipGetLastError(), "ctc_lse");
     const size_t pass_lds = (size_t)(2 * (Sp + 2) + classes * kCtcChunk) * 8 + (size_t)(2 * (Sp + 2)) * 4 + 16;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_pass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pass_lds);
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_pass attribute");
+    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_pass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pass_lds),
+           "ctc_pass attribute");
     hipLaunchKernelGGL(ctc_pass_kernel, dim3(batch, dlogits ? 2 : 1), dim3(kCtcThreads), pass_lds, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_pass");
+    WN_HIP(hipGetLastError(), "ctc_pass");
     if (dlogits) {
         const int steps_per_wave = 4;
         const size_t grad_lds = (size_t)4 * 64 * classes * 8;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_lds);
-        if (e != hipSuccess) return hip_fail_shared(e, "ctc_grad attribute");
+        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_lds),
+               "ctc_grad attribute");
         hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)((length + 4 * steps_per_wave - 1) / (4 * steps_per_wave)), batch), dim3(256),
                            grad_lds, st, a, steps_per_wave);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail_shared(e, "ctc_grad");
+        WN_HIP(hipGetLastError(), "ctc_grad");
     }
     return WN_OK;
 }

@@ -22,6 +22,7 @@
 // keeps the smaller of the two keys and that contributor's backpointer.  Keys are unique, so the selection is a total order.
 // The one deviation from exact prefix merging: two different prefixes of equal length whose 64-bit hashes collide.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -351,9 +352,6 @@ __global__ __launch_bounds__(64) void ctc_beam_walk_kernel(const DecodeArgs a) {
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-}
 using namespace wn;
 
 static int check_decode(int batch, int classes, int length) {
@@ -392,8 +390,7 @@ int wn_ctc_greedy_decode(const float* x, long long sb, long long sc, long long s
     a.B = batch; a.C = classes; a.T = length; a.W = 1; a.blank = blank;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ctc_greedy_kernel, dim3(batch), dim3(kDecThreads), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_greedy");
+    WN_HIP(hipGetLastError(), "ctc_greedy");
     return WN_OK;
 }
 
@@ -415,14 +412,11 @@ int wn_ctc_beam_decode(const float* x, long long sb, long long sc, long long st,
     a.B = batch; a.C = classes; a.T = length; a.W = beam_width; a.blank = blank; a.kind = input_kind;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = beam_lds_bytes(beam_width, classes, nullptr, nullptr);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_beam attribute");
+    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+           "ctc_beam attribute");
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(kDecThreads), lds, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_beam");
+    WN_HIP(hipGetLastError(), "ctc_beam");
     hipLaunchKernelGGL(ctc_beam_walk_kernel, dim3(beam_width, batch), dim3(64), 0, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "ctc_beam_walk");
+    WN_HIP(hipGetLastError(), "ctc_beam_walk");
     return WN_OK;
 }

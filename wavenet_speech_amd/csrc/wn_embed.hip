@@ -8,6 +8,7 @@
 // Both are HBM-bound byte work (dy / y are read / written once; the weight table is 2 KB per output channel and stays
 // in L1/LDS), so no MFMA here: time-coalesced 16-byte accesses and a deterministic reduction -- no float atomics.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -76,12 +77,7 @@ __global__ __launch_bounds__(256) void embed_forward_kernel(const long long* __r
 // slower alternative.  The forward pass and the state saved for backward never hold a one-hot.
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-struct ProfScopeShared { void* impl; ProfScopeShared(int kc, double flops, hipStream_t st); ~ProfScopeShared(); };
-}
 using namespace wn;
-static const int KC_EMBED = 17;   // index into wn_api.hip's kernel-class table
 
 static int check_embed(int batch, int length, int classes, int out_channels, int k) {
     if (batch <= 0 || length <= 0 || classes <= 0 || out_channels <= 0 || k < 1) return WN_ERR_BAD_SHAPE;
@@ -98,10 +94,9 @@ int wn_embed_forward(const long long* levels, const float* weight, const float* 
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)batch * ((length + 3) / 4);
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((out_channels + kEmbCo - 1) / kEmbCo));
-    ProfScopeShared prof(KC_EMBED, 0.0, st);
+    ProfScope prof(KC_EMBED, 0.0, st);
     hipLaunchKernelGGL(embed_forward_kernel, grid, dim3(256), 0, st, levels, weight, bias, y, batch, length, classes, out_channels,
                        kernel_width, bad_levels);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "embed_forward");
+    WN_HIP(hipGetLastError(), "embed_forward");
     return WN_OK;
 }

@@ -13,6 +13,7 @@
 
 #include "../../include/wavenet_amd.h"
 #include "wn_half.h"
+#include "wn_host.h"
 #include "wn_half_dev.h"
 
 namespace wn {
@@ -265,18 +266,11 @@ __global__ void grad_scale_kernel(unsigned* acc, float target, float* out) {
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-struct ProfScopeShared { void* impl; ProfScopeShared(int kc, double flops, hipStream_t st); ~ProfScopeShared(); };
-}
 using namespace wn;
-static const int KC_FRONT = 10;   // timed with the layout loads (hload_kernel class of wn_api.hip's table)
 
 namespace {
-inline int cp32i(int c) { return (c + 31) / 32 * 32; }
-bool halfp(int p) { return p == WN_F16X3 || p == WN_F16 || p == WN_BF16; }
 int check_feat(int precision, int batch, int length, int features, int k, int ld, int halo) {
-    if (!halfp(precision)) return WN_ERR_UNSUPPORTED;
+    if (!half_prec(precision)) return WN_ERR_UNSUPPORTED;
     if (batch <= 0 || length <= 0 || features <= 0 || k < 1) return WN_ERR_BAD_SHAPE;
     if (k > WN_MAX_TAPS || features > WN_MAX_CHANNELS) return WN_ERR_UNSUPPORTED;
     const int lout = length + k - 1;
@@ -295,17 +289,16 @@ int wn_hfeature_forward(int precision, const float* x, const float* weight, cons
     HFeatArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = x; a.w = weight; a.b = bias; a.y = (char*)y_series; a.flag = overflow_flag; a.scale = out_scale; a.slope = leaky_slope;
-    a.B = batch; a.L = length; a.Lout = length + kernel_width - 1; a.F = features; a.G = cp32i(features) / 8; a.k = kernel_width;
+    a.B = batch; a.L = length; a.Lout = length + kernel_width - 1; a.F = features; a.G = cp32(features) / 8; a.k = kernel_width;
     a.ld = ld; a.halo = halo;
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)a.B * a.G * a.Lout;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     if (precision == WN_F16X3) hipLaunchKernelGGL((hfeature_fwd_kernel<2, false>), grid, block, 0, st, a);
     else if (precision == WN_BF16) hipLaunchKernelGGL((hfeature_fwd_kernel<1, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((hfeature_fwd_kernel<1, false>), grid, block, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "hfeature_fwd");
+    WN_HIP(hipGetLastError(), "hfeature_fwd");
     return WN_OK;
 }
 
@@ -313,7 +306,7 @@ size_t wn_hfeature_wgrad_workspace_bytes(int batch, int length, int features, in
     if (batch <= 0 || length <= 0 || features <= 0 || kernel_width < 1 || kernel_width > WN_MAX_TAPS) return 0;
     const long long npos = (long long)batch * (length + kernel_width - 1);
     const long long nslab = (npos + kFeatSlab - 1) / kFeatSlab;
-    return (size_t)nslab * (cp32i(features) / 8) * 8 * (kernel_width + 1) * sizeof(float);
+    return (size_t)nslab * (cp32(features) / 8) * 8 * (kernel_width + 1) * sizeof(float);
 }
 
 int wn_hfeature_backward_weights(int precision, const float* x, const void* dy_series, float dy_scale, float* dweight, float* dbias,
@@ -327,29 +320,27 @@ int wn_hfeature_backward_weights(int precision, const float* x, const void* dy_s
     HFeatWgradArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = x; a.dy = (const char*)dy_series; a.partial = (float*)workspace;
-    a.B = batch; a.L = length; a.Lout = length + kernel_width - 1; a.G = cp32i(features) / 8; a.k = kernel_width; a.ld = ld; a.halo = halo;
+    a.B = batch; a.L = length; a.Lout = length + kernel_width - 1; a.G = cp32(features) / 8; a.k = kernel_width; a.ld = ld; a.halo = halo;
     const long long npos = (long long)a.B * a.Lout;
     a.nslab = (int)((npos + kFeatSlab - 1) / kFeatSlab);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)a.nslab, (unsigned)a.G), block(256);
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     if (precision == WN_F16X3) hipLaunchKernelGGL((hfeature_wgrad_kernel<2, false>), grid, block, 0, st, a);
     else if (precision == WN_BF16) hipLaunchKernelGGL((hfeature_wgrad_kernel<1, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((hfeature_wgrad_kernel<1, false>), grid, block, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "hfeature_wgrad");
+    WN_HIP(hipGetLastError(), "hfeature_wgrad");
     const int n = features * (kernel_width + 1);
     hipLaunchKernelGGL(hfeature_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)workspace, dweight,
                        dbias, dyn_inv_scale, 1.0f / dy_scale, a.nslab, a.G, features, kernel_width);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "hfeature_wgrad_reduce");
+    WN_HIP(hipGetLastError(), "hfeature_wgrad_reduce");
     return WN_OK;
 }
 
 // ---- pooled loads ---------------------------------------------------------------------------------------------------------------
 int wn_hseries_load_pooled(int precision, const float* dense, void* series, int batch, int channels, int length, int pool, int ld, int halo,
                            float scale, const float* dyn_scale, unsigned* overflow_flag, wn_stream_t stream) {
-    if (!halfp(precision)) return WN_ERR_UNSUPPORTED;
+    if (!half_prec(precision)) return WN_ERR_UNSUPPORTED;
     if (!dense || !series) return WN_ERR_NULL;
     if (batch <= 0 || channels <= 0 || length <= 0 || pool < 1 || length / pool < 1 || channels > WN_MAX_CHANNELS) return WN_ERR_BAD_SHAPE;
     const int lp = length / pool;
@@ -357,16 +348,15 @@ int wn_hseries_load_pooled(int precision, const float* dense, void* series, int 
     PoolArgs a;
     std::memset(&a, 0, sizeof(a));
     a.src = dense; a.dst = (char*)series; a.flag = overflow_flag; a.dyn = dyn_scale; a.scale = scale;
-    a.B = batch; a.C = channels; a.L = length; a.Lp = lp; a.pool = pool; a.G = cp32i(channels) / 8; a.ld = ld; a.halo = halo;
+    a.B = batch; a.C = channels; a.L = length; a.Lp = lp; a.pool = pool; a.G = cp32(channels) / 8; a.ld = ld; a.halo = halo;
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)a.B * a.G * a.Lp;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     if (precision == WN_F16X3) hipLaunchKernelGGL((hpool_load_kernel<2, false>), grid, block, 0, st, a);
     else if (precision == WN_BF16) hipLaunchKernelGGL((hpool_load_kernel<1, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((hpool_load_kernel<1, false>), grid, block, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "hpool_load");
+    WN_HIP(hipGetLastError(), "hpool_load");
     return WN_OK;
 }
 
@@ -382,10 +372,9 @@ int wn_series_load_pooled(const float* dense, float* series, int batch, int chan
     a.B = batch; a.C = channels; a.L = length; a.Lp = lp; a.pool = pool; a.Cp = (channels + 7) / 8 * 8; a.ld = ld; a.halo = halo;
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)a.B * a.C * a.Lp;
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     hipLaunchKernelGGL(pool_load_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "pool_load");
+    WN_HIP(hipGetLastError(), "pool_load");
     return WN_OK;
 }
 
@@ -398,10 +387,9 @@ int wn_pool_backward(const float* dpooled, float* dx, int batch, int channels, i
     a.B = batch; a.C = channels; a.L = length; a.Lp = length / pool; a.pool = pool;
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)a.B * a.C * a.L;
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     hipLaunchKernelGGL(pool_unload_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "pool_unload");
+    WN_HIP(hipGetLastError(), "pool_unload");
     return WN_OK;
 }
 
@@ -411,10 +399,9 @@ int wn_grad_scale(const float* x, long long count, float target, float* scale_an
     hipStream_t st = (hipStream_t)stream;
     const long long n4 = count / 4;
     const unsigned grid = (unsigned)(n4 / 256 < 1 ? 1 : (n4 / 256 > 2048 ? 2048 : n4 / 256));
-    ProfScopeShared prof(KC_FRONT, 0.0, st);
+    ProfScope prof(KC_FRONT, 0.0, st);
     hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(256), 0, st, x, count, accumulator);
     hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, st, accumulator, target, scale_and_inverse);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "grad_scale");
+    WN_HIP(hipGetLastError(), "grad_scale");
     return WN_OK;
 }

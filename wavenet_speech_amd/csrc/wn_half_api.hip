@@ -16,27 +16,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/wavenet_amd.h"
 #include "wn_half.h"
+#include "wn_host.h"
 
 using namespace wn;
 
-namespace wn { int hip_fail_shared(hipError_t e, const char* what); }
-
 namespace {
-
-#define WN_HIP(call, what)                                           \
-    do {                                                             \
-        hipError_t e__ = (call);                                     \
-        if (e__ != hipSuccess) return wn::hip_fail_shared(e__, what); \
-    } while (0)
-
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int cp32(int c) { return rup(c, 32); }
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-bool half_prec(int p) { return p == WN_F16X3 || p == WN_F16 || p == WN_BF16; }
 
 int check_hlayout(int B, int L, int ld, int halo, int max_abs_off) {
     if (B <= 0 || L <= 0) return WN_ERR_BAD_SHAPE;
@@ -48,15 +33,9 @@ int check_hlayout(int B, int L, int ld, int halo, int max_abs_off) {
 int check_hblock(const wn_block_shape* s, int prec, int* off) {
     if (!s) return WN_ERR_NULL;
     if (!half_prec(prec)) return WN_ERR_UNSUPPORTED;
-    if (s->in_channels <= 0 || s->out_channels <= 0 || s->skip_rows <= 0 || s->dilation <= 0) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width < 1) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width > WN_MAX_TAPS) return WN_ERR_UNSUPPORTED;
-    if (s->in_channels > WN_MAX_CHANNELS || s->out_channels > WN_MAX_CHANNELS || s->skip_rows > WN_MAX_CHANNELS)
-        return WN_ERR_UNSUPPORTED;
-    wn_tap_offsets(s->kernel_width, s->dilation, s->causal, off);
     int mx = 0;
-    for (int j = 0; j < s->kernel_width; ++j) mx = std::max(mx, std::abs(off[j]));
-    return check_hlayout(s->batch, s->length, s->ld, s->halo, mx);
+    const int rc = check_taps(s->in_channels, s->out_channels, s->skip_rows, s->kernel_width, s->dilation, s->causal, off, &mx);
+    return rc != WN_OK ? rc : check_hlayout(s->batch, s->length, s->ld, s->halo, mx);
 }
 
 // a half series as the kernels address it
@@ -135,7 +114,9 @@ struct HFusedPlan {
     int st_gate = 0, st_res = 0, st_skip = 0;     // ring stages (32 channels of K x 128 rows) per gate half / res / skip phase
     size_t off_w = 0, off_bias = 0;
     int stages() const { return ngh * st_gate + st_res + st_skip; }
-    size_t bytes() const { return on ? align256((size_t)stages() * kFStageBytes) + align256(4 * kFRows * sizeof(float)) + 1024 : 0; }   // + dump line
+    static size_t bias_bytes() { return align256(4 * kFRows * sizeof(float)); }
+    size_t off_dump() const { return off_bias + bias_bytes(); }   // the 1 KiB line that masked store lanes write to
+    size_t bytes() const { return on ? align256((size_t)stages() * kFStageBytes) + bias_bytes() + 1024 : 0; }
 };
 
 bool fused_forward_enabled() {
@@ -154,6 +135,7 @@ struct HBlockPlan {
     HFusedPlan fu;
     bool col = false;               // dz and dx run as hcol_kernel (KA / KB keep hgemm_kernel's 128-row packing for it)
     size_t off_fa = 0, off_fr = 0, off_fs = 0, off_ka = 0, off_kb = 0, off_kap = 0, total = 0;
+    char* dump(const void* packed) const { return (char*)packed + fu.off_dump(); }
 };
 
 HBlockPlan plan_hblock(const wn_block_shape* s, int prec) {
@@ -274,19 +256,7 @@ inline void set_hseg(HGemmArgs& a, int i, const HView& v, int off, int nks) {
     a.seg[i].base = v.base; a.seg[i].ustride = v.ustride; a.seg[i].pstride = v.pstride; a.seg[i].off = off; a.seg[i].nks = nks;
 }
 
-// profiling classes shared with wn_api.hip (same table, same order)
-enum { KC_PACK = 0, KC_GATE_GEMM, KC_OUT_GEMM, KC_DZ_GEMM, KC_DX_GEMM, KC_WGRAD, KC_WGRAD_REDUCE, KC_CONV_FWD, KC_CONV_BWD_DATA,
-       KC_SKIP_GEMM, KC_HLOAD, KC_HGATE, KC_HRES, KC_HDZ, KC_HDX, KC_HSKIP, KC_HWGRAD, KC_EMBED, KC_SYNTH, KC_CTC, KC_HFUSED, KC_HCONV_FWD, KC_HCONV_BWD_DATA, KC_HCOL_DZ, KC_HCOL_DX, KC_HCOL_DXDZ, KC_HCOL_SKIP };
-
 }  // namespace
-
-namespace wn {
-struct ProfScopeShared {   // implemented in wn_api.hip (HIP events on the launch stream when profiling is on)
-    void* impl;
-    ProfScopeShared(int kc, double flops, hipStream_t st);
-    ~ProfScopeShared();
-};
-}  // namespace wn
 
 // ==========================================================================================================================
 // C ABI
@@ -318,7 +288,7 @@ int wn_hseries_load(int precision, const float* dense, void* series, int batch, 
     a.src = dense; a.dst = (char*)series; a.dyn_scale = dyn_scale; a.flag = overflow_flag; a.scale = scale;
     a.B = batch; a.C = channels; a.L = length; a.G = cp32(channels) / 8; a.ld = ld; a.halo = halo;
     a.planes = hp_planes(precision); a.bf16 = precision == WN_BF16;
-    wn::ProfScopeShared prof(KC_HLOAD, 0.0, (hipStream_t)stream);
+    ProfScope prof(KC_HLOAD, 0.0, (hipStream_t)stream);
     WN_HIP(launch_hload(a, (hipStream_t)stream), "hload");
     return WN_OK;
 }
@@ -470,7 +440,7 @@ int wn_hblock_pack_checked(const wn_block_shape* s, int precision, const wn_bloc
     int rc = fill_hblock_jobs(s, precision, p, packed, jobs);
     if (rc != WN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    wn::ProfScopeShared prof(KC_PACK, 0.0, st);
+    ProfScope prof(KC_PACK, 0.0, st);
     for (HPackArgs& a : jobs) {
         a.flag = overflow_flag;
         WN_HIP(launch_hpack(a, st), "hpack(block)");
@@ -515,7 +485,7 @@ int wn_hblock_forward(const wn_block_shape* s, int precision, const void* packed
         if (r_out) fa.r = dst_of(view(r_out, Co, s->ld, P));
         fa.skip = skip_dense; fa.skip_rows = Ms; fa.skip_accum = skip_accumulate ? 1 : 0;
         fa.flag = overflow_flag;
-        fa.dump = (char*)packed + f.off_bias + align256(4 * kFRows * sizeof(float));
+        fa.dump = bp.dump(packed);
         for (int j = 0; j < k; ++j)
             for (int ks = 0; ks < f.nci16; ++ks) fa.xunit[j * f.nci16 + ks] = 2 * ks * s->ld + off[j];
         fa.nkg = f.nkg; fa.nci16 = f.nci16; fa.nzt = f.nzt; fa.co = Co;
@@ -525,7 +495,7 @@ int wn_hblock_forward(const wn_block_shape* s, int precision, const void* packed
         fa.B = s->batch; fa.L = s->length; fa.ld = s->ld; fa.halo = s->halo;
         fa.units_per_row = cdiv(s->length, 32); fa.nunit = s->batch * fa.units_per_row;
         fa.nstage = f.ngh * f.st_gate + (r_out ? f.st_res : 0) + (skip_dense ? f.st_skip : 0);
-        wn::ProfScopeShared prof(KC_HFUSED, 2.0 * ((2.0 * Co) * (double)(k * Ci) + (r_out ? Co * (double)(Co + Ci) : 0.0) +
+        ProfScope prof(KC_HFUSED, 2.0 * ((2.0 * Co) * (double)(k * Ci) + (r_out ? Co * (double)(Co + Ci) : 0.0) +
                                                  (skip_dense ? Ms * (double)Co : 0.0)) * BL, st);
         WN_HIP(launch_hfused_fwd(precision, fa, st), "hfused_fwd");
         return WN_OK;
@@ -539,7 +509,7 @@ int wn_hblock_forward(const wn_block_shape* s, int precision, const void* packed
         if (sg) a.sg = dst_of(view(sg, Co, s->ld, P));
         a.gate_rows = Co;
         a.flag = overflow_flag;
-        wn::ProfScopeShared prof(KC_HGATE, 2.0 * (2.0 * Co) * (double)(k * Ci) * BL, st);
+        ProfScope prof(KC_HGATE, 2.0 * (2.0 * Co) * (double)(k * Ci) * BL, st);
         WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_GATE, a, st), "hgemm<gate>");
     }
     if (r_out) {
@@ -550,7 +520,7 @@ int wn_hblock_forward(const wn_block_shape* s, int precision, const void* packed
         a.dst[0] = dst_of(view(r_out, Co, s->ld, P));
         a.oscale = kResidualScale / kWeightScale;
         a.flag = overflow_flag;
-        wn::ProfScopeShared prof(KC_HRES, 2.0 * Co * (double)(Co + Ci) * BL, st);
+        ProfScope prof(KC_HRES, 2.0 * Co * (double)(Co + Ci) * BL, st);
         WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_STORE, a, st), "hgemm<res>");
     }
     if (skip_dense) {
@@ -558,7 +528,7 @@ int wn_hblock_forward(const wn_block_shape* s, int precision, const void* packed
         fill_hgemm(a, g, packed, bp.off_fs, s->batch, s->length, s->ld, s->halo);
         set_hseg(a, 0, vz, 0, g.seg_nks[0]);
         a.out32 = skip_dense; a.out32_rows = Ms; a.out32_accum = skip_accumulate ? 1 : 0;
-        wn::ProfScopeShared prof(KC_HSKIP, 2.0 * Ms * (double)Co * BL, st);
+        ProfScope prof(KC_HSKIP, 2.0 * Ms * (double)Co * BL, st);
         WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_F32, a, st), "hgemm<skip>");
     }
     return WN_OK;
@@ -584,8 +554,7 @@ void col_args_common(HColArgs& c, const HGemmArgs& a, int out_rows, char* dump, 
     c.nunit = (int)(((long long)B * L + 31) / 32);
 }
 void col_args(HColArgs& c, const HGemmArgs& a, const HBlockPlan& bp, const void* packed, const wn_block_shape* s) {
-    col_args_common(c, a, s->out_channels, (char*)packed + bp.fu.off_bias + align256(4 * kFRows * sizeof(float)), s->batch, s->length,
-                    s->ld, s->halo);
+    col_args_common(c, a, s->out_channels, bp.dump(packed), s->batch, s->length, s->ld, s->halo);
 }
 int hblock_backward_data_impl(const wn_block_shape* s, int precision, const void* packed, const void* dr, const void* dskip,
                               const void* z, const void* sg, void* da, void* dg, void* dx, float* dx_dense,
@@ -617,10 +586,10 @@ int hblock_backward_data_impl(const wn_block_shape* s, int precision, const void
             HColArgs c;
             col_args(c, a, bp, packed, s);
             c.z = a.z; c.sg = a.sg; c.da = a.da; c.dg = a.dg;
-            wn::ProfScopeShared prof(KC_HCOL_DZ, 2.0 * Co * (double)(Ms + (dr ? Co : 0)) * BL, st);
+            ProfScope prof(KC_HCOL_DZ, 2.0 * Co * (double)(Ms + (dr ? Co : 0)) * BL, st);
             WN_HIP(launch_hcol(precision, HEPI_DGATE, c, st), "hcol<dz>");
         } else {
-            wn::ProfScopeShared prof(KC_HDZ, 2.0 * Co * (double)(Ms + (dr ? Co : 0)) * BL, st);
+            ProfScope prof(KC_HDZ, 2.0 * Co * (double)(Ms + (dr ? Co : 0)) * BL, st);
             WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_DGATE, a, st), "hgemm<dz>");
         }
     }
@@ -636,7 +605,7 @@ int hblock_backward_data_impl(const wn_block_shape* s, int precision, const void
         for (int i = 0; i < a.nslab; ++i) a.slab[i].nseg = 2 * k + (dr ? 1 : 0);
         a.flag = overflow_flag;
         const bool col_dx = dx && bp.col;
-        wn::ProfScopeShared prof(col_dx ? KC_HCOL_DX : KC_HDX, 2.0 * Ci * (double)(2 * k * Co + (dr ? Co : 0)) * BL, st);
+        ProfScope prof(col_dx ? KC_HCOL_DX : KC_HDX, 2.0 * Ci * (double)(2 * k * Co + (dr ? Co : 0)) * BL, st);
         if (dx && dx_mask && bp.col) {
             HColArgs c;
             col_args(c, a, bp, packed, s);
@@ -743,12 +712,12 @@ int wn_hblock_backward_pair(const wn_block_shape* upper, const void* packed_uppe
     c.z = dst_of(view(z_lower, Col, ld, P)); c.sg = dst_of(view(sg_lower, Col, ld, P));
     c.da = dst_of(view(da_lower, Col, ld, P)); c.dg = dst_of(view(dg_lower, Col, ld, P));
     c.flag = overflow_flag;
-    c.dump = (char*)packed_upper + pu.fu.off_bias + align256(4 * kFRows * sizeof(float));
+    c.dump = pu.dump(packed_upper);
     c.oscale1 = c.oscale2 = 1.0f / kWeightScale;
     c.B = upper->batch; c.L = upper->length; c.ld = ld; c.halo = upper->halo;
     c.nunit = (int)(((long long)upper->batch * upper->length + 31) / 32);
     const double BL = (double)upper->batch * upper->length;
-    wn::ProfScopeShared prof(KC_HCOL_DXDZ, (2.0 * Ciu * (double)(2 * k * Cou + (dr_upper ? Cou : 0)) + 2.0 * Col * (double)(Ms + Col)) * BL, st);
+    ProfScope prof(KC_HCOL_DXDZ, (2.0 * Ciu * (double)(2 * k * Cou + (dr_upper ? Cou : 0)) + 2.0 * Col * (double)(Ms + Col)) * BL, st);
     WN_HIP(launch_hcol2(precision, c, st), "hcol2<dx+dz>");
     return WN_OK;
 }
@@ -809,7 +778,7 @@ int wn_hskipsum_pack(const wn_skipsum_shape* s, int precision, const float* cons
     for (int l = 0; l < s->nblocks; ++l) if (!w_skip[l]) return WN_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
     const HPlan g = plan_hskipsum(s, precision);
-    wn::ProfScopeShared prof(KC_PACK, 0.0, st);
+    ProfScope prof(KC_PACK, 0.0, st);
     HPackArgs a;
     fill_hpack(a, g, packed, 0, precision);
     for (int l = 0; l < s->nblocks; ++l) a.set[0].seg[l] = hsrc(w_skip[l], s->skip_rows, s->channels[l], s->channels[l], 1, kWeightScale);
@@ -819,6 +788,17 @@ int wn_hskipsum_pack(const wn_skipsum_shape* s, int precision, const float* cons
     return WN_OK;
 }
 
+namespace {
+// the skips_sum GEMM up to its destination: every block's z is one K segment.  Returns the launch's flop count.
+double hskipsum_args(HGemmArgs& a, const wn_skipsum_shape* s, int precision, const HPlan& g, const void* packed, const void* const* z) {
+    const int P = hp_planes(precision);
+    fill_hgemm(a, g, packed, 0, s->batch, s->length, s->ld, s->halo);
+    double ksum = 0;
+    for (int l = 0; l < s->nblocks; ++l) { set_hseg(a, l, view(z[l], s->channels[l], s->ld, P), 0, g.seg_nks[l]); ksum += s->channels[l]; }
+    return 2.0 * s->skip_rows * ksum * (double)s->batch * s->length;
+}
+}  // namespace
+
 int wn_hskipsum_forward(const wn_skipsum_shape* s, int precision, const void* packed, const void* const* z, float* skip_dense,
                         int accumulate, wn_stream_t stream) {
     int rc = check_hskipsum(s, precision);
@@ -827,13 +807,10 @@ int wn_hskipsum_forward(const wn_skipsum_shape* s, int precision, const void* pa
     for (int l = 0; l < s->nblocks; ++l) if (!z[l]) return WN_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
     const HPlan g = plan_hskipsum(s, precision);
-    const int P = hp_planes(precision);
     HGemmArgs a;
-    fill_hgemm(a, g, packed, 0, s->batch, s->length, s->ld, s->halo);
-    double ksum = 0;
-    for (int l = 0; l < s->nblocks; ++l) { set_hseg(a, l, view(z[l], s->channels[l], s->ld, P), 0, g.seg_nks[l]); ksum += s->channels[l]; }
+    const double flops = hskipsum_args(a, s, precision, g, packed, z);
     a.out32 = skip_dense; a.out32_rows = s->skip_rows; a.out32_accum = accumulate ? 1 : 0;
-    wn::ProfScopeShared prof(KC_HSKIP, 2.0 * s->skip_rows * ksum * (double)s->batch * s->length, st);
+    ProfScope prof(KC_HSKIP, flops, st);
     WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_F32, a, st), "hgemm<skipsum>");
     return WN_OK;
 }
@@ -849,22 +826,19 @@ int wn_hskipsum_forward_series(const wn_skipsum_shape* s, int precision, const v
     for (int l = 0; l < s->nblocks; ++l) if (!z[l]) return WN_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
     const HPlan g = plan_hskipsum(s, precision);
-    const int P = hp_planes(precision);
     HGemmArgs a;
-    fill_hgemm(a, g, packed, 0, s->batch, s->length, s->ld, s->halo);
-    double ksum = 0;
-    for (int l = 0; l < s->nblocks; ++l) { set_hseg(a, l, view(z[l], s->channels[l], s->ld, P), 0, g.seg_nks[l]); ksum += s->channels[l]; }
-    a.dst[0] = dst_of(view(out_series, s->skip_rows, s->ld, P));
+    const double flops = hskipsum_args(a, s, precision, g, packed, z);
+    a.dst[0] = dst_of(view(out_series, s->skip_rows, s->ld, hp_planes(precision)));
     a.oscale2 = out_scale; a.leaky = leaky_slope; a.flag = overflow_flag;
     if (skipsum_col(s, precision, g)) {
         HColArgs c;
         col_args_common(c, a, s->skip_rows, (char*)packed + g.bytes(), s->batch, s->length, s->ld, s->halo);
         c.dst = a.dst[0]; c.bias = a.bias; c.oscale2 = out_scale; c.leaky = leaky_slope;
-        wn::ProfScopeShared prof(KC_HCOL_SKIP, 2.0 * s->skip_rows * ksum * (double)s->batch * s->length, st);
+        ProfScope prof(KC_HCOL_SKIP, flops, st);
         WN_HIP(launch_hcol_skipsum(precision, c, st), "hcol<skipsum series>");
         return WN_OK;
     }
-    wn::ProfScopeShared prof(KC_HSKIP, 2.0 * s->skip_rows * ksum * (double)s->batch * s->length, st);
+    ProfScope prof(KC_HSKIP, flops, st);
     WN_HIP(launch_hgemm(precision, g.kernel(), HEPI_LEAKY, a, st), "hgemm<skipsum series>");
     return WN_OK;
 }
@@ -993,7 +967,7 @@ int wn_hstack_pack_run(const void* table_dev, int nblocks, int njobs, int launch
     const HPackArgs* jobs = reinterpret_cast<const HPackArgs*>(table_dev);
     const int* block0 = reinterpret_cast<const int*>((const char*)table_dev + align256((size_t)stack_jobs_upper_bound(nblocks) * sizeof(HPackArgs)));
     hipStream_t st = (hipStream_t)stream;
-    wn::ProfScopeShared prof(KC_PACK, 0.0, st);
+    ProfScope prof(KC_PACK, 0.0, st);
     WN_HIP(launch_hpack_table(jobs, block0, njobs, launch_blocks, d, st), "hpack(table)");
     return WN_OK;
 }
@@ -1053,6 +1027,13 @@ struct HWPlan {
 bool composite_wgrad(int ci, int co, int ms) {
     const char* e = getenv("WN_HWGRAD_COMPOSITE");   // read per call (tests compare both forms)
     return !(e && atoi(e) == 0) && cp32(ci) <= 128 && cp32(co) <= 128 && cp32(ms) <= 128;
+}
+
+// the destinations a block's weight gradients need: the residual path's four only when the block has a residual consumer
+int check_hgrads(const wn_block_params* g, bool has_dr) {
+    if (!g->w_tanh || !g->b_tanh || !g->w_sigmoid || !g->b_sigmoid || !g->w_skip || !g->b_skip) return WN_ERR_NULL;
+    if (has_dr && (!g->w_res || !g->b_res || !g->w_proj || !g->b_proj)) return WN_ERR_NULL;
+    return WN_OK;
 }
 
 std::vector<HPairSpec> hblock_pairs(const wn_block_shape* s, const int* off, const void* x, const void* z, const void* da,
@@ -1160,11 +1141,11 @@ int run_hwgrad(const std::vector<HPairSpec>& ps, int prec, int B, int L, int ld,
     r.npair = nd; r.nsplit = wp.nsplit; r.slab = a.slab; r.rowsum = a.rowsum;
     r.slab_floats = wp.slab_floats; r.rs_floats = wp.rs_floats; r.dyn_inv = dyn_inv;
     {
-        wn::ProfScopeShared prof(KC_HWGRAD, flops, st);
+        ProfScope prof(KC_HWGRAD, flops, st);
         WN_HIP(launch_hwgrad(prec, a, st), "hwgrad");
     }
     {
-        wn::ProfScopeShared prof(KC_WGRAD_REDUCE, 0.0, st);
+        ProfScope prof(KC_WGRAD_REDUCE, 0.0, st);
         WN_HIP(launch_wgrad_reduce(r, st), "wgrad_reduce");
     }
     return WN_OK;
@@ -1192,9 +1173,8 @@ int wn_hblock_backward_weights(const wn_block_shape* s, int precision, const voi
     int rc = check_hblock(s, precision, off);
     if (rc != WN_OK) return rc;
     if (!x || !z || !da || !dg || !dskip || !grads) return WN_ERR_NULL;
-    if (!grads->w_tanh || !grads->b_tanh || !grads->w_sigmoid || !grads->b_sigmoid || !grads->w_skip || !grads->b_skip)
-        return WN_ERR_NULL;
-    if (dr && (!grads->w_res || !grads->b_res || !grads->w_proj || !grads->b_proj)) return WN_ERR_NULL;
+    rc = check_hgrads(grads, dr != nullptr);
+    if (rc != WN_OK) return rc;
     // the 256-channel staging tiles must lie inside the operands: channel counts are padded to 32, tiles to 256
     std::vector<HPairSpec> ps = hblock_pairs(s, off, x, z, da, dg, dr, dskip, grads);
     return run_hwgrad(ps, precision, s->batch, s->length, s->ld, s->halo, dyn_inv_scale, workspace, workspace_bytes, false,
@@ -1254,8 +1234,8 @@ int wn_hblocks_backward_weights(const wn_block_shape* shapes, int nblocks, int p
             return WN_ERR_BAD_SHAPE;                            // one series geometry per launch
         const wn_block_params* g = &grads[l];
         if (!x[l] || !z[l] || !da[l] || !dg[l] || !dskip[l]) return WN_ERR_NULL;
-        if (!g->w_tanh || !g->b_tanh || !g->w_sigmoid || !g->b_sigmoid || !g->w_skip || !g->b_skip) return WN_ERR_NULL;
-        if (dr[l] && (!g->w_res || !g->b_res || !g->w_proj || !g->b_proj)) return WN_ERR_NULL;
+        rc = check_hgrads(g, dr[l] != nullptr);
+        if (rc != WN_OK) return rc;
         std::vector<HPairSpec> ps = hblock_pairs(&shapes[l], off, x[l], z[l], da[l], dg[l], dr[l], dskip[l], g);
         all.insert(all.end(), ps.begin(), ps.end());
     }
@@ -1271,12 +1251,9 @@ namespace {
 int check_hconv(const wn_conv_shape* s, int prec, int* off) {
     if (!s) return WN_ERR_NULL;
     if (!half_prec(prec)) return WN_ERR_UNSUPPORTED;
-    if (s->in_channels <= 0 || s->out_channels <= 0 || s->dilation <= 0 || s->kernel_width < 1) return WN_ERR_BAD_SHAPE;
-    if (s->kernel_width > WN_MAX_TAPS || s->in_channels > WN_MAX_CHANNELS || s->out_channels > WN_MAX_CHANNELS) return WN_ERR_UNSUPPORTED;
-    wn_tap_offsets(s->kernel_width, s->dilation, s->causal, off);
     int mx = 0;
-    for (int j = 0; j < s->kernel_width; ++j) mx = std::max(mx, std::abs(off[j]));
-    return check_hlayout(s->batch, s->length, s->ld, s->halo, mx);
+    const int rc = check_taps(s->in_channels, s->out_channels, 1, s->kernel_width, s->dilation, s->causal, off, &mx);
+    return rc != WN_OK ? rc : check_hlayout(s->batch, s->length, s->ld, s->halo, mx);
 }
 struct HConvPlan {
     HPlan f, kb; size_t off_f = 0, off_kb = 0, off_dump = 0, total = 0;
@@ -1318,7 +1295,7 @@ int wn_hconv_pack(const wn_conv_shape* s, int precision, const float* weight, co
     hipStream_t st = (hipStream_t)stream;
     const HConvPlan cp = plan_hconv(s, precision);
     const int Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
-    wn::ProfScopeShared prof(KC_PACK, 0.0, st);
+    ProfScope prof(KC_PACK, 0.0, st);
     HPackArgs a;
     {   // forward: rows = output channel, taps of x (stored as x * input_scale)
         fill_hpack(a, cp.f, packed, cp.off_f, precision);
@@ -1337,65 +1314,25 @@ int wn_hconv_pack(const wn_conv_shape* s, int precision, const float* weight, co
     return WN_OK;
 }
 
-int wn_hconv_forward(const wn_conv_shape* s, int precision, const void* packed, const void* x, float* y_dense,
-                     wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_hconv(s, precision, off);
-    if (rc != WN_OK) return rc;
-    if (!packed || !x || !y_dense) return WN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
+namespace {
+// y = conv(x) + b as dense fp32 (y_dense), or with the half series on BOTH sides (the feature layer / output block of a model in a
+// half mode stay in the layout between their convs): y_series = leaky(conv(x) + b) * out_scale  (leaky_slope = 1: no activation)
+int hconv_forward(const wn_conv_shape* s, int precision, const int* off, const void* packed, const void* x, float* y_dense,
+                  void* y_series, float out_scale, float leaky_slope, unsigned* overflow_flag, hipStream_t st) {
     const HConvPlan cp = plan_hconv(s, precision);
     const int P = hp_planes(precision), Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
     HGemmArgs a;
     fill_hgemm(a, cp.f, packed, cp.off_f, s->batch, s->length, s->ld, s->halo);
     const HView vx = view(x, Ci, s->ld, P);
     for (int j = 0; j < k; ++j) set_hseg(a, j, vx, off[j], cp.f.seg_nks[j]);
-    a.out32 = y_dense; a.out32_rows = Co; a.out32_accum = 0;
-    wn::ProfScopeShared prof(KC_HCONV_FWD, 2.0 * Co * (double)(k * Ci) * (double)s->batch * s->length, st);
-    WN_HIP(launch_hgemm(precision, cp.f.kernel(), HEPI_F32, a, st), "hgemm<conv>");
-    return WN_OK;
-}
-
-int wn_hconv_backward_data(const wn_conv_shape* s, int precision, const void* packed, const void* dy, float* dx_dense,
-                           const float* dyn_inv_scale, wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_hconv(s, precision, off);
-    if (rc != WN_OK) return rc;
-    if (!packed || !dy || !dx_dense) return WN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    const HConvPlan cp = plan_hconv(s, precision);
-    const int P = hp_planes(precision), Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
-    HGemmArgs a;
-    fill_hgemm(a, cp.kb, packed, cp.off_kb, s->batch, s->length, s->ld, s->halo);
-    a.bias = nullptr;
-    const HView vdy = view(dy, Co, s->ld, P);
-    for (int j = 0; j < k; ++j) set_hseg(a, j, vdy, -off[j], cp.kb.seg_nks[j]);
-    a.out32 = dx_dense; a.out32_rows = Ci; a.out32_accum = 0; a.dyn_inv = dyn_inv_scale;
-    wn::ProfScopeShared prof(KC_HCONV_BWD_DATA, 2.0 * Ci * (double)(k * Co) * (double)s->batch * s->length, st);
-    WN_HIP(launch_hgemm(precision, cp.kb.kernel(), HEPI_F32, a, st), "hgemm<conv dx>");
-    return WN_OK;
-}
-
-// The same convolution with the half series on BOTH sides (the feature layer / output block of a model in a half mode stay in the
-// layout between their convs): y_series = leaky(conv(x) + b) * out_scale  (leaky_slope = 1: no activation).  `packed` from
-// wn_hconv_pack with the input's scale.
-int wn_hconv_forward_series(const wn_conv_shape* s, int precision, const void* packed, const void* x, void* y_series, float out_scale,
-                            float leaky_slope, unsigned* overflow_flag, wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_hconv(s, precision, off);
-    if (rc != WN_OK) return rc;
-    if (!packed || !x || !y_series) return WN_ERR_NULL;
-    if (!(out_scale > 0.0f)) return WN_ERR_BAD_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const HConvPlan cp = plan_hconv(s, precision);
-    const int P = hp_planes(precision), Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
-    HGemmArgs a;
-    fill_hgemm(a, cp.f, packed, cp.off_f, s->batch, s->length, s->ld, s->halo);
-    const HView vx = view(x, Ci, s->ld, P);
-    for (int j = 0; j < k; ++j) set_hseg(a, j, vx, off[j], cp.f.seg_nks[j]);
+    ProfScope prof(KC_HCONV_FWD, 2.0 * Co * (double)(k * Ci) * (double)s->batch * s->length, st);
+    if (y_dense) {
+        a.out32 = y_dense; a.out32_rows = Co; a.out32_accum = 0;
+        WN_HIP(launch_hgemm(precision, cp.f.kernel(), HEPI_F32, a, st), "hgemm<conv>");
+        return WN_OK;
+    }
     a.dst[0] = dst_of(view(y_series, Co, s->ld, P));
     a.oscale2 = out_scale; a.leaky = leaky_slope; a.flag = overflow_flag;
-    wn::ProfScopeShared prof(KC_HCONV_FWD, 2.0 * Co * (double)(k * Ci) * (double)s->batch * s->length, st);
     if (cp.col && cp.f.nslab == 1 && cp.f.MT == 2 && !cp.f.k32) {
         HColArgs c;
         col_args_common(c, a, Co, (char*)packed + cp.off_dump, s->batch, s->length, s->ld, s->halo);
@@ -1407,15 +1344,12 @@ int wn_hconv_forward_series(const wn_conv_shape* s, int precision, const void* p
     return WN_OK;
 }
 
-// dx_series = (W^T dy) * leaky'(act): `act` (nullable: no activation in front of this conv) is the conv's INPUT as it was stored,
-// i.e. the activated value, whose sign is the sign of the pre-activation; gradients keep the scale dy carries
-int wn_hconv_backward_data_series(const wn_conv_shape* s, int precision, const void* packed, const void* dy, const void* act,
-                                  float leaky_slope, void* dx_series, unsigned* overflow_flag, wn_stream_t stream) {
-    int off[WN_MAX_TAPS];
-    int rc = check_hconv(s, precision, off);
-    if (rc != WN_OK) return rc;
-    if (!packed || !dy || !dx_series) return WN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
+// dx = W^T dy as dense fp32 (dx_dense, times the optional device scalar), or in the series: dx_series = (W^T dy) * leaky'(act).
+// `act` (nullable: no activation in front of this conv) is the conv's INPUT as it was stored, i.e. the activated value, whose sign
+// is the sign of the pre-activation; gradients keep the scale dy carries
+int hconv_backward_data(const wn_conv_shape* s, int precision, const int* off, const void* packed, const void* dy, float* dx_dense,
+                        const float* dyn_inv_scale, void* dx_series, const void* act, float leaky_slope, unsigned* overflow_flag,
+                        hipStream_t st) {
     const HConvPlan cp = plan_hconv(s, precision);
     const int P = hp_planes(precision), Ci = s->in_channels, Co = s->out_channels, k = s->kernel_width;
     HGemmArgs a;
@@ -1423,10 +1357,15 @@ int wn_hconv_backward_data_series(const wn_conv_shape* s, int precision, const v
     a.bias = nullptr;
     const HView vdy = view(dy, Co, s->ld, P);
     for (int j = 0; j < k; ++j) set_hseg(a, j, vdy, -off[j], cp.kb.seg_nks[j]);
+    ProfScope prof(KC_HCONV_BWD_DATA, 2.0 * Ci * (double)(k * Co) * (double)s->batch * s->length, st);
+    if (dx_dense) {
+        a.out32 = dx_dense; a.out32_rows = Ci; a.out32_accum = 0; a.dyn_inv = dyn_inv_scale;
+        WN_HIP(launch_hgemm(precision, cp.kb.kernel(), HEPI_F32, a, st), "hgemm<conv dx>");
+        return WN_OK;
+    }
     a.dst[0] = dst_of(view(dx_series, Ci, s->ld, P));
     if (act) a.z = dst_of(view(act, Ci, s->ld, P));
     a.oscale2 = 1.0f; a.leaky = act ? leaky_slope : 1.0f; a.flag = overflow_flag;
-    wn::ProfScopeShared prof(KC_HCONV_BWD_DATA, 2.0 * Ci * (double)(k * Co) * (double)s->batch * s->length, st);
     if (cp.col && act && cp.kb.nslab == 1 && cp.kb.MT == 2 && !cp.kb.k32) {
         HColArgs c;
         col_args_common(c, a, Ci, (char*)packed + cp.off_dump, s->batch, s->length, s->ld, s->halo);
@@ -1436,6 +1375,47 @@ int wn_hconv_backward_data_series(const wn_conv_shape* s, int precision, const v
     }
     WN_HIP(launch_hgemm(precision, cp.kb.kernel(), HEPI_LEAKY, a, st), "hgemm<conv dx series>");
     return WN_OK;
+}
+}  // namespace
+
+int wn_hconv_forward(const wn_conv_shape* s, int precision, const void* packed, const void* x, float* y_dense,
+                     wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_hconv(s, precision, off);
+    if (rc != WN_OK) return rc;
+    if (!packed || !x || !y_dense) return WN_ERR_NULL;
+    return hconv_forward(s, precision, off, packed, x, y_dense, nullptr, 1.0f, 1.0f, nullptr, (hipStream_t)stream);
+}
+
+int wn_hconv_backward_data(const wn_conv_shape* s, int precision, const void* packed, const void* dy, float* dx_dense,
+                           const float* dyn_inv_scale, wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_hconv(s, precision, off);
+    if (rc != WN_OK) return rc;
+    if (!packed || !dy || !dx_dense) return WN_ERR_NULL;
+    return hconv_backward_data(s, precision, off, packed, dy, dx_dense, dyn_inv_scale, nullptr, nullptr, 1.0f, nullptr,
+                               (hipStream_t)stream);
+}
+
+// `packed` from wn_hconv_pack with the input's scale
+int wn_hconv_forward_series(const wn_conv_shape* s, int precision, const void* packed, const void* x, void* y_series, float out_scale,
+                            float leaky_slope, unsigned* overflow_flag, wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_hconv(s, precision, off);
+    if (rc != WN_OK) return rc;
+    if (!packed || !x || !y_series) return WN_ERR_NULL;
+    if (!(out_scale > 0.0f)) return WN_ERR_BAD_SHAPE;
+    return hconv_forward(s, precision, off, packed, x, nullptr, y_series, out_scale, leaky_slope, overflow_flag, (hipStream_t)stream);
+}
+
+int wn_hconv_backward_data_series(const wn_conv_shape* s, int precision, const void* packed, const void* dy, const void* act,
+                                  float leaky_slope, void* dx_series, unsigned* overflow_flag, wn_stream_t stream) {
+    int off[WN_MAX_TAPS];
+    int rc = check_hconv(s, precision, off);
+    if (rc != WN_OK) return rc;
+    if (!packed || !dy || !dx_series) return WN_ERR_NULL;
+    return hconv_backward_data(s, precision, off, packed, dy, nullptr, nullptr, dx_series, act, leaky_slope, overflow_flag,
+                               (hipStream_t)stream);
 }
 
 namespace {

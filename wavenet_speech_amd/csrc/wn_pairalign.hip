@@ -36,6 +36,7 @@
 #include <climits>
 
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -256,9 +257,6 @@ __global__ __launch_bounds__(kMulti ? kPaMaxThreads : 64) void pair_align_kernel
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-}
 using namespace wn;
 
 static int check_pair_align(int batch, int max_ref_len, int max_query_len) {
@@ -311,7 +309,6 @@ int wn_pair_align(const int* ref, long long ref_stride, const int* ref_lengths, 
     hipStream_t s = (hipStream_t)stream;
     if (threads == 64) hipLaunchKernelGGL(pair_align_kernel<false>, dim3(batch), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(pair_align_kernel<true>, dim3(batch), dim3(threads), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "pair_align");
+    WN_HIP(hipGetLastError(), "pair_align");
     return WN_OK;
 }

@@ -20,6 +20,7 @@
 // No floating point, no workspace, no scratch.  No value of an op, a label, a length, a qual or a dwell is used as an index
 // before it is checked.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 #include <limits.h>
 
@@ -218,8 +219,6 @@ __global__ __launch_bounds__(kPThreads) void quality_profile_kernel(const Profil
     }
 }
 
-int hip_fail_shared(hipError_t e, const char* what);
-
 }  // namespace wn
 using namespace wn;
 
@@ -247,7 +246,6 @@ int wn_quality_profile(const unsigned char* ops, long long ops_stride, const int
     a.read_counts = read_counts; a.outcome = outcome; a.ref_index = ref_index; a.bad = bad;
     a.B = batch; a.N = max_ref_len; a.M = max_query_len; a.max_ops = max_ops; a.C = classes; a.count_ends = count_ends;
     hipLaunchKernelGGL(quality_profile_kernel, dim3(batch), dim3(kPThreads), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "quality_profile");
+    WN_HIP(hipGetLastError(), "quality_profile");
     return WN_OK;
 }

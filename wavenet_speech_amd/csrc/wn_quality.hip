@@ -22,6 +22,7 @@
 // No value of a label, frame or length is used as an index before it is checked.  No atomics on floating point, no workspace,
 // no scratch, plain vector stores; expf and log10 are the device library's.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 #include <float.h>
 
@@ -166,8 +167,6 @@ __global__ __launch_bounds__(kQThreads) void read_error_kernel(const QualityArgs
     if (tid == 0) a.read_error[b] = read_ok && len > 0 ? (float)(part[0] / (double)len) : __builtin_nanf("");
 }
 
-int hip_fail_shared(hipError_t e, const char* what);
-
 }  // namespace wn
 using namespace wn;
 
@@ -191,16 +190,14 @@ int wn_ctc_base_quality(const float* x, long long sb, long long sc, long long st
     hipStream_t s = (hipStream_t)stream;
     if (error || qual || dwell || bad) {                             // the per-base launch also owns the bad count
         hipLaunchKernelGGL(base_quality_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(kQThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail_shared(e, "base_quality");
+        WN_HIP(hipGetLastError(), "base_quality");
     }
     if (read_error) {
         if (error)
             hipLaunchKernelGGL(read_error_kernel<true>, dim3(batch), dim3(kQThreads), 0, s, a);
         else
             hipLaunchKernelGGL(read_error_kernel<false>, dim3(batch), dim3(kQThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail_shared(e, "read_error");
+        WN_HIP(hipGetLastError(), "read_error");
     }
     return WN_OK;
 }

@@ -26,6 +26,7 @@
 // The uniform integer in [lo, hi) is lo + mulhi(word, hi - lo): its bias is at most (hi - lo) / 2^32 per value.
 // All results leave through ordinary vector stores from plain C++.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 #include "wn_philox.h"
 
@@ -245,9 +246,6 @@ __global__ __launch_bounds__(kRdTile) void reads_signal_kernel(const int* __rest
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-}
 using namespace wn;
 
 static int check_reads(int batch, int max_bases) {
@@ -302,8 +300,7 @@ int wn_reads_plan(unsigned long long seed, int batch, int min_bases, int max_bas
     a.kmers = reinterpret_cast<unsigned short*>(workspace); a.kmer_stride = (long long)reads_kmer_stride(max_bases);
     a.bad = bad; a.clamped = clamped;
     hipLaunchKernelGGL(reads_plan_kernel, dim3(batch), dim3(kRdTile), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "reads_plan");
+    WN_HIP(hipGetLastError(), "reads_plan");
     return WN_OK;
 }
 
@@ -323,7 +320,6 @@ int wn_reads_signal(const int* base_lengths, const int* starts, const int* signa
                        base_lengths, starts, signal_lengths, reinterpret_cast<const unsigned short*>(workspace),
                        (long long)reads_kmer_stride(max_bases), max_bases, window, ld, means, stdvs, seed, noise, signal, sample_kmer,
                        clipped_lengths, bad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "reads_signal");
+    WN_HIP(hipGetLastError(), "reads_signal");
     return WN_OK;
 }

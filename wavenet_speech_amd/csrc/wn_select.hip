@@ -27,6 +27,7 @@
 // the stream by wn_read_select itself.  The number of launches depends on the dtype and on center only; nothing is read back.
 // No length or rank is used before it is checked.  No scratch, no loop with a data-dependent trip count beyond the tile.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 
 namespace wn {
@@ -277,8 +278,6 @@ __global__ __launch_bounds__(kSelThreads) void select_final_kernel(int ld, const
     }
 }
 
-int hip_fail_shared(hipError_t e, const char* what);
-
 template <typename T, bool DEV>
 static int select_launch(const void* signal, int batch, int ld, const int* signal_lengths, const int* ranks, int K,
                          const float* center, float* out, unsigned* hist, int* bad, hipStream_t stream) {
@@ -287,13 +286,11 @@ static int select_launch(const void* signal, int batch, int ld, const int* signa
     for (int pass = 0; pass < kPasses; ++pass) {
         hipLaunchKernelGGL((select_pass_kernel<T, DEV>), grid, dim3(kSelThreads), 0, stream, reinterpret_cast<const T*>(signal), ld,
                            signal_lengths, ranks, K, center, pass, hist);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail_shared(e, "read_select pass");
+        WN_HIP(hipGetLastError(), "read_select pass");
     }
     hipLaunchKernelGGL((select_final_kernel<T, DEV>), dim3((unsigned)batch), dim3(kSelThreads), 0, stream, ld, signal_lengths, ranks,
                        K, hist, out, bad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "read_select final");
+    WN_HIP(hipGetLastError(), "read_select final");
     return WN_OK;
 }
 
@@ -315,8 +312,7 @@ int wn_read_select(const void* signal, int signal_is_int16, int batch, int ld, c
     if ((reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need) return WN_ERR_WORKSPACE;
     if (reinterpret_cast<uintptr_t>(signal) & (signal_is_int16 ? 1 : 3)) return WN_ERR_WORKSPACE;       // not aligned to its element
     hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(workspace, 0, need, s);
-    if (e != hipSuccess) return hip_fail_shared(e, "read_select memset");
+    WN_HIP(hipMemsetAsync(workspace, 0, need, s), "read_select memset");
     unsigned* hist = reinterpret_cast<unsigned*>(workspace);
     if (signal_is_int16)
         return center ? select_launch<short, true>(signal, batch, ld, signal_lengths, ranks, K, center, out, hist, bad, s)

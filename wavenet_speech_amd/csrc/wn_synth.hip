@@ -15,6 +15,7 @@
 // (wn_embed.hip) the one-hot is not needed at all and the generator moves 8 B per sample.
 // The per-read mean is a fixed-order sum (per-workgroup partials combined in index order): bit-reproducible run to run.
 #include "../../include/wavenet_amd.h"
+#include "wn_host.h"
 #include "wn_kernels.h"
 #include "wn_philox.h"
 
@@ -135,12 +136,7 @@ __global__ __launch_bounds__(kSynTile) void synth_quantize_kernel(const double* 
 
 }  // namespace wn
 
-namespace wn {
-int hip_fail_shared(hipError_t e, const char* what);
-struct ProfScopeShared { void* impl; ProfScopeShared(int kc, double flops, hipStream_t st); ~ProfScopeShared(); };
-}
 using namespace wn;
-static const int KC_SYNTH = 18;   // index into wn_api.hip's kernel-class table
 
 static int check_synth(int batch, int length) {
     if (batch <= 0 || length <= 0) return WN_ERR_BAD_SHAPE;
@@ -158,10 +154,9 @@ int wn_synth_bases(unsigned long long seed, int batch, int nbases, long long* ba
     if (!bases) return WN_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)batch * nbases;
-    ProfScopeShared prof(KC_SYNTH, 0.0, st);
+    ProfScope prof(KC_SYNTH, 0.0, st);
     hipLaunchKernelGGL(synth_bases_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, seed, n, bases);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "synth_bases");
+    WN_HIP(hipGetLastError(), "synth_bases");
     return WN_OK;
 }
 
@@ -176,11 +171,10 @@ int wn_synth_signal(const long long* bases, int batch, int nbases, int length, i
     if (workspace_bytes < wn_synth_workspace_bytes(batch, length)) return WN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (length + kSynTile - 1) / kSynTile;
-    ProfScopeShared prof(KC_SYNTH, 0.0, st);
+    ProfScope prof(KC_SYNTH, 0.0, st);
     hipLaunchKernelGGL(synth_signal_kernel, dim3(nblk, batch), dim3(kSynTile), 0, st, bases, nbases, length, upsampling, means, stdvs,
                        seed, noise, picoamps, (SynPart*)workspace, nblk, bad_bases);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "synth_signal");
+    WN_HIP(hipGetLastError(), "synth_signal");
     return WN_OK;
 }
 
@@ -193,7 +187,7 @@ int wn_synth_quantize(const double* picoamps, const void* workspace, size_t work
     if (workspace_bytes < wn_synth_workspace_bytes(batch, length)) return WN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (length + kSynTile - 1) / kSynTile;
-    ProfScopeShared prof(KC_SYNTH, 0.0, st);
+    ProfScope prof(KC_SYNTH, 0.0, st);
     const bool vec = one_hot && (length % 4 == 0) && ((reinterpret_cast<uintptr_t>(one_hot) & 15) == 0);
     if (vec)
         hipLaunchKernelGGL((synth_quantize_kernel<true>), dim3(nblk, batch), dim3(kSynTile), 0, st, picoamps, (const SynPart*)workspace,
@@ -201,7 +195,6 @@ int wn_synth_quantize(const double* picoamps, const void* workspace, size_t work
     else
         hipLaunchKernelGGL((synth_quantize_kernel<false>), dim3(nblk, batch), dim3(kSynTile), 0, st, picoamps, (const SynPart*)workspace,
                            nblk, length, num_levels, edges, levels, one_hot);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail_shared(e, "synth_quantize");
+    WN_HIP(hipGetLastError(), "synth_quantize");
     return WN_OK;
 }
