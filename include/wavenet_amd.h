@@ -506,6 +506,70 @@ int wn_quality_profile(const unsigned char* ops, long long ops_stride, const int
                        unsigned char* outcome /* may be NULL */, int* ref_index /* may be NULL */, int* bad /* may be NULL */,
                        wn_stream_t stream);
 
+/* ---- Event tables and k-mer pore-model tables from a segmentation (wavenet_speech_amd.events.kmer_events, DESIGN.md section
+ * 7j): signal + event boundaries + bases give, per event, its k-mer, its sample range and the integer sum and sum of squares of
+ * its samples; the used events are added into per-k-mer tables from which a pore model (level mean and stdv per k-mer) and a
+ * dwell model are fitted on the host.  The device-side counterpart of what the reference's utils/dump_distributions.py and
+ * utils/dump_durations_from_eventalign.py read out of nanopolish eventalign files.  All pointers are DEVICE pointers.
+ *   signal           rows of signal_stride elements of which max_signal may be read: fp32 (signal_kind 0) or int16 (1)
+ *   signal_lengths   [B] int32, in [0, max_signal]
+ *   scale_shift      [B][2] fp32 (scale, shift) or NULL
+ *   seg_begin, seg_end   int32: event j of read b begins at seg_begin[b seg_row_stride + j seg_elem_stride] and ends (exclusive)
+ *                    at seg_end[the same offset].  spans [B][N][2] of wn_ctc_align: (spans, spans + 1, 2 N, 2); starts
+ *                    [B][N + 1] of wn_reads_plan: (starts, starts + 1, N + 1, 1)
+ *   frame_stride, frame_offset   event j covers the samples [begin frame_stride + frame_offset, end frame_stride + frame_offset)
+ *                    intersected with [0, signal_lengths[b]); positions are formed in 64 bits
+ *   labels           int32 rows of labels_stride elements, bases in 1..4; label_lengths [B] int32 in [0, max_labels]
+ *   events           [B] int32 in [0, max_events]: the events of each read
+ *   k, first         the k-mer of event j is labels[j + first .. j + first + k); its index is sum_i (label_i - 1) 4^(k-1-i), the
+ *                    first base most significant.  first = -2, k = 5: centred 5-mers over force-aligned bases; first = 2 / 0:
+ *                    the "loader" / "generator" windows of wn_reads_plan
+ *   frac_bits F, max_dwell D
+ * Arithmetic (the definition).  v = (double)x (double)scale + (double)shift -- the product is exact in double for both kinds,
+ * so there is one rounding and a fused multiply-add gives the same bits -- or v = (double)x without scale_shift;
+ * q = llrint(v 2^F), ties to even.  A used sample must be finite with |q| < 2^23; a used event holds at most 65536 samples, so
+ * sum q^2 < 2^62.  All sums are integers: any reduction order and any atomic order gives the same bits, two runs are bitwise
+ * identical.
+ * Per-event outputs [B][max_events], each may be NULL:
+ *   ev_kmer  int32   the k-mer index when the event is USED, else the first of these that applies:
+ *                    -4 in a bad read, or j >= events[b];   -2 no samples after clipping;   -3 cut by signal_lengths[b] (its
+ *                    unclipped end lies past it) or longer than 65536 samples;   -1 the window runs off [0, label_lengths[b])
+ *   ev_start, ev_len int32   the clipped range [min(s0, n), min(s1, n)), n = signal_lengths[b]; 0, 0 with code -4
+ *   ev_sum, ev_sumsq int64   sum q and sum q^2 over the samples of a used event; 0 for every other event (its samples are
+ *                    not looked at)
+ * read_counts [B][4] int32: events used, events with code -1, events with code -2 or -3, samples in used events.
+ * Tables, ADDED INTO with 64-bit integer adds and never cleared; only used events of good reads enter:
+ *   kmer_stats [4^k][5] int64   events, samples, sum of ev_sum, sum of (ev_sumsq & 0xffffffff), sum of (ev_sumsq >> 32): the two
+ *                    limbs are taken PER EVENT, so sum q^2 = column 4 * 2^32 + column 3 exactly, beyond 64 bits
+ *   dwell_hist [4^k][D + 1] int64   column min(ev_len, D)
+ * Checked on the device.  A read is bad when signal_lengths[b], label_lengths[b] or events[b] is out of range (nothing else
+ * of it is then read); a boundary of an event j < events[b] is negative, begin > end, or begin_j < end_(j-1) (gaps are fine,
+ * overlaps are not); a label in the window of an event that would otherwise be used is outside 1..4; a sample of such an
+ * event is not finite or has |q| >= 2^23 (scale and shift included).  Samples and labels of events with a negative code are
+ * never read and cannot make a read bad.  A bad read has ev_kmer -4, ev_start / ev_len / ev_sum / ev_sumsq 0, read_counts -1
+ * throughout, adds nothing to any table and counts once in *bad (DEVICE int, caller-zeroed, may be NULL).  No bad value is
+ * used as an index.
+ * One memset and two launches through the workspace (validity must be known before anything reaches a shared table): events
+ * first, grid (ceil(max_events / 256), batch) so that a long read does not serialise on one workgroup; tables second.  Nothing
+ * is read back: the call can be captured into a HIP graph.  workspace: wn_kmer_events_workspace_bytes(batch, max_events)
+ * bytes, 16-byte aligned (per-read flags and counts, and the per-event rows the caller passes NULL for); 0 for batch or
+ * max_events out of range.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_events, max_signal or max_labels < 1, a negative
+ * stride, frame_stride < 1, frame_offset < 0, signal_kind not 0 or 1.  WN_ERR_UNSUPPORTED: k outside 1..6, |first| > 8, F
+ * outside 0..20, D outside 1..65536, batch > 65535, max_signal frame_stride >= 2^31.  WN_ERR_NULL: signal, signal_lengths,
+ * seg_begin, seg_end, labels, label_lengths, events or the workspace (with or without tables); every output NULL (bad is no
+ * output).  WN_ERR_WORKSPACE: a workspace too small or not 16-byte aligned, a signal not aligned to its element size. */
+size_t wn_kmer_events_workspace_bytes(int batch, int max_events);
+int wn_kmer_events(const void* signal, int signal_kind, long long signal_stride, const int* signal_lengths,
+                   const float* scale_shift /* may be NULL */, const int* seg_begin, const int* seg_end, long long seg_row_stride,
+                   long long seg_elem_stride, int frame_stride, int frame_offset, const int* labels, long long labels_stride,
+                   const int* label_lengths, const int* events, int batch, int max_signal, int max_labels, int max_events, int k,
+                   int first, int frac_bits, int max_dwell, int* ev_kmer /* may be NULL */, int* ev_start /* may be NULL */,
+                   int* ev_len /* may be NULL */, long long* ev_sum /* may be NULL */, long long* ev_sumsq /* may be NULL */,
+                   int* read_counts /* may be NULL */, long long* kmer_stats /* may be NULL */,
+                   long long* dwell_hist /* may be NULL */, void* workspace, size_t workspace_bytes, int* bad /* may be NULL */,
+                   wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

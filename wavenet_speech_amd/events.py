@@ -1,0 +1,340 @@
+"""
+Event tables and k-mer pore-model fitting from alignments (csrc/wn_events.hip through the C ABI's
+wn_kmer_events).
+
+    reads = ragged_reads(64, (200, 300), device="cuda")                                   # or real signal + ctc_forced_align spans
+    ev = kmer_events(reads.signal, reads.signal_lengths, reads.bases, reads.base_lengths, starts=reads.starts, first=2)
+    means, stdvs, counts = fit_kmer_model(ev.kmer_stats, prior=standin_kmer_table())
+    dwell = fit_dwell_model(ev.dwell_hist, sample_rate=4000.0)                            # ("gamma", shape, rate, sample_rate)
+    again = ragged_reads(64, (200, 300), table=(means, stdvs), dwell=dwell, device="cuda")
+
+What the reference does off-line from nanopolish `eventalign` files (utils/dump_distributions.py: samples per k-mer;
+utils/dump_durations_from_eventalign.py: a gamma dwell model per 5-mer), from signal that is on the device already.  kmer_events
+is HIP only (no CPU fallback); the fits and the text formatter run on the host on the small tables.
+"""
+import math
+from collections import namedtuple
+
+import torch
+
+from . import _flags, _lib
+from .decoding import DEFAULT_ALPHABET
+
+MAX_K = 6
+MAX_FIRST = 8
+MAX_FRAC_BITS = 20
+MAX_DWELL = 65536
+EVENTALIGN_COLUMNS = ("read_index", "position", "reference_kmer", "event_index", "event_level_mean", "event_stdv", "event_length",
+                      "event_start_time", "model_mean", "model_stdv", "standardized_level")
+
+_Fields = namedtuple("KmerEvents", "kmer start length sum sumsq read_counts kmer_stats dwell_hist")
+
+
+class KmerEvents(_Fields):
+    """kmer [B, N] int32: the k-mer index of a used event, else -1 (its window runs off the labels), -2 (no samples), -3 (cut by
+    the read's end, or above 65536 samples), -4 (bad read, or past the read's events); start, length [B, N] int32: the clipped
+    sample range; sum, sumsq [B, N] int64: the sums of q = round(v 2^frac_bits) and of q^2 over a used event (0 elsewhere) -- the
+    five are None with want_events=False; read_counts [B, 4] int32: events used, with code -1, with code -2 or -3, samples used
+    (-1 throughout for a bad read); kmer_stats [4^k, 5] int64: events, samples, sum q, and the low and high 32-bit limbs of
+    sum q^2; dwell_hist [4^k, max_dwell + 1] int64: events by min(length, max_dwell).  Device tensors.  k, first, frac_bits and
+    max_dwell of the call ride along as attributes."""
+
+    def __new__(cls, *fields, k=5, first=-2, frac_bits=12, max_dwell=255):
+        self = super().__new__(cls, *fields)
+        self.k, self.first, self.frac_bits, self.max_dwell = int(k), int(first), int(frac_bits), int(max_dwell)
+        return self
+
+    @property
+    def mean(self):
+        """[B, N] float64: the level of every used event in the units of v, NaN elsewhere (one division of exact integers)"""
+        n = torch.where(self.kmer >= 0, self.length, torch.zeros_like(self.length)).double()
+        return self.sum.double() / (n * float(1 << self.frac_bits))          # 0 / 0 = NaN where the event is not used
+
+    @property
+    def stdv(self):
+        """[B, N] float64: the population standard deviation of every used event, NaN elsewhere.  Formed as sumsq / n - (sum / n)^2
+        in float64: its absolute error is about 2^-52 level^2 / stdv"""
+        n = torch.where(self.kmer >= 0, self.length, torch.zeros_like(self.length)).double()
+        m = self.sum.double() / n
+        var = (self.sumsq.double() / n - m * m).clamp_(min=0.0)
+        return var.sqrt() / float(1 << self.frac_bits)
+
+
+def _rows(x, dtypes, what, name, dev=None):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
+    if x.dtype not in dtypes:
+        raise ValueError("wavenet_speech_amd.%s: %s must be %s, got %s" % (what, name, " or ".join(str(d) for d in dtypes), x.dtype))
+    if dev is not None and x.device != dev:
+        raise ValueError("wavenet_speech_amd.%s: %s must be on %s" % (what, name, dev))
+    return x.detach()
+
+
+def _lengths(x, B, dev, what, name):
+    x = torch.as_tensor(x).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if x.shape[0] != B:
+        raise ValueError("wavenet_speech_amd.%s: %s must hold %d lengths, got %d" % (what, name, B, x.shape[0]))
+    return x
+
+
+def _table(into, field, shape, dev, what):
+    t = getattr(into, field) if into is not None else None
+    if t is None:
+        return torch.zeros(shape, dtype=torch.int64, device=dev)
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int64 tensor of shape %s on %s" % (what, field, shape, dev))
+    return t
+
+
+def kmer_events(signal, signal_lengths, labels, label_lengths, spans=None, starts=None, k=5, first=-2, frame_stride=1,
+                frame_offset=0, scale_shift=None, frac_bits=12, max_dwell=255, into=None, want_events=True):
+    """The event table of a segmentation and the k-mer tables a pore model is fitted from.
+
+    signal          [B, L] or [B, 1, L], float32 or int16; a view is passed by its row stride (unit stride along L)
+    signal_lengths  [B]; labels [B, n] bases in 1..4 with label_lengths [B]
+    spans           [B, N, 2] int32, CTCAlignment.spans: event j = base j over the frames [spans[b, j, 0], spans[b, j, 1]); each
+                    read has label_lengths[b] events
+    starts          [B, N + 1] int32, RaggedReads.starts: event j = [starts[b, j], starts[b, j + 1]); each read has N events, the
+                    empty ones past a read's last k-mer get code -2.  Exactly one of spans / starts.
+    k, first        the k-mer of event j is labels[j + first .. j + first + k), first base most significant as KMER_WEIGHTS; first =
+                    -2: centred 5-mers over force-aligned bases; first = 2 / 0: the generator's "loader" / "generator" windows
+    frame_stride, frame_offset   a boundary f stands for sample f * frame_stride + frame_offset (the stride and the receptive
+                    field's offset of the network the frames came from)
+    scale_shift     [B, 2] float32 or None: v = x * scale + shift in float64 (from read_normalisation's pair: (scale, shift * scale))
+    frac_bits, max_dwell   q = round(v * 2^frac_bits), |q| < 2^23; the dwell histogram has max_dwell + 1 columns, the last one
+                    holds everything at or above max_dwell
+    into            an earlier KmerEvents whose two tables are accumulated in place (and returned); per-read fields are replaced
+    want_events     False: only read_counts and the tables are produced
+    Integer arithmetic, bitwise reproducible, no host synchronisation (capturable with fixed shapes).  A bad read (lengths out of
+    range, negative / reversed / overlapping boundaries, a label outside 1..4 or a non-finite or out-of-range sample in a used
+    event) has kmer -4, zeros elsewhere, read_counts -1, adds nothing to the tables and is reported through
+    check_device_flags().  Returns KmerEvents."""
+    what = "kmer_events"
+    signal = _rows(signal, (torch.float32, torch.int16), what, "signal")
+    dev = signal.device
+    if signal.dim() == 3 and signal.shape[1] == 1:
+        signal = signal[:, 0, :]
+    if signal.dim() != 2 or signal.shape[0] < 1 or signal.shape[1] < 1:
+        raise ValueError("wavenet_speech_amd.%s: signal must be [B, L] or [B, 1, L] with B, L >= 1, got %s" % (what, tuple(signal.shape)))
+    if signal.stride(1) != 1 and signal.shape[1] > 1 or signal.stride(0) < 0:
+        signal = signal.contiguous()
+    B, L = int(signal.shape[0]), int(signal.shape[1])
+    labels = _rows(labels, (torch.int32, torch.int64), what, "labels", dev)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 1:
+        raise ValueError("wavenet_speech_amd.%s: labels must be [%d, n >= 1], got %s" % (what, B, tuple(labels.shape)))
+    if labels.dtype != torch.int32:
+        labels = labels.int()
+    if labels.stride(1) != 1 and labels.shape[1] > 1 or labels.stride(0) < 0:
+        labels = labels.contiguous()
+    if (spans is None) == (starts is None):
+        raise ValueError("wavenet_speech_amd.%s: give exactly one of spans and starts" % what)
+    k, first, F, D = int(k), int(first), int(frac_bits), int(max_dwell)
+    if not 1 <= k <= MAX_K or abs(first) > MAX_FIRST or not 0 <= F <= MAX_FRAC_BITS or not 1 <= D <= MAX_DWELL:
+        raise ValueError("wavenet_speech_amd.%s: k in [1, %d], |first| <= %d, frac_bits in [0, %d], max_dwell in [1, %d]"
+                         % (what, MAX_K, MAX_FIRST, MAX_FRAC_BITS, MAX_DWELL))
+    frame_stride, frame_offset = int(frame_stride), int(frame_offset)
+    if frame_stride < 1 or frame_offset < 0 or L * frame_stride >= 2 ** 31:
+        raise ValueError("wavenet_speech_amd.%s: frame_stride >= 1, frame_offset >= 0 and L * frame_stride < 2^31" % what)
+    with torch.cuda.device(dev):
+        signal_lengths = _lengths(signal_lengths, B, dev, what, "signal_lengths")
+        label_lengths = _lengths(label_lengths, B, dev, what, "label_lengths")
+        if spans is not None:
+            seg = _rows(spans, (torch.int32,), what, "spans", dev)
+            if seg.dim() != 3 or seg.shape[0] != B or seg.shape[1] < 1 or seg.shape[2] != 2:
+                raise ValueError("wavenet_speech_amd.%s: spans must be [%d, N >= 1, 2], got %s" % (what, B, tuple(seg.shape)))
+            if seg.stride(2) != 1 or seg.stride(0) < 0 or seg.stride(1) < 0:
+                seg = seg.contiguous()
+            N, end_offset, events = int(seg.shape[1]), 1, label_lengths
+        else:
+            seg = _rows(starts, (torch.int32,), what, "starts", dev)
+            if seg.dim() != 2 or seg.shape[0] != B or seg.shape[1] < 2:
+                raise ValueError("wavenet_speech_amd.%s: starts must be [%d, N + 1 >= 2], got %s" % (what, B, tuple(seg.shape)))
+            if seg.stride(0) < 0 or seg.stride(1) < 0:
+                seg = seg.contiguous()
+            N, end_offset = int(seg.shape[1]) - 1, int(seg.stride(1))
+            events = torch.full((B,), N, dtype=torch.int32, device=dev)
+        if scale_shift is not None:
+            scale_shift = _rows(scale_shift, (torch.float32,), what, "scale_shift", dev)
+            if tuple(scale_shift.shape) != (B, 2):
+                raise ValueError("wavenet_speech_amd.%s: scale_shift must be [%d, 2], got %s" % (what, B, tuple(scale_shift.shape)))
+            scale_shift = scale_shift.contiguous()
+        if into is not None and not isinstance(into, KmerEvents):
+            raise ValueError("wavenet_speech_amd.%s: into must be a KmerEvents, got %s" % (what, type(into).__name__))
+        if into is not None and (into.k, into.first, into.frac_bits, into.max_dwell) != (k, first, F, D):
+            raise ValueError("wavenet_speech_amd.%s: into was made with other k, first, frac_bits or max_dwell" % what)
+        lib = _lib.load()
+        from .functional import _p, _stream
+        kmer_stats = _table(into, "kmer_stats", (4 ** k, 5), dev, what)
+        dwell_hist = _table(into, "dwell_hist", (4 ** k, D + 1), dev, what)
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        ev = [None] * 5
+        if want_events:
+            ev = [torch.empty(B, N, **i32) for _ in range(3)] + [torch.empty(B, N, **i64) for _ in range(2)]
+        read_counts = torch.empty(B, 4, **i32)
+        bad = torch.zeros(1, **i32)
+        ws_bytes = lib.wn_kmer_events_workspace_bytes(B, N)
+        if ws_bytes == 0:
+            _lib.check(-2, "wn_kmer_events_workspace_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        seg_end = seg.data_ptr() + 4 * end_offset
+        _lib.check(lib.wn_kmer_events(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
+                                      _p(seg), _p(seg_end), seg.stride(0), seg.stride(1), frame_stride, frame_offset, _p(labels),
+                                      labels.stride(0), _p(label_lengths), _p(events), B, L, int(labels.shape[1]), N, k, first, F, D,
+                                      _p(ev[0]), _p(ev[1]), _p(ev[2]), _p(ev[3]), _p(ev[4]), _p(read_counts), _p(kmer_stats),
+                                      _p(dwell_hist), _p(ws), ws_bytes, _p(bad), _stream()), "wn_kmer_events")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n: "wavenet_speech_amd.kmer_events: %d bad read(s): a length out of range, a negative, reversed or "
+                          "overlapping event boundary, a label outside 1..4 or a non-finite or out-of-range sample in a used event" % n,
+                          at_once=False)
+    return KmerEvents(ev[0], ev[1], ev[2], ev[3], ev[4], read_counts, kmer_stats, dwell_hist, k=k, first=first, frac_bits=F, max_dwell=D)
+
+
+def _host_table(t, what, name, columns=None):
+    rows = torch.as_tensor(t)
+    if rows.is_floating_point() or rows.dim() != 2 or (columns is not None and rows.shape[1] != columns):
+        raise ValueError("wavenet_speech_amd.%s: %s must be a 2-d integer table%s" % (what, name, "" if columns is None else " with %d columns" % columns))
+    return rows.cpu().tolist()
+
+
+def fit_kmer_model(kmer_stats, frac_bits=12, min_count=100, prior=None):
+    """The pore model of a kmer_stats table ([4^k, 5] integers): returns (means, stdvs, counts), float64 [4^k] host tensors --
+    what ragged_reads(table=...) and RawGaussianModelLoader take.  Per k-mer with n samples, S1 = sum q and S2 = high limb * 2^32
+    + low limb = sum q^2: mean = S1 / (n 2^F), stdv = sqrt((n S2 - S1^2) / (n^2 2^2F)), the POPULATION standard deviation of its
+    samples.  Both numerators and denominators are exact Python integers divided once (correctly rounded), so mean carries one
+    float64 rounding and stdv two.  counts: the samples of each k-mer.  A k-mer with fewer than min_count samples takes its
+    entry of prior = (means, stdvs), or NaN.  Runs on the host: the table is 40 KB at k = 5."""
+    what = "fit_kmer_model"
+    rows = _host_table(kmer_stats, what, "kmer_stats", 5)
+    F, min_count = int(frac_bits), int(min_count)
+    if not 0 <= F <= MAX_FRAC_BITS or min_count < 1:
+        raise ValueError("wavenet_speech_amd.%s: frac_bits in [0, %d] and min_count >= 1" % (what, MAX_FRAC_BITS))
+    nan = float("nan")
+    pm = ps = None
+    if prior is not None:
+        pm, ps = (torch.as_tensor(p).double().cpu().reshape(-1).tolist() for p in prior)
+        if len(pm) != len(rows) or len(ps) != len(rows):
+            raise ValueError("wavenet_speech_amd.%s: prior must hold %d means and stdvs" % (what, len(rows)))
+    means, stdvs, counts = [], [], []
+    for i, (_, n, s1, lo, hi) in enumerate(rows):
+        counts.append(float(n))
+        if n < min_count:
+            means.append(pm[i] if pm else nan)
+            stdvs.append(ps[i] if ps else nan)
+            continue
+        s2 = (hi << 32) + lo
+        means.append(s1 / (n << F))
+        stdvs.append(math.sqrt((n * s2 - s1 * s1) / ((n * n) << (2 * F))))
+    f64 = dict(dtype=torch.float64)
+    return torch.tensor(means, **f64), torch.tensor(stdvs, **f64), torch.tensor(counts, **f64)
+
+
+def _digamma(x):
+    return float(torch.special.digamma(torch.tensor(x, dtype=torch.float64)))
+
+
+def _trigamma(x):
+    return float(torch.special.polygamma(1, torch.tensor(x, dtype=torch.float64)))
+
+
+def _gamma_shape(s):
+    """the root a of log a - digamma(a) = s, s > 0: Minka's start and his Newton step on 1 / a, float64"""
+    a = (3.0 - s + math.sqrt((s - 3.0) ** 2 + 24.0 * s)) / (12.0 * s)
+    for _ in range(100):
+        f = math.log(a) - _digamma(a) - s
+        step = f / (a * a * (1.0 / a - _trigamma(a)))
+        new = 1.0 / (1.0 / a + step)
+        if not (new > 0.0 and math.isfinite(new)):
+            break
+        done = abs(new - a) <= 4e-16 * a
+        a = new
+        if done:
+            break
+    return a
+
+
+def _fit_gamma(hist, sample_rate):
+    """hist[d] events of d samples (hist[0] ignored) -> (shape, rate, events) of the maximum-likelihood gamma of d / sample_rate"""
+    n = sum(hist[1:])
+    mean_d = math.fsum(d * h for d, h in enumerate(hist) if d and h) / n
+    mean_log = math.fsum(h * math.log(d) for d, h in enumerate(hist) if d and h) / n
+    s = math.log(mean_d) - mean_log
+    if not s > 1e-14:
+        raise ValueError("wavenet_speech_amd.fit_dwell_model: every event has the same length: the gamma shape is unbounded")
+    a = _gamma_shape(s)
+    return a, a * sample_rate / mean_d, n
+
+
+def fit_dwell_model(dwell_hist, sample_rate, per_kmer=False, min_count=100):
+    """The gamma dwell model of a dwell_hist table ([4^k, D + 1] integers): the maximum-likelihood gamma of the event durations
+    d / sample_rate seconds, as the reference's utils/dump_durations_from_eventalign.py fits per 5-mer.  The shape a solves
+    log a - digamma(a) = log(mean d) - mean(log d) (Newton from Minka's closed-form start, float64); rate = a sample_rate / mean d.
+    per_kmer=False: all k-mers pooled; returns ("gamma", shape, rate, sample_rate), the dwell spec of ragged_reads; raises below
+    min_count events.  per_kmer=True: returns a float64 [4^k, 2] host tensor of (shape, rate), NaN for a k-mer with fewer than
+    min_count events or with events of one length only.
+    Raises if the last column, which holds every event of D samples or more, is not empty: rerun kmer_events with a larger
+    max_dwell.  Dwells are whole samples: the generator truncates Gamma * sample_rate to an integer (and lifts 0 to 1), so a fit to
+    its output is biased low in the mean by about half a sample -- as the reference script's fit to nanopolish's event lengths."""
+    what = "fit_dwell_model"
+    rows = _host_table(dwell_hist, what, "dwell_hist")
+    sample_rate, min_count = float(sample_rate), int(min_count)
+    if len(rows[0]) < 2 or not (sample_rate > 0 and math.isfinite(sample_rate)) or min_count < 1:
+        raise ValueError("wavenet_speech_amd.%s: at least two columns, sample_rate > 0 and min_count >= 1" % what)
+    clamped = sum(r[-1] for r in rows)
+    if clamped:
+        raise ValueError("wavenet_speech_amd.%s: %d event(s) in the clamp column (%d samples or more): use a larger max_dwell"
+                         % (what, clamped, len(rows[0]) - 1))
+    if not per_kmer:
+        pooled = [sum(col) for col in zip(*rows)]
+        if sum(pooled[1:]) < min_count:
+            raise ValueError("wavenet_speech_amd.%s: %d event(s), fewer than min_count = %d" % (what, sum(pooled[1:]), min_count))
+        a, rate, _ = _fit_gamma(pooled, sample_rate)
+        return ("gamma", a, rate, sample_rate)
+    out = []
+    for r in rows:
+        try:
+            if sum(r[1:]) < min_count:
+                raise ValueError
+            a, rate, _ = _fit_gamma(r, sample_rate)
+            out.append([a, rate])
+        except ValueError:
+            out.append([float("nan")] * 2)
+    return torch.tensor(out, dtype=torch.float64)
+
+
+def eventalign_rows(events, labels, names=None, model=None, alphabet=DEFAULT_ALPHABET, sample_rate=None, header=True):
+    """host formatter: the event table as the tab-separated lines of nanopolish `eventalign`, with the columns this library can
+    fill (EVENTALIGN_COLUMNS): read_index (names[b] when given, else b), position (of the k-mer's first base, j + first),
+    reference_kmer (alphabet[label] per base), event_index j, event_level_mean (%.2f), event_stdv (%.3f), event_length and
+    event_start_time (samples; seconds %.5f with sample_rate), and with model = (means, stdvs): model_mean, model_stdv (%.2f) and
+    standardized_level (%.2f) = (level - model_mean) / model_stdv.  Events with a negative code are left out.  events: a
+    KmerEvents with its per-event fields; labels: the labels it was made from.  Returns a list of lines without line ends."""
+    if not isinstance(events, KmerEvents) or events.kmer is None:
+        raise ValueError("eventalign_rows: events must be a KmerEvents with its per-event fields (want_events=True)")
+    k, first = events.k, events.first
+    kmer = events.kmer.cpu().tolist()
+    start, length = events.start.cpu().tolist(), events.length.cpu().tolist()
+    mean, stdv = events.mean.cpu().tolist(), events.stdv.cpu().tolist()
+    rows = torch.as_tensor(labels).cpu().tolist()
+    if len(rows) != len(kmer) or (names is not None and len(names) != len(kmer)):
+        raise ValueError("eventalign_rows: %d reads, %d label rows, %s names" % (len(kmer), len(rows), "no" if names is None else len(names)))
+    mm = ms = None
+    if model is not None:
+        mm, ms = (torch.as_tensor(p).double().cpu().reshape(-1).tolist() for p in model)
+    out = []
+    if header:
+        out.append("\t".join(EVENTALIGN_COLUMNS if model is not None else EVENTALIGN_COLUMNS[:8]))
+    for b, codes in enumerate(kmer):
+        name = str(names[b]) if names is not None else str(b)
+        for j, code in enumerate(codes):
+            if code < 0:
+                continue
+            text = "".join(alphabet[int(v)] for v in rows[b][j + first:j + first + k])
+            if sample_rate is None:
+                span = ["%d" % length[b][j], "%d" % start[b][j]]
+            else:
+                span = ["%.5f" % (length[b][j] / float(sample_rate)), "%.5f" % (start[b][j] / float(sample_rate))]
+            cols = [name, "%d" % (j + first), text, "%d" % j, "%.2f" % mean[b][j], "%.3f" % stdv[b][j]] + span
+            if model is not None:
+                cols += ["%.2f" % mm[code], "%.2f" % ms[code], "%.2f" % ((mean[b][j] - mm[code]) / ms[code])]
+            out.append("\t".join(cols))
+    return out
