@@ -570,6 +570,56 @@ int wn_kmer_events(const void* signal, int signal_kind, long long signal_stride,
                    long long* dwell_hist /* may be NULL */, void* workspace, size_t workspace_bytes, int* bad /* may be NULL */,
                    wn_stream_t stream);
 
+/* ---- Signal-to-base alignment under the k-mer pore model (wavenet_speech_amd.events.signal_align): the
+ * raw samples of a read against the k-mers of its KNOWN bases, the minimum-cost monotone path inside a band around the
+ * diagonal.  The segmentation nanopolish `eventalign` makes before the reference's utils/dump_distributions.py reads it, with
+ * no network; its `starts` go straight into wn_kmer_events.  All pointers are DEVICE pointers.
+ *   signal, signal_kind, signal_stride, signal_lengths, scale_shift, labels, labels_stride, label_lengths: as wn_kmer_events
+ *   model            [4^k][3] int32: level, weight, offset per k-mer
+ *   k, first         read b has N_b = label_lengths[b] - (k - 1) - 2 first STATES; state j is the k-mer labels[j + first .. j +
+ *                    first + k), index sum_i (label_i - 1) 4^(k-1-i).  first = 2 / 0: the "loader" / "generator" windows of
+ *                    wn_reads_plan
+ *   frac_bits F, weight_shift S, max_cost, band W
+ * Arithmetic (the definition; tests/signal_align_ref.py mirrors it).  Samples exactly as wn_kmer_events: v = (double)x
+ * (double)scale + (double)shift, or (double)x; q = llrint(v 2^F), ties to even; v finite and |q| < 2^23.  With d = |q - level|
+ * (< 2^24), the cost of a sample in a state is   min((d d weight) >> S, max_cost) + offset,   the product in full (79 bits).
+ * A path has s_0 = 0, s_(T-1) = N - 1 and moves by 0 (stay) or +1 (step) per sample: no skips, every k-mer holds at least one
+ * sample, and no transition costs (they would be the same constant on every path).  Its cost is the sum of its sample costs
+ * (below 2^24 (2^31 + 2^30) in magnitude: int64).  The result is the minimum-cost path INSIDE THE BAND:
+ *   c(t) = ((2 t + 1) N) / (2 T) in 64-bit integer division;   lo(t) = clamp(c(t) - W / 2, 0, max(N - W, 0));
+ *   state j is allowed at sample t if and only if lo(t) <= j < lo(t) + W.
+ * For N <= T the centre line c is itself a path inside the band, so an alignment exists whenever T >= N >= 1.  Ties: at (t, j)
+ * the stay predecessor (t - 1, j) is taken first, the step predecessor (t - 1, j - 1) replaces it only if strictly smaller.
+ * Outputs:
+ *   starts        [B][max_events + 1] int32   starts[j] = the first sample of state j; every entry j >= N_b is T_b (the
+ *                 convention of wn_reads_plan: event j = [starts[j], starts[j + 1]))
+ *   score         [B] int64   the cost of the path
+ *   band_hits     [B] int32   the samples t whose state is lo(t) with lo(t) > 0, or lo(t) + W - 1 with lo(t) + W < N: the
+ *                 caller's sign that the band was too narrow
+ *   sample_state  [B][max_signal] int32, may be NULL   the state of every sample, -1 past the read
+ * Checked on the device, in this order.  A read is BAD when signal_lengths[b] is outside [0, max_signal], label_lengths[b]
+ * outside [0, max_labels] or N_b > max_events (nothing else of it is then read): score LLONG_MIN, every other output -1, counted
+ * once in *bad (DEVICE int, caller-zeroed, may be NULL).  A read with N_b < 1 or T_b < N_b gives NO ALIGNMENT: score LLONG_MAX,
+ * starts and sample_state -1, band_hits 0; nothing else of it is read and it is not bad.  Every other read is bad (as above)
+ * when a label in labels[first .. first + N_b + k - 1) is outside 1..4, a sample in [0, T_b) is not finite or has |q| >= 2^23,
+ * or the model row of one of its k-mers has weight < 1, |level| >= 2^23 or |offset| >= 2^30.  Samples past T_b are never read.
+ * No bad value is used as an index.
+ * One launch, one workgroup per read: T_b sequential steps over band / 8 threads, then the trace.  Nothing is read back: the
+ * call can be captured into a HIP graph.  workspace: wn_signal_align_workspace_bytes(batch, max_signal, band) bytes, 16-byte
+ * aligned (1 bit per sample and band slot); 0 for an argument out of range.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_signal, max_labels or max_events < 1, a negative
+ * stride, signal_kind not 0 or 1.  WN_ERR_UNSUPPORTED: k outside 1..6, first outside 0..8, F outside 0..20, S outside 16..63,
+ * max_cost < 1, band not a multiple of 64 in [64, 2048], batch > 65535, max_signal > 2^24, max_events > 2^20.  WN_ERR_NULL:
+ * signal, signal_lengths, labels, label_lengths, model, starts, score, band_hits or the workspace.  WN_ERR_WORKSPACE: a
+ * workspace too small or not 16-byte aligned, a signal not aligned to its element size. */
+size_t wn_signal_align_workspace_bytes(int batch, int max_signal, int band);
+int wn_signal_align(const void* signal, int signal_kind, long long signal_stride, const int* signal_lengths,
+                    const float* scale_shift /* may be NULL */, const int* labels, long long labels_stride,
+                    const int* label_lengths, const int* model, int batch, int max_signal, int max_labels, int max_events, int k,
+                    int first, int frac_bits, int weight_shift, int max_cost, int band, int* starts, long long* score,
+                    int* band_hits, int* sample_state /* may be NULL */, void* workspace, size_t workspace_bytes,
+                    int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

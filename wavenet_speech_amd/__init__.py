@@ -22,6 +22,7 @@ from .functional_half import check_fp16_overflow  # noqa: F401
 from .basecalling import Basecaller, Basecalls, ChunkPlan, chunk_plan, receptive_field  # noqa: F401
 from .normalise import read_med_mad, read_normalisation, read_order_statistics, read_quantiles  # noqa: F401
 from .events import KmerEvents, eventalign_rows, fit_dwell_model, fit_kmer_model, kmer_events  # noqa: F401
+from .events import SignalAlignment, SignalModel, signal_align, signal_model  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,9 +11,19 @@ wn_kmer_events).
 What the reference does off-line from nanopolish `eventalign` files (utils/dump_distributions.py: samples per k-mer;
 utils/dump_durations_from_eventalign.py: a gamma dwell model per 5-mer), from signal that is on the device already.  kmer_events
 is HIP only (no CPU fallback); the fits and the text formatter run on the host on the small tables.
+
+Where no segmentation exists yet, signal_align (csrc/wn_sigalign.hip through wn_signal_align) makes one from
+the signal, the known bases and a table alone -- what nanopolish does before `eventalign` prints anything -- and the loop
+align -> kmer_events -> fit_kmer_model -> align again is Viterbi training of the table:
+
+    model = signal_model(*standin_kmer_table())                                            # or a fitted (means, stdvs)
+    al = signal_align(reads.signal, reads.signal_lengths, reads.bases, reads.base_lengths, model, first=2, band=128)
+    ev = kmer_events(reads.signal, reads.signal_lengths, reads.bases, reads.base_lengths, starts=al.starts, k=al.k, first=al.first)
+    model = signal_model(*fit_kmer_model(ev.kmer_stats, prior=standin_kmer_table())[:2])
 """
 import math
 from collections import namedtuple
+from fractions import Fraction
 
 import torch
 
@@ -24,6 +34,10 @@ MAX_K = 6
 MAX_FIRST = 8
 MAX_FRAC_BITS = 20
 MAX_DWELL = 65536
+MIN_WEIGHT_SHIFT, MAX_WEIGHT_SHIFT = 16, 63
+MIN_BAND, MAX_BAND = 64, 2048
+MAX_ALIGN_SIGNAL = 1 << 24
+MAX_ALIGN_EVENTS = 1 << 20
 EVENTALIGN_COLUMNS = ("read_index", "position", "reference_kmer", "event_index", "event_level_mean", "event_stdv", "event_length",
                       "event_start_time", "model_mean", "model_stdv", "standardized_level")
 
@@ -338,3 +352,179 @@ def eventalign_rows(events, labels, names=None, model=None, alphabet=DEFAULT_ALP
                 cols += ["%.2f" % mm[code], "%.2f" % ms[code], "%.2f" % ((mean[b][j] - mm[code]) / ms[code])]
             out.append("\t".join(cols))
     return out
+
+
+class SignalModel:
+    """The integer pore model signal_align works under.  table: [4^k, 3] int32 host tensor, per k-mer
+        level   the current in units of 2^-frac_bits (the units of the quantised samples q), |level| < 2^23
+        weight  in [1, 2^31): a sample costs min((q - level)^2 weight >> weight_shift, max_cost) + offset
+        offset  |offset| < 2^30
+    Any table within these ranges may be filled by hand: SignalModel(table, weight_shift, frac_bits, cost_bits); cost_bits only
+    scales SignalAlignment.nats (a cost of 2^cost_bits is one nat).  signal_model() fills it with -log N(v; mean, stdv)."""
+
+    def __init__(self, table, weight_shift, frac_bits=12, cost_bits=8):
+        what = "SignalModel"
+        table = torch.as_tensor(table)
+        if table.is_floating_point() or table.dim() != 2 or table.shape[1] != 3:
+            raise ValueError("wavenet_speech_amd.%s: table must be [4^k, 3] integers, got %s %s" % (what, table.dtype, tuple(table.shape)))
+        k = next((k for k in range(1, MAX_K + 1) if 4 ** k == table.shape[0]), None)
+        if k is None:
+            raise ValueError("wavenet_speech_amd.%s: table must have 4^k rows, k in [1, %d], got %d" % (what, MAX_K, table.shape[0]))
+        table = table.detach().cpu().long()
+        level, weight, offset = table[:, 0], table[:, 1], table[:, 2]
+        if bool((level.abs() >= 2 ** 23).any()) or bool((weight < 1).any()) or bool((weight >= 2 ** 31).any()) or bool((offset.abs() >= 2 ** 30).any()):
+            raise ValueError("wavenet_speech_amd.%s: |level| < 2^23, weight in [1, 2^31) and |offset| < 2^30" % what)
+        self.weight_shift, self.frac_bits, self.cost_bits, self.k = int(weight_shift), int(frac_bits), int(cost_bits), k
+        if not MIN_WEIGHT_SHIFT <= self.weight_shift <= MAX_WEIGHT_SHIFT or not 0 <= self.frac_bits <= MAX_FRAC_BITS or not 0 <= self.cost_bits <= 16:
+            raise ValueError("wavenet_speech_amd.%s: weight_shift in [%d, %d], frac_bits in [0, %d], cost_bits in [0, 16]"
+                             % (what, MIN_WEIGHT_SHIFT, MAX_WEIGHT_SHIFT, MAX_FRAC_BITS))
+        self.table = table.int().contiguous()
+        self._on = {}
+
+    def on(self, device):
+        """the table on a device (uploaded once per device, so that a later call can be captured into a graph)"""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = self.table.to(device)
+        return self._on[device]
+
+
+def signal_model(means, stdvs, frac_bits=12, cost_bits=8):
+    """The SignalModel of a Gaussian pore model: the cost of a sample v in a k-mer is -log N(v; mean, stdv) in units of 2^-cost_bits
+    nats, up to the constant log sqrt(2 pi) - frac_bits log 2 that every path shares.  means, stdvs: [4^k] floats -- what
+    fit_kmer_model returns (with a prior, so that no entry is NaN) and what standin_kmer_table() gives.  With s = stdv 2^F exactly:
+        level  = round(mean 2^F)                         (ties to even, as everywhere below)
+        weight = round(2^(S + cost_bits) / (2 s^2))      so that d^2 weight >> S = 2^cost_bits d^2 / (2 s^2)
+        offset = round(2^cost_bits ln s)                 (one float64 logarithm)
+    S is the largest weight_shift in [16, 63] at which the largest weight (of the smallest stdv) stays below 2^31: it then lies in
+    [2^30, 2^31) unless S = 63 came first.  Refused: a non-finite mean or stdv, a stdv <= 0, a level at or beyond 2^23, a largest
+    weight that does not fit at S = 16, a smallest weight that rounds below 1 (the stdvs span more than the 31 bits hold)."""
+    what = "signal_model"
+    mm = torch.as_tensor(means, dtype=torch.float64).cpu().reshape(-1).tolist()        # a list of Python floats keeps its 53 bits
+    ss = torch.as_tensor(stdvs, dtype=torch.float64).cpu().reshape(-1).tolist()
+    F, cb = int(frac_bits), int(cost_bits)
+    if len(mm) != len(ss) or len(mm) not in [4 ** k for k in range(1, MAX_K + 1)]:
+        raise ValueError("wavenet_speech_amd.%s: means and stdvs must both hold 4^k entries, k in [1, %d]" % (what, MAX_K))
+    if not 0 <= F <= MAX_FRAC_BITS or not 0 <= cb <= 16:
+        raise ValueError("wavenet_speech_amd.%s: frac_bits in [0, %d], cost_bits in [0, 16]" % (what, MAX_FRAC_BITS))
+    if not all(math.isfinite(m) for m in mm) or not all(math.isfinite(s) and s > 0 for s in ss):
+        raise ValueError("wavenet_speech_amd.%s: every mean must be finite and every stdv finite and positive "
+                         "(fit_kmer_model leaves NaN where a k-mer has no data: give it a prior)" % what)
+    sq = [Fraction(s) * (1 << F) for s in ss]                         # stdv 2^F, exact
+    smallest = min(sq)
+    S = next((S for S in range(MAX_WEIGHT_SHIFT, MIN_WEIGHT_SHIFT - 1, -1)
+              if round(Fraction(1 << (S + cb)) / (2 * smallest * smallest)) < 2 ** 31), None)
+    if S is None:
+        raise ValueError("wavenet_speech_amd.%s: the smallest stdv (%g) is too small for frac_bits = %d" % (what, min(ss), F))
+    rows = []
+    for m, s in zip(mm, sq):
+        level = round(Fraction(m) * (1 << F))
+        weight = round(Fraction(1 << (S + cb)) / (2 * s * s))
+        if abs(level) >= 2 ** 23 or weight < 1:
+            raise ValueError("wavenet_speech_amd.%s: a level at or beyond 2^23 or a weight below 1 (mean %g, stdv %g, weight_shift %d)"
+                             % (what, m, float(s) / (1 << F), S))
+        rows.append([level, weight, round((1 << cb) * math.log(float(s)))])
+    return SignalModel(torch.tensor(rows, dtype=torch.int64), S, F, cb)
+
+
+_AlignFields = namedtuple("SignalAlignment", "starts score band_hits states")
+
+
+class SignalAlignment(_AlignFields):
+    """starts [B, N + 1] int32: starts[b, j] is the first sample of state (k-mer) j, every entry past the read's last state is
+    signal_lengths[b] -- RaggedReads.starts' convention, so it goes into kmer_events(starts=...) as it is; score [B] int64: the cost
+    of the path, LLONG_MAX where there is no alignment (no state, or fewer samples than states) and LLONG_MIN for a bad read;
+    band_hits [B] int32: the samples whose state lies on the band's edge while the band could still have been wider there -- above 0
+    the band was too narrow for this read; states [B, L] int32 with want_states, else None: the state of every sample, -1 past the
+    read.  No alignment: starts and states -1, band_hits 0; a bad read: everything -1.  Device tensors.  k, first, frac_bits,
+    cost_bits and band of the call ride along as attributes."""
+
+    def __new__(cls, *fields, k=5, first=0, frac_bits=12, cost_bits=8, band=512):
+        self = super().__new__(cls, *fields)
+        self.k, self.first, self.frac_bits, self.cost_bits, self.band = int(k), int(first), int(frac_bits), int(cost_bits), int(band)
+        return self
+
+    @property
+    def nats(self):
+        """[B] float64: score / 2^cost_bits (+-inf-like sentinels stay huge: mask with score first)"""
+        return self.score.double() / float(1 << self.cost_bits)
+
+
+def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, band=512, scale_shift=None, max_cost=None,
+                 want_states=False):
+    """Align raw samples to the k-mers of known bases under a SignalModel: the minimum-cost path in which
+    every sample stays in its k-mer or steps to the next one (no skips: every k-mer holds at least one sample), inside a band of
+    `band` k-mers around the diagonal.
+
+    signal          [B, L] or [B, 1, L], float32 or int16; a view is passed by its row stride (unit stride along L)
+    signal_lengths  [B]; labels [B, n] bases in 1..4 (int32 or int64) with label_lengths [B]
+    model           a SignalModel (signal_model(means, stdvs), or filled by hand); its k and frac_bits are the call's
+    first           read b has label_lengths[b] - (k - 1) - 2 first states, state j the k-mer labels[j + first .. j + first + k);
+                    first = 2 / 0: the generator's "loader" / "generator" windows
+    band            a multiple of 64 in [64, 2048]; state j is allowed at sample t iff lo(t) <= j < lo(t) + band, lo(t) =
+                    clamp(((2 t + 1) N) // (2 T) - band / 2, 0, max(N - band, 0))
+    scale_shift     [B, 2] float32 or None, as kmer_events
+    max_cost        the clamp of a sample's quadratic term, in [1, 2^31 - 1] (None: 2^31 - 1): an outlier costs no more
+    want_states     also return the state of every sample
+    Integer arithmetic, ties to the stay, bitwise reproducible, no host synchronisation (capturable with fixed shapes once the
+    model has been used on the device).  A bad read (a length out of range, a label of the used window outside 1..4, a non-finite
+    or out-of-range sample before signal_lengths[b]) is reported through check_device_flags().  HIP only.  Returns
+    SignalAlignment."""
+    what = "signal_align"
+    signal = _rows(signal, (torch.float32, torch.int16), what, "signal")
+    dev = signal.device
+    if signal.dim() == 3 and signal.shape[1] == 1:
+        signal = signal[:, 0, :]
+    if signal.dim() != 2 or signal.shape[0] < 1 or signal.shape[1] < 1:
+        raise ValueError("wavenet_speech_amd.%s: signal must be [B, L] or [B, 1, L] with B, L >= 1, got %s" % (what, tuple(signal.shape)))
+    if signal.stride(1) != 1 and signal.shape[1] > 1 or signal.stride(0) < 0:
+        signal = signal.contiguous()
+    B, L = int(signal.shape[0]), int(signal.shape[1])
+    labels = _rows(labels, (torch.int32, torch.int64), what, "labels", dev)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 1:
+        raise ValueError("wavenet_speech_amd.%s: labels must be [%d, n >= 1], got %s" % (what, B, tuple(labels.shape)))
+    if labels.dtype != torch.int32:
+        labels = labels.int()
+    if labels.stride(1) != 1 and labels.shape[1] > 1 or labels.stride(0) < 0:
+        labels = labels.contiguous()
+    if not isinstance(model, SignalModel):
+        raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
+    first, band = int(first), int(band)
+    max_cost = 2 ** 31 - 1 if max_cost is None else int(max_cost)
+    if not 0 <= first <= MAX_FIRST or not MIN_BAND <= band <= MAX_BAND or band % 64 or not 1 <= max_cost <= 2 ** 31 - 1:
+        raise ValueError("wavenet_speech_amd.%s: first in [0, %d], band a multiple of 64 in [%d, %d], max_cost in [1, 2^31 - 1]"
+                         % (what, MAX_FIRST, MIN_BAND, MAX_BAND))
+    k = model.k
+    N = max(int(labels.shape[1]) - (k - 1) - 2 * first, 1)
+    if L > MAX_ALIGN_SIGNAL or N > MAX_ALIGN_EVENTS or B > 65535:
+        raise ValueError("wavenet_speech_amd.%s: at most 2^24 samples and 2^20 k-mers per read and 65535 reads" % what)
+    with torch.cuda.device(dev):
+        signal_lengths = _lengths(signal_lengths, B, dev, what, "signal_lengths")
+        label_lengths = _lengths(label_lengths, B, dev, what, "label_lengths")
+        if scale_shift is not None:
+            scale_shift = _rows(scale_shift, (torch.float32,), what, "scale_shift", dev)
+            if tuple(scale_shift.shape) != (B, 2):
+                raise ValueError("wavenet_speech_amd.%s: scale_shift must be [%d, 2], got %s" % (what, B, tuple(scale_shift.shape)))
+            scale_shift = scale_shift.contiguous()
+        lib = _lib.load()
+        from .functional import _p, _stream
+        table = model.on(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        starts = torch.empty(B, N + 1, **i32)
+        score = torch.empty(B, dtype=torch.int64, device=dev)
+        band_hits = torch.empty(B, **i32)
+        states = torch.empty(B, L, **i32) if want_states else None
+        bad = torch.zeros(1, **i32)
+        ws_bytes = lib.wn_signal_align_workspace_bytes(B, L, band)
+        if ws_bytes == 0:
+            _lib.check(-2, "wn_signal_align_workspace_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.wn_signal_align(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
+                                       _p(labels), labels.stride(0), _p(label_lengths), _p(table), B, L, int(labels.shape[1]), N, k, first,
+                                       model.frac_bits, model.weight_shift, max_cost, band, _p(starts), _p(score), _p(band_hits),
+                                       _p(states), _p(ws), ws_bytes, _p(bad), _stream()), "wn_signal_align")
+        _flags.WATCH.poll()
+        _flags.WATCH.note(bad, lambda n: "wavenet_speech_amd.signal_align: %d bad read(s): a length out of range, a label outside 1..4, "
+                          "a non-finite or out-of-range sample or a model row out of range" % n, at_once=False)
+    return SignalAlignment(starts, score, band_hits, states, k=k, first=first, frac_bits=model.frac_bits, cost_bits=model.cost_bits,
+                           band=band)
