@@ -4,8 +4,8 @@ import ctypes
 
 import pytest
 
-WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL, WN_ERR_WORKSPACE = 0, -1, -2, -3, -5
-FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below returns before it would be used
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE
+
 
 
 @pytest.fixture(scope="module")

@@ -33,6 +33,15 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == _declared_functions()
 
 
+def test_every_signature_row_matches_the_header():
+    """result type, argument count and every argument type of all of _lib.SIGNATURES, by the rule of tests/abi_util.py"""
+    from tests.abi_util import check_row
+    from wavenet_speech_amd import _lib
+    assert len(_lib.SIGNATURES) >= 106
+    for name in _lib.SIGNATURES:
+        check_row(name)
+
+
 def test_host_only_entry_points():
     from wavenet_speech_amd import _lib
     lib = _lib.load()

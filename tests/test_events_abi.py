@@ -2,14 +2,11 @@
 argument, and every host-side rejection in its documented order (shape, unsupported, NULL, workspace).  The pointers are fakes:
 every call below returns before anything would be launched -- none of them touches a device."""
 import ctypes
-import os
-import re
 
 import pytest
 
-WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL, WN_ERR_WORKSPACE = 0, -1, -2, -3, -5
-FAKE = ctypes.c_void_p(1 << 20)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row, header_names
+
 NAME = "wn_kmer_events"
 ARGS = ["signal", "signal_kind", "signal_stride", "signal_lengths", "scale_shift", "seg_begin", "seg_end", "seg_row_stride",
         "seg_elem_stride", "frame_stride", "frame_offset", "labels", "labels_stride", "label_lengths", "events", "batch", "max_signal",
@@ -32,27 +29,10 @@ def test_events_symbols_are_exported(lib):
     assert lib.wn_version() == 300                                   # an additive entry point
 
 
-def _header_row(name):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wavenet_amd.h")).read(), flags=re.S)
-    m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, name
-    return m.group(1).strip(), [" ".join(p.split()) for p in m.group(2).split(",")]
-
-
 def test_signature_rows_match_the_header():
-    from wavenet_speech_amd import _lib
-    kinds = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
     for name, count in ((NAME, 35), (NAME + "_workspace_bytes", 2)):
-        res_text, params = _header_row(name)
-        res, args = _lib.SIGNATURES[name]
-        assert res is kinds[res_text]
-        assert len(params) == len(args) == count, (len(params), len(args))
-        for p, ctype in zip(params, args):
-            if "*" in p or p.startswith("wn_stream_t"):
-                assert ctype is ctypes.c_void_p, p
-            else:
-                assert ctype is kinds[p.rsplit(" ", 1)[0]], p
-    names = [p.replace("*", " ").split()[-1] for p in _header_row(NAME)[1]]
+        check_row(name, count=count, opaque=True)
+    names = header_names(NAME)
     assert names == ARGS
 
 

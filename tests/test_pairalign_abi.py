@@ -2,14 +2,11 @@
 workspace formula, and the shape / limit / pointer checks, which run on the host before any HIP call -- none of the calls
 below touches a device."""
 import ctypes
-import os
-import re
 
 import pytest
 
-WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL, WN_ERR_WORKSPACE = 0, -1, -2, -3, -5
-FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below returns before it would be used
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row
+
 
 
 @pytest.fixture(scope="module")
@@ -27,21 +24,8 @@ def test_pair_align_symbols_are_exported(lib):
 
 
 def test_signature_table_matches_the_header():
-    from wavenet_speech_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wavenet_amd.h")).read(), flags=re.S)
-    kinds = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
     for name in ("wn_pair_align_workspace_bytes", "wn_pair_align"):
-        m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-        assert m, name
-        res, args = _lib.SIGNATURES[name]
-        assert res is kinds[m.group(1).strip()]
-        params = [" ".join(p.split()) for p in m.group(2).split(",")]
-        assert len(params) == len(args), (name, len(params), len(args))
-        for p, ctype in zip(params, args):
-            if "*" in p or p.startswith("wn_stream_t"):
-                assert ctype is ctypes.c_void_p, (name, p)
-            else:
-                assert ctype is kinds[p.rsplit(" ", 1)[0]], (name, p)
+        check_row(name, opaque=True)
 
 
 def _want_bytes(B, N, M):

@@ -1,14 +1,10 @@
 """CPU: the C ABI of the quality profile (csrc/wn_profile.hip): the exported symbol, the ctypes row against the header, and the
 shape / limit / pointer checks, which run on the host before any HIP call -- none of the calls below touches a device."""
-import ctypes
-import os
-import re
 
 import pytest
 
-WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL = 0, -1, -2, -3
-FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below returns before it would be used
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+
 NAME = "wn_quality_profile"
 OUTPUTS = ("q_counts", "dwell_counts", "confusion", "read_counts", "outcome", "ref_index")
 
@@ -27,21 +23,8 @@ def test_profile_symbol_is_exported(lib):
 
 
 def test_signature_row_matches_the_header():
-    from wavenet_speech_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wavenet_amd.h")).read(), flags=re.S)
-    kinds = {"int": ctypes.c_int, "long long": ctypes.c_longlong}
-    m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % NAME, src)
-    assert m
-    res, args = _lib.SIGNATURES[NAME]
-    assert res is kinds[m.group(1).strip()]
-    params = [" ".join(p.split()) for p in m.group(2).split(",")]
-    assert len(params) == len(args) == 27, (len(params), len(args))
-    for p, ctype in zip(params, args):
-        if "*" in p or p.startswith("wn_stream_t"):
-            assert ctype is ctypes.c_void_p, p
-        else:
-            assert ctype is kinds[p.rsplit(" ", 1)[0]], p
-    names = [p.replace("*", " ").split()[-1] for p in params]
+    check_row(NAME, count=27, opaque=True)
+    names = header_names(NAME)
     assert names == ["ops", "ops_stride", "ops_len", "ref", "ref_stride", "ref_lengths", "query", "query_stride", "query_lengths",
                      "qual", "qual_stride", "dwell", "dwell_stride", "batch", "max_ref_len", "max_query_len", "max_ops", "classes",
                      "count_ends", "q_counts", "dwell_counts", "confusion", "read_counts", "outcome", "ref_index", "bad", "stream"]

@@ -1,14 +1,10 @@
 """CPU: the C ABI of the per-base qualities (csrc/wn_quality.hip): the exported symbol, the ctypes row against the header, and
 the shape / limit / pointer checks, which run on the host before any HIP call -- none of the calls below touches a device."""
-import ctypes
-import os
-import re
 
 import pytest
 
-WN_OK, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, WN_ERR_NULL = 0, -1, -2, -3
-FAKE = ctypes.c_void_p(1 << 20)          # never dereferenced: every call below returns before it would be used
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+
 NAME = "wn_ctc_base_quality"
 INF, NAN = float("inf"), float("nan")
 
@@ -27,21 +23,8 @@ def test_quality_symbol_is_exported(lib):
 
 
 def test_signature_row_matches_the_header():
-    from wavenet_speech_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wavenet_amd.h")).read(), flags=re.S)
-    kinds = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
-    m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % NAME, src)
-    assert m
-    res, args = _lib.SIGNATURES[NAME]
-    assert res is kinds[m.group(1).strip()]
-    params = [" ".join(p.split()) for p in m.group(2).split(",")]
-    assert len(params) == len(args) == 25, (len(params), len(args))
-    for p, ctype in zip(params, args):
-        if "*" in p or p.startswith("wn_stream_t"):
-            assert ctype is ctypes.c_void_p, p
-        else:
-            assert ctype is kinds[p.rsplit(" ", 1)[0]], p
-    names = [p.replace("*", " ").split()[-1] for p in params]
+    check_row(NAME, count=25, opaque=True)
+    names = header_names(NAME)
     assert names == ["x", "sb", "sc", "st", "input_kind", "input_lengths", "labels", "labels_stride", "frames", "frames_stride",
                      "lengths", "batch", "classes", "length", "max_labels", "blank", "stat", "qscale", "qbias", "error", "qual",
                      "dwell", "read_error", "bad", "stream"]

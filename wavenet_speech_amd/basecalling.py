@@ -23,13 +23,13 @@ Gather (raw samples -> chunk rows) and stitch (kept frames -> [B, C, Tmax]) are 
 host arithmetic, so the read lengths are needed on the host: lengths given as a device tensor cost one read-back per call,
 like the max() of ragged_reads(pad_to=None).  There is no CPU fallback: CPU tensors raise.
 """
-import ctypes
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import _flags, _lib, series
+from . import _args, _flags, _lib, series
+from ._args import _p, _stream
 from .decoding import ctc_base_qualities, ctc_beam_decode, ctc_greedy_decode, pairwise_align, quality_profile
 from .modules.block import freeze_for_inference
 from .modules.raw_ctcnet import RawCTCNet
@@ -116,19 +116,8 @@ def _plan(signal_lengths, chunk, left, right, feature_kwidth, capacity, multiple
                      torch.from_numpy(per_read.astype(np.int32)))
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _need(t, name, dtypes, what, dense=True):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
-    if t.dtype not in dtypes:
-        raise TypeError("wavenet_speech_amd.%s: %s must be %s, got %s" % (what, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    _args.gpu_tensor(t, what, name, dtypes, TypeError)
     if dense and not t.is_contiguous():
         raise ValueError("wavenet_speech_amd.%s: %s must be contiguous" % (what, name))
 
@@ -153,8 +142,8 @@ def chunk_gather(signal, signal_lengths, plan, chunk, out, scale=None, shift=Non
     B, ld = int(signal.shape[0]), int(signal.shape[1])
     if signal_lengths.shape != (B,) or any(t is not None and t.shape != (B,) for t in (scale, shift)):
         raise ValueError("wavenet_speech_amd.%s: signal_lengths, scale and shift must have shape (%d,)" % (what, B))
-    _lib.check(_lib.load().wn_chunk_gather(_ptr(signal), int(signal.dtype == torch.int16), B, ld, _ptr(signal_lengths), _ptr(scale),
-                                           _ptr(shift), _ptr(plan), int(plan.shape[0]), int(chunk), _ptr(out), _ptr(bad), _stream()),
+    _lib.check(_lib.load().wn_chunk_gather(_p(signal), int(signal.dtype == torch.int16), B, ld, _p(signal_lengths), _p(scale),
+                                           _p(shift), _p(plan), int(plan.shape[0]), int(chunk), _p(out), _p(bad), _stream()),
                "wn_chunk_gather")
 
 
@@ -173,9 +162,9 @@ def chunk_stitch(y, plan, out, frame_lengths, bad=None):
         raise ValueError("wavenet_speech_amd.%s: need y [N, C, Ty], plan [N, %d], out [B, C, Tmax] with unit stride in time and "
                          "frame_lengths [B], got %s, %s, %s, %s" % (what, PLAN_INTS, tuple(y.shape), tuple(plan.shape), tuple(out.shape),
                                                                     tuple(frame_lengths.shape)))
-    _lib.check(_lib.load().wn_chunk_stitch(_ptr(y), y.stride(0), y.stride(1), y.stride(2), int(y.shape[2]), _ptr(plan),
-                                           int(plan.shape[0]), int(y.shape[1]), int(out.shape[0]), _ptr(out), out.stride(0),
-                                           out.stride(1), int(out.shape[2]), _ptr(frame_lengths), _ptr(bad), _stream()),
+    _lib.check(_lib.load().wn_chunk_stitch(_p(y), y.stride(0), y.stride(1), y.stride(2), int(y.shape[2]), _p(plan),
+                                           int(plan.shape[0]), int(y.shape[1]), int(out.shape[0]), _p(out), out.stride(0),
+                                           out.stride(1), int(out.shape[2]), _p(frame_lengths), _p(bad), _stream()),
                "wn_chunk_stitch")
 
 

@@ -247,12 +247,10 @@ static int check_align(int batch, int classes, int length, int max_label_len) {
     if ((double)batch * (double)length >= 2147483648.0) return WN_ERR_UNSUPPORTED;
     return WN_OK;
 }
-static int align_sp(int max_label_len) { return (2 * max_label_len + 1 + 63) / 64 * 64; }
-
 // workspace: backpointers, 2 bits per state, [B][T][Sp / 4] bytes (Sp a multiple of 64: every row a multiple of 16 bytes)
 size_t wn_ctc_align_workspace_bytes(int batch, int classes, int length, int max_label_len) {
     if (check_align(batch, classes, length, max_label_len) != WN_OK) return 0;
-    return (size_t)batch * (size_t)length * (size_t)(align_sp(max_label_len) / 4);
+    return (size_t)batch * (size_t)length * (size_t)(ctc_states_padded(max_label_len) / 4);
 }
 
 int wn_ctc_align(const float* x, long long sb, long long sc, long long st, int input_kind, const long long* labels,
@@ -271,7 +269,7 @@ int wn_ctc_align(const float* x, long long sb, long long sc, long long st, int i
     a.states = states; a.frame_labels = frame_labels; a.spans = spans; a.score = score; a.bad = bad;
     a.bp = reinterpret_cast<unsigned short*>(workspace);
     a.B = batch; a.C = classes; a.T = length; a.Lmax = max_label_len; a.blank = blank; a.kind = input_kind;
-    a.row_threads = align_sp(max_label_len) / kAlnPer;
+    a.row_threads = ctc_states_padded(max_label_len) / kAlnPer;
     const int threads = (a.row_threads + 63) / 64 * 64;                  // 64 (one wave, no barrier per step) up to 512
     const size_t lds = (size_t)kAlnChunk * classes * sizeof(double);
     hipStream_t s = (hipStream_t)stream;

@@ -283,12 +283,10 @@ static int check_ctc(int batch, int classes, int length, int max_label_len, int 
     if ((double)batch * (double)length >= 2147483648.0) return WN_ERR_UNSUPPORTED;
     return WN_OK;
 }
-static int ctc_sp(int max_label_len) { return (2 * max_label_len + 1 + 63) / 64 * 64; }
-
 size_t wn_ctc_workspace_bytes(int batch, int classes, int length, int max_label_len) {
     if (check_ctc(batch, classes, length, max_label_len, 0) != WN_OK) return 0;
     const size_t rows = (size_t)batch * (size_t)length;
-    return rows * 8 /* lse */ + 2 * rows * (size_t)ctc_sp(max_label_len) * 8 /* alpha, beta */ + (size_t)batch * 8 /* nll */ + 256;
+    return rows * 8 /* lse */ + 2 * rows * (size_t)ctc_states_padded(max_label_len) * 8 /* alpha, beta */ + (size_t)batch * 8 /* nll */ + 256;
 }
 
 int wn_ctc_loss(const float* logits, const long long* labels, const long long* label_lengths, const long long* input_lengths,
@@ -301,7 +299,7 @@ int wn_ctc_loss(const float* logits, const long long* labels, const long long* l
     if (reinterpret_cast<uintptr_t>(workspace) & 7) return WN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t rows = (size_t)batch * (size_t)length;
-    const int Sp = ctc_sp(max_label_len);
+    const int Sp = ctc_states_padded(max_label_len);
     CtcArgs a;
     a.x = logits; a.labels = labels; a.label_len = label_lengths; a.input_len = input_lengths;
     double* w = reinterpret_cast<double*>(workspace);

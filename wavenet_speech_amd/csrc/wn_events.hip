@@ -21,20 +21,17 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_signal_dev.h"
 
 namespace wn {
 
 constexpr int kEvThreads = 256;
 constexpr int kEvShort = 32;                  // up to here one lane sums the event; above, the whole wave
 constexpr int kEvMaxLen = 65536;              // samples per event: sum of q^2 < 2^16 * 2^46 = 2^62
-constexpr int kEvMaxK = 6;
-constexpr int kEvMaxFirst = 8;
-constexpr int kEvMaxFrac = 20;
 constexpr int kEvMaxDwell = 65536;
 constexpr int kEvLdsK = 5;                    // kmer_stats lives in LDS up to this k
 constexpr long long kEvTableChunk = 4096;     // events per workgroup of the second launch, at least
 constexpr int kEvTableBlocks = 256;           // workgroups of the second launch, at most
-constexpr double kEvQLimit = 8388608.0;       // |q| < 2^23
 
 struct EventArgs {
     const void* signal;
@@ -65,17 +62,6 @@ struct EventArgs {
     int* counts;                        // workspace: [B][4]
     int* bad;
 };
-
-// q = llrint(v 2^F), v = x scale + shift in double with one rounding; false for a non-finite v or |q| >= 2^23
-template <typename T>
-__device__ __forceinline__ bool quantise(T x, bool scaled, double scale, double shift, double two_f, int* q) {
-    double v = (double)x;
-    if (scaled) v = __fma_rn(v, scale, shift);
-    const double r = rint(v * two_f);                                // ties to even; a power-of-two product is exact
-    if (!(fabs(r) < kEvQLimit)) return false;                        // NaN and inf fail the comparison
-    *q = (int)r;
-    return true;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kEvThreads) void kmer_events_kernel(const EventArgs a) {
@@ -111,13 +97,9 @@ __global__ __launch_bounds__(kEvThreads) void kmer_events_kernel(const EventArgs
             } else if (w0 < 0 || w0 + a.k > ll) {
                 code = -1;
             } else {
-                const int* lab = a.labels + (long long)b * a.labels_stride + w0;
-                int idx = 0;
-                for (int i = 0; i < a.k; ++i) {
-                    const int v = lab[i];
-                    if (v < 1 || v > 4) bad = true;
-                    idx = idx * 4 + ((v - 1) & 3);
-                }
+                bool labels_ok = true;
+                const int idx = kmer_code(a.labels + (long long)b * a.labels_stride + w0, a.k, &labels_ok);
+                bad = !labels_ok;
                 code = bad ? -4 : idx;
             }
         }
@@ -254,14 +236,14 @@ int wn_kmer_events(const void* signal, int signal_kind, long long signal_stride,
     if (batch < 1 || max_events < 1 || max_signal < 1 || max_labels < 1) return WN_ERR_BAD_SHAPE;
     if (signal_stride < 0 || seg_row_stride < 0 || seg_elem_stride < 0 || labels_stride < 0) return WN_ERR_BAD_SHAPE;
     if (frame_stride < 1 || frame_offset < 0 || signal_kind < 0 || signal_kind > 1) return WN_ERR_BAD_SHAPE;
-    if (k < 1 || k > kEvMaxK || first < -kEvMaxFirst || first > kEvMaxFirst) return WN_ERR_UNSUPPORTED;
-    if (frac_bits < 0 || frac_bits > kEvMaxFrac || max_dwell < 1 || max_dwell > kEvMaxDwell) return WN_ERR_UNSUPPORTED;
+    if (k < 1 || k > kSigMaxK || first < -kSigMaxFirst || first > kSigMaxFirst) return WN_ERR_UNSUPPORTED;
+    if (frac_bits < 0 || frac_bits > kSigMaxFrac || max_dwell < 1 || max_dwell > kEvMaxDwell) return WN_ERR_UNSUPPORTED;
     if (batch > 65535 || (long long)max_signal * frame_stride >= (1ll << 31)) return WN_ERR_UNSUPPORTED;
     if (!signal || !signal_lengths || !seg_begin || !seg_end || !labels || !label_lengths || !events) return WN_ERR_NULL;
     if (!workspace) return WN_ERR_NULL;                              // the per-read flags live there: tables or not
     if (!ev_kmer && !ev_start && !ev_len && !ev_sum && !ev_sumsq && !read_counts && !kmer_stats && !dwell_hist) return WN_ERR_NULL;
     if (workspace_bytes < wn_kmer_events_workspace_bytes(batch, max_events) || ((size_t)workspace & 15)) return WN_ERR_WORKSPACE;
-    if (((size_t)signal & (signal_kind ? 1 : 3)) != 0) return WN_ERR_WORKSPACE;
+    if (!signal_aligned(signal, signal_kind)) return WN_ERR_WORKSPACE;
 
     const size_t rows = (size_t)batch * (size_t)max_events;
     char* ws = (char*)workspace;

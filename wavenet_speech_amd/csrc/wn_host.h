@@ -86,6 +86,8 @@ inline int cp8(int c) { return rup(c, 8); }      // channel rows of an fp32 seri
 inline int cp32(int c) { return rup(c, 32); }    // channels of a half series
 inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 inline bool half_prec(int p) { return p == WN_F16X3 || p == WN_F16 || p == WN_BF16; }
+// states of the blank-extended labelling of the CTC loss and the forced alignment, 2 L + 1, in whole waves
+inline int ctc_states_padded(int max_label_len) { return (2 * max_label_len + 1 + 63) / 64 * 64; }
 
 // column offsets of the k taps of a dilated conv: tap j reads x[t + off[j]]
 inline void tap_offsets(int k, int d, int causal, int* off) {

@@ -26,6 +26,7 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_signal_dev.h"
 
 namespace wn {
 
@@ -35,14 +36,10 @@ constexpr int kSaSamples = 1024;              // samples quantised into LDS at a
 constexpr int kSaCodes = 256;                 // k-mer codes staged for the states that enter the band next
 constexpr int kSaTrace = 64;                  // samples walked at a time by the trace
 constexpr int kSaWinBytes = kSaTrace / 8 + 1; // backpointer bytes per sample of a trace window
-constexpr int kSaMaxK = 6;
-constexpr int kSaMaxFirst = 8;
-constexpr int kSaMaxFrac = 20;
 constexpr int kSaMinBand = 64;
 constexpr int kSaMaxBand = 2048;
 constexpr int kSaMaxSignal = 1 << 24;
 constexpr int kSaMaxEvents = 1 << 20;
-constexpr int kSaQLimit = 1 << 23;            // |q| and |level| stay below
 constexpr int kSaOffsetLimit = 1 << 30;
 constexpr long long kSaInf = 1ll << 62;       // a path's cost stays below 2^24 (2^31 + 2^30) < 2^56
 constexpr long long kSaNoAlignment = 0x7fffffffffffffffll;
@@ -66,17 +63,6 @@ struct SigAlignArgs {
     int* bad;
 };
 
-// q = llrint(v 2^F), v = x scale + shift in double with one rounding; false for a non-finite v or |q| >= 2^23 (section 7j's)
-template <typename T>
-__device__ __forceinline__ bool sa_quantise(T x, bool scaled, double scale, double shift, double two_f, int* q) {
-    double v = (double)x;
-    if (scaled) v = __fma_rn(v, scale, shift);
-    const double r = rint(v * two_f);                                // ties to even; a power-of-two product is exact
-    if (!(fabs(r) < (double)kSaQLimit)) return false;                // NaN and inf fail the comparison
-    *q = (int)r;
-    return true;
-}
-
 // min((d d weight) >> S, max_cost) + offset with d = |q - level| < 2^24: the 79-bit product in two 64-bit halves
 __device__ __forceinline__ long long sa_sample_cost(int q, int level, int weight, int offset, int S, int max_cost) {
     const int df = q - level;
@@ -91,21 +77,10 @@ __device__ __forceinline__ long long sa_sample_cost(int q, int level, int weight
     return c + offset;
 }
 
-// the k-mer index of the window lab[0 .. k), first base most significant; a label outside 1..4 clears *ok and counts as 1
-__device__ __forceinline__ int sa_state_code(const int* lab, int k, bool* ok) {
-    int idx = 0;
-    for (int i = 0; i < k; ++i) {
-        const int v = lab[i];
-        if (v < 1 || v > 4) *ok = false;
-        idx = idx * 4 + ((v - 1) & 3);
-    }
-    return idx;
-}
-
 // the model row of a k-mer that the path can use; a row out of range clears *ok and is replaced by (0, 1, 0)
 __device__ __forceinline__ void sa_model_row(const int* model, int code, int* level, int* weight, int* offset, bool* ok) {
     const int l = model[3 * code], w = model[3 * code + 1], o = model[3 * code + 2];
-    const bool good = w >= 1 && l > -kSaQLimit && l < kSaQLimit && o > -kSaOffsetLimit && o < kSaOffsetLimit;
+    const bool good = w >= 1 && l > -kSigQLimit && l < kSigQLimit && o > -kSaOffsetLimit && o < kSaOffsetLimit;
     if (!good) *ok = false;
     *level = good ? l : 0;
     *weight = good ? w : 1;
@@ -169,7 +144,7 @@ __global__ __launch_bounds__(kSaMaxThreads) void signal_align_kernel(const SigAl
         lvl[i] = 0; wgt[i] = 1; off[i] = 0;
         d[i] = kSaInf;
         if (tid < nact && j < N) {                                   // j + k <= N + k - 1 = Lb - 2 first: inside the labels
-            const int code = sa_state_code(lab + j, k, &ok);
+            const int code = kmer_code(lab + j, k, &ok);
             sa_model_row(s_model, code, &lvl[i], &wgt[i], &off[i], &ok);
             alive |= 1u << i;
         }
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(kSaMaxThreads) void signal_align_kernel(const SigAl
         if (ks == 0) {                                               // the barrier of step t - 1: the old chunk is no longer read
             for (int i = tid; i < kSaSamples && t + i < Tb; i += nthr) {
                 int q = 0;
-                if (!sa_quantise(sig[t + i], scaled, scale, shift, a.two_f, &q)) { ok = false; q = 0; }
+                if (!quantise(sig[t + i], scaled, scale, shift, a.two_f, &q)) { ok = false; q = 0; }
                 s_q[i] = q;
             }
             __syncthreads();
@@ -211,7 +186,7 @@ __global__ __launch_bounds__(kSaMaxThreads) void signal_align_kernel(const SigAl
                     for (int i = tid; i < kSaCodes; i += nthr) {
                         const long long j = (long long)W + r + i;
                         int code = 0;
-                        if (j < N) code = sa_state_code(lab + j, k, &ok);
+                        if (j < N) code = kmer_code(lab + j, k, &ok);
                         s_code[i] = code;
                     }
                     __syncthreads();
@@ -334,14 +309,14 @@ int wn_signal_align(const void* signal, int signal_kind, long long signal_stride
                     int* bad, wn_stream_t stream) {
     if (batch < 1 || max_signal < 1 || max_labels < 1 || max_events < 1) return WN_ERR_BAD_SHAPE;
     if (signal_stride < 0 || labels_stride < 0 || signal_kind < 0 || signal_kind > 1) return WN_ERR_BAD_SHAPE;
-    if (k < 1 || k > kSaMaxK || first < 0 || first > kSaMaxFirst || frac_bits < 0 || frac_bits > kSaMaxFrac) return WN_ERR_UNSUPPORTED;
+    if (k < 1 || k > kSigMaxK || first < 0 || first > kSigMaxFirst || frac_bits < 0 || frac_bits > kSigMaxFrac) return WN_ERR_UNSUPPORTED;
     if (weight_shift < 16 || weight_shift > 63 || max_cost < 1) return WN_ERR_UNSUPPORTED;
     if (band < kSaMinBand || band > kSaMaxBand || band % 64 != 0) return WN_ERR_UNSUPPORTED;
     if (batch > 65535 || max_signal > kSaMaxSignal || max_events > kSaMaxEvents) return WN_ERR_UNSUPPORTED;
     if (!signal || !signal_lengths || !labels || !label_lengths || !model || !starts || !score || !band_hits || !workspace)
         return WN_ERR_NULL;
     if (workspace_bytes < wn_signal_align_workspace_bytes(batch, max_signal, band) || ((size_t)workspace & 15)) return WN_ERR_WORKSPACE;
-    if (((size_t)signal & (signal_kind ? 1 : 3)) != 0) return WN_ERR_WORKSPACE;
+    if (!signal_aligned(signal, signal_kind)) return WN_ERR_WORKSPACE;
 
     SigAlignArgs a = {};
     a.signal = signal; a.signal_lengths = signal_lengths; a.scale_shift = scale_shift; a.labels = labels;

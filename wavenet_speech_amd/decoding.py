@@ -31,7 +31,8 @@ from collections import namedtuple
 
 import torch
 
-from . import _flags, _lib
+from . import _args, _lib
+from ._args import _p, _stream
 
 MAX_CLASSES = 64
 MAX_BEAM_WIDTH = 64
@@ -42,15 +43,13 @@ DEFAULT_ALPHABET = " AGCT"          # the reference's lookup (Decoder.py:26): 0 
 
 
 def _prep(x, layout, input_lengths, what):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: needs a GPU tensor (there is no CPU fallback)" % what)
+    x = _args.gpu_tensor(x, what, "input")
     if x.dim() != 3:
         raise ValueError("wavenet_speech_amd.%s: input must be 3-d, got shape %s" % (what, tuple(x.shape)))
     if layout not in LAYOUTS:
         raise ValueError("wavenet_speech_amd.%s: layout must be one of %s, got %r" % (what, LAYOUTS, layout))
     if not x.is_floating_point():
         raise TypeError("wavenet_speech_amd.%s: input must be floating point, got %s" % (what, x.dtype))
-    x = x.detach()
     if x.dtype != torch.float32:
         x = x.float()
     if layout == "BCT":
@@ -74,9 +73,8 @@ def _prep(x, layout, input_lengths, what):
 
 
 def _note(bad, C, blank, what):
-    _flags.WATCH.poll()
-    _flags.WATCH.note(bad, lambda n, C=C, blank=blank: "wavenet_speech_amd.%s: input_lengths outside [0, T] or blank (%d) outside "
-                      "[0, %d) in %d utterance(s)" % (what, blank, C, n), at_once=False)
+    _args.note_bad(bad, lambda n, C=C, blank=blank: "wavenet_speech_amd.%s: input_lengths outside [0, T] or blank (%d) outside "
+                   "[0, %d) in %d utterance(s)" % (what, blank, C, n))
 
 
 def ctc_greedy_decode(x, blank=0, input_lengths=None, layout="BCT"):
@@ -85,7 +83,6 @@ def ctc_greedy_decode(x, blank=0, input_lengths=None, layout="BCT"):
     same.  Returns (labels [B, T] int32 zero-padded, lengths [B] int32, frames [B, T] int32: the frame of each label)."""
     x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, "ctc_greedy_decode")
     lib = _lib.load()
-    from .functional import _p, _stream
     dev = x.device
     with torch.cuda.device(dev):
         labels = torch.empty(B, T, dtype=torch.int32, device=dev)
@@ -112,7 +109,6 @@ def ctc_beam_decode(x, beam_width, blank=0, input_lengths=None, input="logits", 
         raise ValueError("wavenet_speech_amd.ctc_beam_decode: beam_width must be in [1, %d], got %d" % (MAX_BEAM_WIDTH, W))
     x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, "ctc_beam_decode")
     lib = _lib.load()
-    from .functional import _p, _stream
     dev = x.device
     with torch.cuda.device(dev):
         ws_bytes = lib.wn_ctc_decode_workspace_bytes(B, C, T, W)
@@ -167,7 +163,6 @@ def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, in
     if lmax == 0:                                                    # the C ABI wants one column; no utterance may use it
         lmax, targets = 1, torch.zeros(B, 1, dtype=torch.int64, device=dev)
     lib = _lib.load()
-    from .functional import _p, _stream
     with torch.cuda.device(dev):
         ws_bytes = lib.wn_ctc_align_workspace_bytes(B, C, T, lmax)
         if ws_bytes == 0:
@@ -182,9 +177,8 @@ def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, in
         _lib.check(lib.wn_ctc_align(_p(x), sb, sc, st, INPUT_KINDS[input], _p(targets), _p(target_lengths), _p(in_len), B, C, T, lmax,
                                     int(blank), _p(states), _p(frame_labels), _p(spans), _p(score), _p(ws), ws_bytes, _p(bad),
                                     _stream()), "wn_ctc_align")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_forced_align: labels outside [0, %d), equal to "
-                          "the blank (%d), or lengths out of range in %d utterance(s)" % (C, blank, n), at_once=False)
+        _args.note_bad(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_forced_align: labels outside [0, %d), equal to "
+                       "the blank (%d), or lengths out of range in %d utterance(s)" % (C, blank, n))
     return CTCAlignment(states, frame_labels, spans[:, :width], score)
 
 
@@ -207,24 +201,9 @@ class PairwiseAlignment(namedtuple("PairwiseAlignment", "score matches mismatche
 
 
 def _pair_rows(rows, lengths, what, name):
-    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
-    if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 2:
-        raise ValueError("wavenet_speech_amd.%s: %s must be int32 or int64 of shape (B, n), got %s %s"
-                         % (what, name, rows.dtype, tuple(rows.shape)))
-    B = int(rows.shape[0])
-    lengths = torch.as_tensor(lengths)
-    if lengths.is_floating_point() or lengths.dtype == torch.bool or lengths.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: %s_lengths must be integers of shape (%d,), got %s %s"
-                         % (what, name, B, lengths.dtype, tuple(lengths.shape)))
-    rows = rows.detach()
-    if rows.dtype != torch.int32:
-        rows = rows.to(torch.int32)                                  # on the device; labels are compared for equality only
-    if rows.shape[1] == 0:                                           # the C ABI wants one column; no pair may use it
-        rows = torch.zeros(B, 1, dtype=torch.int32, device=rows.device)
-    if rows.stride(1) != 1:
-        rows = rows.contiguous()
-    return rows, lengths.to(device=rows.device, dtype=torch.int32).contiguous()
+    """label rows of any width (none: one unused column; labels are compared for equality only) with their [B] lengths"""
+    rows = _args.int_rows(rows, what, name, pad_empty=True, lone_column_in_place=False)
+    return rows, _args.lengths(lengths, int(rows.shape[0]), rows.device, what, name + "_lengths")
 
 
 def _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_free, want_stats, want_ops):
@@ -239,7 +218,6 @@ def _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_fr
         raise ValueError("wavenet_speech_amd.%s: at most %d reference and %d query labels per pair, got %d and %d"
                          % (what, MAX_PAIR_REF, MAX_PAIR_QUERY, N, M))
     lib = _lib.load()
-    from .functional import _p, _stream
     dev = ref.device
     with torch.cuda.device(dev):
         score = torch.empty(B, dtype=torch.int32, device=dev)
@@ -256,9 +234,8 @@ def _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_fr
         _lib.check(lib.wn_pair_align(_p(ref), ref.stride(0), _p(ref_lengths), _p(query), query.stride(0), _p(query_lengths), B, N, M,
                                      costs[0], costs[1], costs[2], costs[3], int(bool(end_gaps_free)), _p(score), _p(stats), _p(ops),
                                      _p(ops_len), _p(ws), ws_bytes, _p(bad), _stream()), "wn_pair_align")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n, N=N, M=M: "wavenet_speech_amd.%s: ref_lengths outside [0, %d] or query_lengths outside "
-                          "[0, %d] in %d pair(s)" % (what, N, M, n), at_once=False)
+        _args.note_bad(bad, lambda n, N=N, M=M: "wavenet_speech_amd.%s: ref_lengths outside [0, %d] or query_lengths outside "
+                       "[0, %d] in %d pair(s)" % (what, N, M, n))
     return score, stats, ops, ops_len
 
 
@@ -330,20 +307,6 @@ BaseQualities.__doc__ = """error [B, Lmax] fp32: the error probability of every 
 the read's bases (NaN for an empty read); mean_qscore [B] fp32: qscale (-10 log10 read_error) + qbias.  All on the device."""
 
 
-def _label_rows(rows, B, what, name):
-    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
-    if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 2 or rows.shape[0] != B:
-        raise ValueError("wavenet_speech_amd.%s: %s must be int32 or int64 of shape (%d, Lmax), got %s %s"
-                         % (what, name, B, rows.dtype, tuple(rows.shape)))
-    rows = rows.detach()
-    if rows.dtype != torch.int32:
-        rows = rows.to(torch.int32)
-    if rows.shape[1] > 1 and rows.stride(1) != 1 or rows.stride(0) < 0:
-        rows = rows.contiguous()                                     # a row stride is read in place: labels[:, 0] of a beam search
-    return rows
-
-
 def ctc_base_qualities(x, labels, lengths, frames, input_lengths=None, blank=0, input="logits", layout="BCT", stat="mean",
                        qscale=1.0, qbias=0.0):
     """A Phred quality for every decoded base and a mean error per read.
@@ -368,22 +331,17 @@ def ctc_base_qualities(x, labels, lengths, frames, input_lengths=None, blank=0, 
     x, (B, C, T), (sb, sc, st), in_len = _prep(x, layout, input_lengths, what)
     if not 0 <= int(blank) < C:
         raise ValueError("wavenet_speech_amd.%s: blank must be in [0, %d), got %d" % (what, C, int(blank)))
-    labels, frames = _label_rows(labels, B, what, "labels"), _label_rows(frames, B, what, "frames")
+    labels, frames = (_args.int_rows(r, what, name, B=B, shape="(%d, Lmax)" % B) for r, name in ((labels, "labels"), (frames, "frames")))
     if labels.device != x.device or frames.device != x.device or labels.shape != frames.shape:
         raise ValueError("wavenet_speech_amd.%s: labels and frames must have one shape, on the device of the input" % what)
     lmax = width = int(labels.shape[1])
     if lmax > T:
         raise ValueError("wavenet_speech_amd.%s: at most one label per frame: Lmax = %d, T = %d" % (what, lmax, T))
-    lengths = torch.as_tensor(lengths)
-    if lengths.is_floating_point() or lengths.dtype == torch.bool or lengths.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: lengths must be integers of shape (%d,), got %s %s"
-                         % (what, B, lengths.dtype, tuple(lengths.shape)))
     dev = x.device
-    lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    lengths = _args.lengths(lengths, B, dev, what, "lengths")
     if lmax == 0:                                                    # the C ABI wants one column; no read may use it
         lmax, labels, frames = 1, torch.zeros(B, 1, dtype=torch.int32, device=dev), torch.zeros(B, 1, dtype=torch.int32, device=dev)
     lib = _lib.load()
-    from .functional import _p, _stream
     with torch.cuda.device(dev):
         error = torch.empty(B, lmax, dtype=torch.float32, device=dev)
         qual = torch.empty(B, lmax, dtype=torch.uint8, device=dev)
@@ -394,10 +352,9 @@ def ctc_base_qualities(x, labels, lengths, frames, input_lengths=None, blank=0, 
                                            frames.stride(0), _p(lengths), B, C, T, lmax, int(blank), QUALITY_STATS[stat], qscale,
                                            qbias, _p(error), _p(qual), _p(dwell), _p(read_error), _p(bad), _stream()),
                    "wn_ctc_base_quality")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_base_qualities: %d base(s) or read(s) with a "
-                          "label outside [0, %d) or equal to the blank (%d), a frame outside its utterance or out of order, or a "
-                          "length out of range" % (n, C, blank), at_once=False)
+        _args.note_bad(bad, lambda n, C=C, blank=int(blank): "wavenet_speech_amd.ctc_base_qualities: %d base(s) or read(s) with a "
+                       "label outside [0, %d) or equal to the blank (%d), a frame outside its utterance or out of order, or a "
+                       "length out of range" % (n, C, blank))
         mean_qscore = torch.log10(read_error) * (-10.0 * qscale) + qbias
     return BaseQualities(error[:, :width], qual[:, :width], dwell[:, :width], read_error, mean_qscore)
 
@@ -449,28 +406,10 @@ class QualityProfile(namedtuple("QualityProfile", "q_counts dwell_counts confusi
 
 
 def _profile_rows(rows, B, M, dtype, what, name):
+    """the optional qual / dwell rows of a query: at least its M columns (none: one unused column, as _pair_rows)"""
     if rows is None:
         return None
-    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
-    if rows.dtype != dtype or rows.dim() != 2 or rows.shape[0] != B or rows.shape[1] < M:
-        raise ValueError("wavenet_speech_amd.%s: %s must be %s of shape (%d, >= %d), got %s %s"
-                         % (what, name, dtype, B, M, rows.dtype, tuple(rows.shape)))
-    rows = rows.detach()
-    if rows.shape[1] == 0:                                           # a query without columns: one unused column, as _pair_rows
-        rows = torch.zeros(B, 1, dtype=dtype, device=rows.device)
-    if rows.shape[1] > 1 and rows.stride(1) != 1 or rows.stride(0) < 0:
-        rows = rows.contiguous()
-    return rows
-
-
-def _profile_table(into, field, shape, dev, what):
-    t = getattr(into, field) if into is not None else None
-    if t is None:
-        return torch.zeros(shape, dtype=torch.int64, device=dev)
-    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int64 tensor of shape %s on %s" % (what, field, shape, dev))
-    return t
+    return _args.int_rows(rows, what, name, B=B, shape="(%d, >= %d)" % (B, M), min_width=M, dtypes=(dtype,), pad_empty=True)
 
 
 def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None, dwell=None, classes=5, count_ends=False,
@@ -491,9 +430,7 @@ def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None
     what = "quality_profile"
     if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
         raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
-    ops, ops_len = alignment.ops, alignment.ops_len
-    if not isinstance(ops, torch.Tensor) or not ops.is_cuda or not isinstance(ops_len, torch.Tensor) or not ops_len.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: the alignment must be on the GPU (there is no CPU fallback)" % what)
+    ops, ops_len = _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
     width = int(query.shape[1]) if isinstance(query, torch.Tensor) and query.dim() == 2 else 0
     ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
     query, query_lengths = _pair_rows(query, query_lengths, what, "query")
@@ -524,11 +461,10 @@ def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None
     if into is not None and ((into.q_counts is None) != (qual is None) or (into.dwell_counts is None) != (dwell is None)):
         raise ValueError("wavenet_speech_amd.%s: into carries a table for which no qual / dwell is given, or the reverse" % what)
     lib = _lib.load()
-    from .functional import _p, _stream
     with torch.cuda.device(dev):
-        q_counts = _profile_table(into, "q_counts", (QUAL_ROWS, 3), dev, what) if qual is not None else None
-        dwell_counts = _profile_table(into, "dwell_counts", (DWELL_ROWS, 3), dev, what) if dwell is not None else None
-        confusion = _profile_table(into, "confusion", (C + 1, C + 1), dev, what)
+        q_counts = _args.into_table(into, "q_counts", (QUAL_ROWS, 3), dev, what) if qual is not None else None
+        dwell_counts = _args.into_table(into, "dwell_counts", (DWELL_ROWS, 3), dev, what) if dwell is not None else None
+        confusion = _args.into_table(into, "confusion", (C + 1, C + 1), dev, what)
         read_counts = torch.empty(B, 5, dtype=torch.int32, device=dev)
         outcome = torch.empty(B, M, dtype=torch.uint8, device=dev)
         ref_index = torch.empty(B, M, dtype=torch.int32, device=dev)
@@ -538,10 +474,9 @@ def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None
                                           _p(dwell), dwell.stride(0) if dwell is not None else 0, B, N, M, max_ops, C,
                                           int(bool(count_ends)), _p(q_counts), _p(dwell_counts), _p(confusion), _p(read_counts),
                                           _p(outcome), _p(ref_index), _p(bad), _stream()), "wn_quality_profile")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n, C=C: "wavenet_speech_amd.quality_profile: %d pair(s) whose ops do not fit their labels: a "
-                          "length out of range, an op outside 1..4, labels consumed or compared wrongly, a label outside [0, %d), a "
-                          "qual above %d or a negative dwell" % (n, C, MAX_QUAL), at_once=False)
+        _args.note_bad(bad, lambda n, C=C: "wavenet_speech_amd.quality_profile: %d pair(s) whose ops do not fit their labels: a "
+                       "length out of range, an op outside 1..4, labels consumed or compared wrongly, a label outside [0, %d), a "
+                       "qual above %d or a negative dwell" % (n, C, MAX_QUAL))
     return QualityProfile(q_counts, dwell_counts, confusion, read_counts, outcome[:, :width], ref_index[:, :width])
 
 

@@ -27,7 +27,8 @@ from fractions import Fraction
 
 import torch
 
-from . import _flags, _lib
+from . import _args, _lib
+from ._args import _alloc_bytes, _p, _stream
 from .decoding import DEFAULT_ALPHABET
 
 MAX_K = 6
@@ -74,30 +75,18 @@ class KmerEvents(_Fields):
         return var.sqrt() / float(1 << self.frac_bits)
 
 
-def _rows(x, dtypes, what, name, dev=None):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: %s must be a GPU tensor (there is no CPU fallback)" % (what, name))
-    if x.dtype not in dtypes:
-        raise ValueError("wavenet_speech_amd.%s: %s must be %s, got %s" % (what, name, " or ".join(str(d) for d in dtypes), x.dtype))
-    if dev is not None and x.device != dev:
-        raise ValueError("wavenet_speech_amd.%s: %s must be on %s" % (what, name, dev))
-    return x.detach()
-
-
-def _lengths(x, B, dev, what, name):
-    x = torch.as_tensor(x).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    if x.shape[0] != B:
-        raise ValueError("wavenet_speech_amd.%s: %s must hold %d lengths, got %d" % (what, name, B, x.shape[0]))
-    return x
-
-
-def _table(into, field, shape, dev, what):
-    t = getattr(into, field) if into is not None else None
-    if t is None:
-        return torch.zeros(shape, dtype=torch.int64, device=dev)
-    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int64 tensor of shape %s on %s" % (what, field, shape, dev))
-    return t
+def _read_inputs(what, signal, signal_lengths, labels, label_lengths, scale_shift):
+    """what kmer_events and signal_align take alike: the signal as [B, L] rows and the int32 label rows, both read in place by
+    their row stride, the two [B] length vectors and the [B, 2] scale_shift pair on the signal's device; then B, L and the device"""
+    signal = _args.signal_rows(signal, what)
+    dev = signal.device
+    B, L = int(signal.shape[0]), int(signal.shape[1])
+    labels = _args.int_rows(labels, what, "labels", B=B, shape="(%d, n >= 1)" % B, min_width=1, device=dev)
+    with torch.cuda.device(dev):
+        signal_lengths = _args.lengths(signal_lengths, B, dev, what, "signal_lengths", flatten=True)
+        label_lengths = _args.lengths(label_lengths, B, dev, what, "label_lengths", flatten=True)
+        scale_shift = _args.scale_shift(scale_shift, B, dev, what)
+    return signal, signal_lengths, labels, label_lengths, scale_shift, B, L, dev
 
 
 def kmer_events(signal, signal_lengths, labels, label_lengths, spans=None, starts=None, k=5, first=-2, frame_stride=1,
@@ -124,22 +113,8 @@ def kmer_events(signal, signal_lengths, labels, label_lengths, spans=None, start
     event) has kmer -4, zeros elsewhere, read_counts -1, adds nothing to the tables and is reported through
     check_device_flags().  Returns KmerEvents."""
     what = "kmer_events"
-    signal = _rows(signal, (torch.float32, torch.int16), what, "signal")
-    dev = signal.device
-    if signal.dim() == 3 and signal.shape[1] == 1:
-        signal = signal[:, 0, :]
-    if signal.dim() != 2 or signal.shape[0] < 1 or signal.shape[1] < 1:
-        raise ValueError("wavenet_speech_amd.%s: signal must be [B, L] or [B, 1, L] with B, L >= 1, got %s" % (what, tuple(signal.shape)))
-    if signal.stride(1) != 1 and signal.shape[1] > 1 or signal.stride(0) < 0:
-        signal = signal.contiguous()
-    B, L = int(signal.shape[0]), int(signal.shape[1])
-    labels = _rows(labels, (torch.int32, torch.int64), what, "labels", dev)
-    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 1:
-        raise ValueError("wavenet_speech_amd.%s: labels must be [%d, n >= 1], got %s" % (what, B, tuple(labels.shape)))
-    if labels.dtype != torch.int32:
-        labels = labels.int()
-    if labels.stride(1) != 1 and labels.shape[1] > 1 or labels.stride(0) < 0:
-        labels = labels.contiguous()
+    signal, signal_lengths, labels, label_lengths, scale_shift, B, L, dev = _read_inputs(what, signal, signal_lengths, labels,
+                                                                                         label_lengths, scale_shift)
     if (spans is None) == (starts is None):
         raise ValueError("wavenet_speech_amd.%s: give exactly one of spans and starts" % what)
     k, first, F, D = int(k), int(first), int(frac_bits), int(max_dwell)
@@ -150,56 +125,43 @@ def kmer_events(signal, signal_lengths, labels, label_lengths, spans=None, start
     if frame_stride < 1 or frame_offset < 0 or L * frame_stride >= 2 ** 31:
         raise ValueError("wavenet_speech_amd.%s: frame_stride >= 1, frame_offset >= 0 and L * frame_stride < 2^31" % what)
     with torch.cuda.device(dev):
-        signal_lengths = _lengths(signal_lengths, B, dev, what, "signal_lengths")
-        label_lengths = _lengths(label_lengths, B, dev, what, "label_lengths")
         if spans is not None:
-            seg = _rows(spans, (torch.int32,), what, "spans", dev)
+            seg = _args.gpu_tensor(spans, what, "spans", (torch.int32,), ValueError, dev)
             if seg.dim() != 3 or seg.shape[0] != B or seg.shape[1] < 1 or seg.shape[2] != 2:
                 raise ValueError("wavenet_speech_amd.%s: spans must be [%d, N >= 1, 2], got %s" % (what, B, tuple(seg.shape)))
             if seg.stride(2) != 1 or seg.stride(0) < 0 or seg.stride(1) < 0:
                 seg = seg.contiguous()
             N, end_offset, events = int(seg.shape[1]), 1, label_lengths
         else:
-            seg = _rows(starts, (torch.int32,), what, "starts", dev)
+            seg = _args.gpu_tensor(starts, what, "starts", (torch.int32,), ValueError, dev)
             if seg.dim() != 2 or seg.shape[0] != B or seg.shape[1] < 2:
                 raise ValueError("wavenet_speech_amd.%s: starts must be [%d, N + 1 >= 2], got %s" % (what, B, tuple(seg.shape)))
             if seg.stride(0) < 0 or seg.stride(1) < 0:
                 seg = seg.contiguous()
             N, end_offset = int(seg.shape[1]) - 1, int(seg.stride(1))
             events = torch.full((B,), N, dtype=torch.int32, device=dev)
-        if scale_shift is not None:
-            scale_shift = _rows(scale_shift, (torch.float32,), what, "scale_shift", dev)
-            if tuple(scale_shift.shape) != (B, 2):
-                raise ValueError("wavenet_speech_amd.%s: scale_shift must be [%d, 2], got %s" % (what, B, tuple(scale_shift.shape)))
-            scale_shift = scale_shift.contiguous()
         if into is not None and not isinstance(into, KmerEvents):
             raise ValueError("wavenet_speech_amd.%s: into must be a KmerEvents, got %s" % (what, type(into).__name__))
         if into is not None and (into.k, into.first, into.frac_bits, into.max_dwell) != (k, first, F, D):
             raise ValueError("wavenet_speech_amd.%s: into was made with other k, first, frac_bits or max_dwell" % what)
         lib = _lib.load()
-        from .functional import _p, _stream
-        kmer_stats = _table(into, "kmer_stats", (4 ** k, 5), dev, what)
-        dwell_hist = _table(into, "dwell_hist", (4 ** k, D + 1), dev, what)
+        kmer_stats = _args.into_table(into, "kmer_stats", (4 ** k, 5), dev, what)
+        dwell_hist = _args.into_table(into, "dwell_hist", (4 ** k, D + 1), dev, what)
         i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
         ev = [None] * 5
         if want_events:
             ev = [torch.empty(B, N, **i32) for _ in range(3)] + [torch.empty(B, N, **i64) for _ in range(2)]
         read_counts = torch.empty(B, 4, **i32)
         bad = torch.zeros(1, **i32)
-        ws_bytes = lib.wn_kmer_events_workspace_bytes(B, N)
-        if ws_bytes == 0:
-            _lib.check(-2, "wn_kmer_events_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _alloc_bytes(lib.wn_kmer_events_workspace_bytes(B, N), "wn_kmer_events_workspace_bytes", dev, status=-2)
         seg_end = seg.data_ptr() + 4 * end_offset
         _lib.check(lib.wn_kmer_events(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
                                       _p(seg), _p(seg_end), seg.stride(0), seg.stride(1), frame_stride, frame_offset, _p(labels),
                                       labels.stride(0), _p(label_lengths), _p(events), B, L, int(labels.shape[1]), N, k, first, F, D,
                                       _p(ev[0]), _p(ev[1]), _p(ev[2]), _p(ev[3]), _p(ev[4]), _p(read_counts), _p(kmer_stats),
-                                      _p(dwell_hist), _p(ws), ws_bytes, _p(bad), _stream()), "wn_kmer_events")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n: "wavenet_speech_amd.kmer_events: %d bad read(s): a length out of range, a negative, reversed or "
-                          "overlapping event boundary, a label outside 1..4 or a non-finite or out-of-range sample in a used event" % n,
-                          at_once=False)
+                                      _p(dwell_hist), _p(ws), ws.numel(), _p(bad), _stream()), "wn_kmer_events")
+        _args.note_bad(bad, lambda n: "wavenet_speech_amd.kmer_events: %d bad read(s): a length out of range, a negative, reversed or "
+                       "overlapping event boundary, a label outside 1..4 or a non-finite or out-of-range sample in a used event" % n)
     return KmerEvents(ev[0], ev[1], ev[2], ev[3], ev[4], read_counts, kmer_stats, dwell_hist, k=k, first=first, frac_bits=F, max_dwell=D)
 
 
@@ -471,22 +433,8 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
     or out-of-range sample before signal_lengths[b]) is reported through check_device_flags().  HIP only.  Returns
     SignalAlignment."""
     what = "signal_align"
-    signal = _rows(signal, (torch.float32, torch.int16), what, "signal")
-    dev = signal.device
-    if signal.dim() == 3 and signal.shape[1] == 1:
-        signal = signal[:, 0, :]
-    if signal.dim() != 2 or signal.shape[0] < 1 or signal.shape[1] < 1:
-        raise ValueError("wavenet_speech_amd.%s: signal must be [B, L] or [B, 1, L] with B, L >= 1, got %s" % (what, tuple(signal.shape)))
-    if signal.stride(1) != 1 and signal.shape[1] > 1 or signal.stride(0) < 0:
-        signal = signal.contiguous()
-    B, L = int(signal.shape[0]), int(signal.shape[1])
-    labels = _rows(labels, (torch.int32, torch.int64), what, "labels", dev)
-    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 1:
-        raise ValueError("wavenet_speech_amd.%s: labels must be [%d, n >= 1], got %s" % (what, B, tuple(labels.shape)))
-    if labels.dtype != torch.int32:
-        labels = labels.int()
-    if labels.stride(1) != 1 and labels.shape[1] > 1 or labels.stride(0) < 0:
-        labels = labels.contiguous()
+    signal, signal_lengths, labels, label_lengths, scale_shift, B, L, dev = _read_inputs(what, signal, signal_lengths, labels,
+                                                                                         label_lengths, scale_shift)
     if not isinstance(model, SignalModel):
         raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
     first, band = int(first), int(band)
@@ -499,15 +447,7 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
     if L > MAX_ALIGN_SIGNAL or N > MAX_ALIGN_EVENTS or B > 65535:
         raise ValueError("wavenet_speech_amd.%s: at most 2^24 samples and 2^20 k-mers per read and 65535 reads" % what)
     with torch.cuda.device(dev):
-        signal_lengths = _lengths(signal_lengths, B, dev, what, "signal_lengths")
-        label_lengths = _lengths(label_lengths, B, dev, what, "label_lengths")
-        if scale_shift is not None:
-            scale_shift = _rows(scale_shift, (torch.float32,), what, "scale_shift", dev)
-            if tuple(scale_shift.shape) != (B, 2):
-                raise ValueError("wavenet_speech_amd.%s: scale_shift must be [%d, 2], got %s" % (what, B, tuple(scale_shift.shape)))
-            scale_shift = scale_shift.contiguous()
         lib = _lib.load()
-        from .functional import _p, _stream
         table = model.on(dev)
         i32 = dict(dtype=torch.int32, device=dev)
         starts = torch.empty(B, N + 1, **i32)
@@ -515,16 +455,12 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
         band_hits = torch.empty(B, **i32)
         states = torch.empty(B, L, **i32) if want_states else None
         bad = torch.zeros(1, **i32)
-        ws_bytes = lib.wn_signal_align_workspace_bytes(B, L, band)
-        if ws_bytes == 0:
-            _lib.check(-2, "wn_signal_align_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _alloc_bytes(lib.wn_signal_align_workspace_bytes(B, L, band), "wn_signal_align_workspace_bytes", dev, status=-2)
         _lib.check(lib.wn_signal_align(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
                                        _p(labels), labels.stride(0), _p(label_lengths), _p(table), B, L, int(labels.shape[1]), N, k, first,
                                        model.frac_bits, model.weight_shift, max_cost, band, _p(starts), _p(score), _p(band_hits),
-                                       _p(states), _p(ws), ws_bytes, _p(bad), _stream()), "wn_signal_align")
-        _flags.WATCH.poll()
-        _flags.WATCH.note(bad, lambda n: "wavenet_speech_amd.signal_align: %d bad read(s): a length out of range, a label outside 1..4, "
-                          "a non-finite or out-of-range sample or a model row out of range" % n, at_once=False)
+                                       _p(states), _p(ws), ws.numel(), _p(bad), _stream()), "wn_signal_align")
+        _args.note_bad(bad, lambda n: "wavenet_speech_amd.signal_align: %d bad read(s): a length out of range, a label outside 1..4, "
+                       "a non-finite or out-of-range sample or a model row out of range" % n)
     return SignalAlignment(starts, score, band_hits, states, k=k, first=first, frac_bits=model.frac_bits, cost_bits=model.cost_bits,
                            band=band)

@@ -14,6 +14,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _flags, _lib
+from ._args import _alloc_bytes, _p, _stream  # noqa: F401  (tools and tests import them from here)
 from .series import Lease, SeriesLayout, fresh_series, load_series, window
 
 PARAMS_PER_BLOCK = 10  # order = _lib.BlockParams fields
@@ -66,28 +67,6 @@ def _own(view):
     """Fresh contiguous copy of a window of a pooled buffer.  `.contiguous()` is NOT enough: when halo == 0, L is a
     multiple of 128 and C a multiple of 8 the padded layout is already dense and it would return the alias."""
     return view.clone(memory_format=torch.contiguous_format)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(x):
-    """device pointer of a tensor / Lease / None"""
-    if x is None:
-        return None
-    if isinstance(x, int):
-        return ctypes.c_void_p(x)
-    if isinstance(x, Lease):
-        return ctypes.c_void_p(x.ptr)
-    return ctypes.c_void_p(x.data_ptr())
-
-
-def _alloc_bytes(nbytes, what, device, status=-1):
-    """uint8 device buffer of the size the library's query `what` returned; 0 is its refusal of the shape and raises `status`"""
-    if nbytes == 0:
-        _lib.check(status, what)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def _workspace(ws_bytes, device):

@@ -15,41 +15,22 @@ A rank outside [0, n), every rank of an empty read and a read whose length is ne
 their result is 0.0 and they are counted; the count raises a RuntimeError through the package's device flags (_flags.WATCH)
 unless the caller passes its own `bad` counter.  There is no CPU fallback: CPU tensors raise.
 """
-import ctypes
-
 import torch
 
-from . import _flags, _lib
+from . import _args, _flags, _lib
+from ._args import _p, _stream
 
 TILE = 8192                 # samples per workgroup of a pass (kSelTile in csrc/wn_select.hip)
 MAX_RANKS = 8               # K of one wn_read_select call
 MAD_TO_SD = 1.4826          # the MAD of a normal distribution is sd / 1.4826
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _signal2d(signal, what):
-    if not isinstance(signal, torch.Tensor) or not signal.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: signal must be a GPU tensor (there is no CPU fallback)" % what)
-    if signal.dtype not in (torch.float32, torch.int16):
-        raise TypeError("wavenet_speech_amd.%s: signal must be float32 or int16, got %s" % (what, signal.dtype))
-    if signal.dim() == 3 and signal.shape[1] == 1:
-        signal = signal[:, 0]
-    if signal.dim() != 2 or signal.shape[0] < 1 or signal.shape[1] < 1:
-        raise ValueError("wavenet_speech_amd.%s: signal must be [B, 1, Lpad] or [B, Lpad], got shape %s" % (what, tuple(signal.shape)))
-    signal = signal.detach()
-    return signal if signal.is_contiguous() else signal.contiguous()
+    return _args.signal_rows(signal, what, error=TypeError, dense=True)      # dense rows: the row length is the reads' capacity
 
 
 def _lengths(signal_lengths, B, device, what):
-    if not isinstance(signal_lengths, torch.Tensor) or not signal_lengths.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: signal_lengths must be a GPU tensor (there is no CPU fallback)" % what)
-    if signal_lengths.is_floating_point() or signal_lengths.dtype == torch.bool or signal_lengths.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: signal_lengths must be integers of shape (%d,), got %s %s"
-                         % (what, B, signal_lengths.dtype, tuple(signal_lengths.shape)))
-    return signal_lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+    return _args.lengths(signal_lengths, B, device, what, "signal_lengths", on_gpu=True)       # never read back, never uploaded
 
 
 def select_workspace(batch, K, dtype, has_center, device):
@@ -71,13 +52,12 @@ def read_order_statistics(signal, signal_lengths, ranks, center=None, bad=None, 
     B, ld = int(signal.shape[0]), int(signal.shape[1])
     dev = signal.device
     len_d = _lengths(signal_lengths, B, dev, what)
-    if not isinstance(ranks, torch.Tensor) or not ranks.is_cuda:
-        raise RuntimeError("wavenet_speech_amd.%s: ranks must be a GPU tensor (there is no CPU fallback)" % what)
+    ranks = _args.gpu_tensor(ranks, what, "ranks")
     if ranks.is_floating_point() or ranks.dim() != 2 or ranks.shape[0] != B or not 1 <= ranks.shape[1] <= MAX_RANKS:
         raise ValueError("wavenet_speech_amd.%s: ranks must be integers of shape (%d, K), 1 <= K <= %d, got %s %s"
                          % (what, B, MAX_RANKS, ranks.dtype, tuple(ranks.shape)))
     K = int(ranks.shape[1])
-    ranks = ranks.detach().to(device=dev, dtype=torch.int32).contiguous()
+    ranks = ranks.to(device=dev, dtype=torch.int32).contiguous()
     if center is not None:
         if not isinstance(center, torch.Tensor) or not center.is_cuda or center.shape != (B,):
             raise ValueError("wavenet_speech_amd.%s: center must be a GPU tensor of shape (%d,)" % (what, B))
@@ -94,9 +74,8 @@ def read_order_statistics(signal, signal_lengths, ranks, center=None, bad=None, 
                 or not workspace.is_contiguous():
             raise ValueError("wavenet_speech_amd.%s: workspace must be a contiguous uint8 GPU tensor (select_workspace)" % what)
         out = torch.empty(B, K, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().wn_read_select(_ptr(signal), int(signal.dtype == torch.int16), B, ld, _ptr(len_d), _ptr(ranks), K,
-                                              _ptr(center), _ptr(out), _ptr(workspace), int(workspace.numel()), _ptr(bad),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "wn_read_select")
+        _lib.check(_lib.load().wn_read_select(_p(signal), int(signal.dtype == torch.int16), B, ld, _p(len_d), _p(ranks), K, _p(center),
+                                              _p(out), _p(workspace), int(workspace.numel()), _p(bad), _stream()), "wn_read_select")
         if own_bad:
             _note(bad, what)
     return out

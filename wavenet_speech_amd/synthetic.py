@@ -29,9 +29,13 @@ zero-padded to a common length, the bases as CTC targets -- csrc/wn_reads.hip on
 `RawGaussianModelLoader` is the reference's loader class on top of it.
 """
 import collections
+import ctypes
 import math
 
 import torch
+
+from . import _args, _flags, _lib
+from ._args import _alloc_bytes, _p, _stream
 
 KMER_WEIGHTS = (256, 64, 16, 4, 1)
 
@@ -96,19 +100,14 @@ def hip_signal(bases, length, num_levels=256, upsampling=3, table=None, seed=0, 
     """The HIP stages on given nucleotides (device int64 [B, n]).  `noise` (float64 [B, L]) replaces the Philox Gaussian
     draw; `picoamps` (float64 [B, L]) skips the signal stage altogether (quantize + one-hot of a given signal).
     Returns (levels, one_hot or None, picoamps)."""
-    import ctypes
-    from . import _lib
-    from .functional import _p, _stream
     lib = _lib.load()
     dev = bases.device
     if dev.type != "cuda":
         raise RuntimeError("wavenet_speech_amd: the HIP generator needs device tensors")
     B, nb = bases.shape
     with torch.cuda.device(dev):
-        ws_bytes = lib.wn_synth_workspace_bytes(B, length)
-        if ws_bytes == 0:
-            _lib.check(-1, "wn_synth_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _alloc_bytes(lib.wn_synth_workspace_bytes(B, length), "wn_synth_workspace_bytes", dev)
+        ws_bytes = ws.numel()
         means, stdvs = table if table is not None else standin_kmer_table(device=dev)
         means, stdvs = means.to(dev).double().contiguous(), stdvs.to(dev).double().contiguous()
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -137,9 +136,6 @@ def hip_signal(bases, length, num_levels=256, upsampling=3, table=None, seed=0, 
 
 
 def hip_bases(batch, nbases, seed, device):
-    import ctypes
-    from . import _lib
-    from .functional import _p, _stream
     lib = _lib.load()
     dev = torch.device(device)
     with torch.cuda.device(dev):
@@ -239,9 +235,6 @@ def hip_reads_plan(batch, min_bases, max_bases, window, dwell, max_dwell, seed, 
                    dwell_values=None):
     """wn_reads_plan.  Rows are max_bases wide; given bases / dwell_values (int32, device) must be too.  Returns a dict of the
     outputs, the workspace for hip_reads_signal and the device counters `bad` and `clamped`."""
-    import ctypes
-    from . import _lib
-    from .functional import _p, _stream
     lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -265,9 +258,6 @@ def hip_reads_plan(batch, min_bases, max_bases, window, dwell, max_dwell, seed, 
 def hip_reads_signal(plan, ld, table, seed, noise=None, signal=None, sample_kmer=None):
     """wn_reads_signal on a plan of hip_reads_plan.  noise: float64 [B, ld].  signal / sample_kmer may be given (prefilled
     buffers [B, ld]); returns (signal [B, ld] float32, sample_kmer [B, ld] int32, clipped_lengths [B] int32, bad [1] int32)."""
-    import ctypes
-    from . import _lib
-    from .functional import _p, _stream
     lib = _lib.load()
     dev = plan["bases"].device
     B = plan["bases"].shape[0]
@@ -404,7 +394,6 @@ def ragged_reads(batch, lengths=(20, 30), dwell=("uniform", 6, 2), window="loade
             generator = torch.Generator(device=dev).manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,), generator=generator)))
         return _torch_reads(batch, lo, hi, win, dwell, max_dwell, table, generator, dev, pad_to, bases, base_lengths, dwell_values,
                             noise)
-    from . import _flags
     seed = _device_seed(generator, dev)
     nmax, kmax = hi - 1, hi - 1 - 4 - 2 * win
     with torch.cuda.device(dev):
@@ -413,12 +402,10 @@ def ragged_reads(batch, lengths=(20, 30), dwell=("uniform", 6, 2), window="loade
         gd = None if dwell_values is None else _given_rows(dwell_values, hi, dev, "dwell_values")
         plan = hip_reads_plan(batch, lo, hi, win, dwell, max_dwell, seed, dev, gb, gl, gd)
         poisoned = "wavenet_speech_amd: ragged_reads: %d read(s) with a length out of range, bases outside 1..4 or dwell below 1"
-        _flags.WATCH.poll()
+        _args.note_bad(plan["bad"], lambda n: poisoned % n, at_once=pad_to is None)
         if pad_to is None:
-            _flags.WATCH.note(plan["bad"], lambda n: poisoned % n, at_once=True)
             ld = max(int(plan["signal_lengths"].max()), 1)             # the one host read, as batchify's max()
         else:
-            _flags.WATCH.note(plan["bad"], lambda n: poisoned % n, at_once=False)
             ld = int(pad_to)
         nz = None
         if noise is not None:

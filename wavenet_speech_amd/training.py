@@ -16,6 +16,9 @@ reference holds for warp-ctc (tests/test_classifier.py:59 -> 2.4628) and against
 import torch
 import torch.nn.functional as F
 
+from . import _args, _lib
+from ._args import _p, _stream
+
 
 def sequence_nll(pred, target):
     """sum over time of the batch-averaged cross entropy (Loss.py:38-43, legacy_code/train.py:37-39).
@@ -33,9 +36,6 @@ class _CTCFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, transcription, labels, label_lengths, input_lengths, blank):
-        import ctypes
-        from . import _lib
-        from .functional import _p, _stream
         lib = _lib.load()
         x = transcription.detach().contiguous().float()
         B, C, T = x.shape
@@ -60,10 +60,8 @@ class _CTCFn(torch.autograd.Function):
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
             _lib.check(lib.wn_ctc_loss(_p(x), _p(labels), _p(label_lengths), _p(in_len), B, C, T, lmax, int(blank), _p(nll),
                                        _p(dx), _p(ws), ws_bytes, _p(bad), _stream()), "wn_ctc_loss")
-            from . import _flags
-            _flags.WATCH.poll()
-            _flags.WATCH.note(bad, lambda n, C=C, blank=blank: "wavenet_speech_amd: ctc labels outside [0, %d), equal to the blank "
-                              "(%d), or lengths out of range in %d utterance(s)" % (C, blank, n), at_once=not need_grad)
+            _args.note_bad(bad, lambda n, C=C, blank=blank: "wavenet_speech_amd: ctc labels outside [0, %d), equal to the blank "
+                           "(%d), or lengths out of range in %d utterance(s)" % (C, blank, n), at_once=not need_grad)
         ctx.dx = dx
         return nll.sum()
 
