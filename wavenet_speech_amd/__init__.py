@@ -8,7 +8,7 @@ modules.classifier.WaveNetClassifier, modules.conv_ops.*).
 All arithmetic of the hot path runs in hand-written HIP kernels (csrc/, gfx950) reached through the C ABI of
 libwavenet_amd.so (include/wavenet_amd.h).  No CPU fallback exists.
 """
-from . import basecalling, decoding, events, functional, graphs, modules, normalise, series  # noqa: F401
+from . import basecalling, decoding, events, functional, graphs, mapping, modules, normalise, series  # noqa: F401
 from .modules import (CausalConv1d, NonCausalConv1d, RawCTCNet, ResidualBlock, WaveNet,  # noqa: F401
                       WaveNetClassifier)
 from .modules.block import freeze_for_inference, set_precision  # noqa: F401
@@ -23,6 +23,7 @@ from .basecalling import Basecaller, Basecalls, ChunkPlan, chunk_plan, receptive
 from .normalise import read_med_mad, read_normalisation, read_order_statistics, read_quantiles  # noqa: F401
 from .events import KmerEvents, eventalign_rows, fit_dwell_model, fit_kmer_model, kmer_events  # noqa: F401
 from .events import SignalAlignment, SignalModel, signal_align, signal_model  # noqa: F401
+from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 
 __version__ = "0.1.0"

@@ -40,7 +40,6 @@ constexpr int kSaMinBand = 64;
 constexpr int kSaMaxBand = 2048;
 constexpr int kSaMaxSignal = 1 << 24;
 constexpr int kSaMaxEvents = 1 << 20;
-constexpr int kSaOffsetLimit = 1 << 30;
 constexpr long long kSaInf = 1ll << 62;       // a path's cost stays below 2^24 (2^31 + 2^30) < 2^56
 constexpr long long kSaNoAlignment = 0x7fffffffffffffffll;
 constexpr long long kSaBadRead = -0x7fffffffffffffffll - 1;
@@ -62,30 +61,6 @@ struct SigAlignArgs {
     unsigned char* bp;                  // workspace: [B][max_signal][band / 8]
     int* bad;
 };
-
-// min((d d weight) >> S, max_cost) + offset with d = |q - level| < 2^24: the 79-bit product in two 64-bit halves
-__device__ __forceinline__ long long sa_sample_cost(int q, int level, int weight, int offset, int S, int max_cost) {
-    const int df = q - level;
-    const unsigned d = (unsigned)(df < 0 ? -df : df);
-    const unsigned long long dd = (unsigned long long)d * d;         // < 2^48
-    const unsigned long long w = (unsigned)weight;
-    const unsigned long long p0 = (dd & 0xffffffffull) * w, p1 = (dd >> 32) * w;     // p1 < 2^47
-    const unsigned long long lo = p0 + (p1 << 32);
-    const unsigned long long hi = (p1 >> 32) + (lo < p0 ? 1ull : 0ull);              // < 2^15
-    const unsigned long long sh = (lo >> S) | (hi << (64 - S));      // S in 16..63: the quotient is below 2^63
-    const long long c = sh < (unsigned long long)max_cost ? (long long)sh : (long long)max_cost;
-    return c + offset;
-}
-
-// the model row of a k-mer that the path can use; a row out of range clears *ok and is replaced by (0, 1, 0)
-__device__ __forceinline__ void sa_model_row(const int* model, int code, int* level, int* weight, int* offset, bool* ok) {
-    const int l = model[3 * code], w = model[3 * code + 1], o = model[3 * code + 2];
-    const bool good = w >= 1 && l > -kSigQLimit && l < kSigQLimit && o > -kSaOffsetLimit && o < kSaOffsetLimit;
-    if (!good) *ok = false;
-    *level = good ? l : 0;
-    *weight = good ? w : 1;
-    *offset = good ? o : 0;
-}
 
 // lo(t): the first state of the band at sample t
 __device__ __forceinline__ int sa_band_lo(long long t, int N, int T, int W) {
