@@ -676,6 +676,55 @@ int wn_signal_map(const void* signal, int signal_kind, long long signal_stride, 
                   long long* runner_up, long long* block_cost, int* block_end, long long* end_cost /* may be NULL */,
                   void* workspace, size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Event detection (wavenet_speech_amd.events.detect_events): a raw read in, the table of its events
+ * out -- where its level changes -- with no bases and no network: what nanopolish, scrappie, UNCALLED and sigmap run before
+ * anything else.  Its `starts` follow wn_signal_align's convention and its event means are a shorter "read" for wn_signal_map and
+ * wn_signal_align.  All pointers are DEVICE pointers.
+ *   signal, signal_kind, signal_stride, signal_lengths, scale_shift, frac_bits F: as wn_kmer_events; q_t = llrint(v_t 2^F), ties
+ *   to even, |q| < 2^23; T_b = signal_lengths[b] in [0, max_signal].
+ * Two detectors, `short` (d = 0) and `long` (d = 1), each with a window w_d in 1..16 (window_long = 0 switches the long detector
+ * off; its other three arguments are then ignored), a radius r_d in 1..64, a threshold theta_d (int32 >= 1, on t^2 in units of
+ * 2^-8) and a variance floor vmin_d = min_var_* (int64 in 1..2^55).
+ * Arithmetic (the definition; tests/event_detect_ref.py mirrors it in Python integers).  For a position i with w <= i <= T - w:
+ *   S1 = sum q[i-w .. i),  S2 = sum q[i .. i+w),  Q = sum of q^2 over both windows,
+ *   A_i = w (S2 - S1)^2 (< 2^60),   V_i = max(w Q - S1^2 - S2^2, vmin) (<= 2^55),   score(i) = A_i / V_i:
+ * Welch's t^2 between two equal windows.  Every other position has score 0.  Scores are compared exactly as rationals: A_i / V_i
+ * > A_j / V_j iff A_i V_j > A_j V_i, in 128-bit products; i PASSES THE THRESHOLD iff 256 A_i >= theta V_i.  No floating-point
+ * division or square root appears.  i is a PEAK of detector d iff it passes the threshold and, for every j != i in [i - r, i + r],
+ * its score is strictly greater when j < i and greater or equal when j > i (ties go to the smaller index).
+ * Boundaries of a read with T >= 1: position 0; every short peak; every long peak with no short peak within +-w_1 (distance
+ * w_1 included).  Then every gap between consecutive boundaries -- T counts as the last boundary -- that is longer than
+ * max_event_len (1..65536, so that an event's sum of q^2 stays below 2^62) also gets a FORCED boundary every max_event_len samples
+ * after its left end.  Event e is [b_e, b_(e+1)).
+ * Outputs ([B][max_events] unless said otherwise):
+ *   n_events  [B] int32   the true count of events, even above max_events: the rows then hold the first max_events events whole
+ *   starts    [B][max_events + 1] int32   starts[e] = b_e; every entry e >= n_events[b] is T_b (wn_signal_align's convention)
+ *   ev_sum, ev_sumsq  int64   sum q and sum q^2 over the event; 0 past the last event
+ *   ev_kind   int32, may be NULL   why the event begins: 0 the read's start, 1 a short peak, 2 a long peak, 3 forced; -1 past
+ *             the last event
+ * Checked on the device.  T_b = 0 gives 0 events and is not bad.  A read is BAD when T_b is outside [0, max_signal] (nothing
+ * else of it is then read) or a sample in [0, T_b) is not finite or has |q| >= 2^23: n_events -1, starts -1, ev_sum / ev_sumsq
+ * 0, ev_kind -1, counted once in *bad (DEVICE int, caller-zeroed, may be NULL).  Samples past T_b are never read.
+ * chunk_samples: the positions one workgroup of the first launch decides, a multiple of 256 in [256, 16384], or 0 for the
+ * library's choice.  A tuning argument: NO OUTPUT DEPENDS ON IT and it sizes nothing.  One memset and three launches (scores and
+ * peaks, grid (ceil(max_signal / chunk), batch); ranks, one workgroup per read; sums, grid (ceil((max_events + 1) / 256), batch));
+ * integer arithmetic only, two runs are bitwise identical; nothing is read back and nothing is allocated, so the call can be
+ * captured into a HIP graph.  workspace: wn_event_detect_workspace_bytes(batch, max_signal) bytes, 16-byte aligned (a flag per
+ * read and two bits per sample); 0 for batch outside 1..65535 or max_signal outside 1..2^24.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_signal or max_events < 1, a negative stride,
+ * signal_kind not 0 or 1.  WN_ERR_UNSUPPORTED: F outside 0..20, batch > 65535, max_signal > 2^24, max_events > 2^24,
+ * window_short outside 1..16, window_long outside 0..16, a radius outside 1..64, a threshold < 1, a min_var outside 1..2^55 (the
+ * long detector's three only with window_long > 0), max_event_len outside 1..65536, a chunk_samples that is neither 0 nor a
+ * multiple of 256 in [256, 16384].  WN_ERR_NULL: signal, signal_lengths, n_events, starts, ev_sum, ev_sumsq or the workspace.
+ * WN_ERR_WORKSPACE: a workspace too small or not 16-byte aligned, a signal not aligned to its element size. */
+size_t wn_event_detect_workspace_bytes(int batch, int max_signal);
+int wn_event_detect(const void* signal, int signal_kind, long long signal_stride, const int* signal_lengths,
+                    const float* scale_shift /* may be NULL */, int batch, int max_signal, int frac_bits, int window_short,
+                    int window_long, int radius_short, int radius_long, int threshold_short, int threshold_long,
+                    long long min_var_short, long long min_var_long, int max_event_len, int max_events, int chunk_samples,
+                    int* n_events, int* starts, long long* ev_sum, long long* ev_sumsq, int* ev_kind /* may be NULL */,
+                    void* workspace, size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

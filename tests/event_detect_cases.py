@@ -1,0 +1,273 @@
+"""Inputs of the event-detection tests, built once (seeded numpy), with their references from tests/event_detect_ref.py cached per
+case.  A case is a batch of reads and the keyword arguments of wavenet_speech_amd.detect_events; `reference` forms the detectors
+from those arguments exactly as detect_events does.  tests/test_event_detect_ref.py proves from the reference alone that each
+case reaches what it is for; tests/test_gpu_event_detect.py runs them on the device."""
+import collections
+import functools
+
+import numpy as np
+
+from tests import event_detect_ref as R
+from wavenet_speech_amd import events as E
+
+Case = collections.namedtuple("Case", "signal signal_lengths kw truth")
+QMAX = (1 << 23) - 1
+CHUNK = 256                             # the smallest chunk: the seams of the tests lie at its multiples
+LENGTHS_W = 6
+LENGTHS = (0, 1, 2 * LENGTHS_W - 1, 2 * LENGTHS_W, 2 * LENGTHS_W + 1, 255, 256, 257, 511, 512, 513, 1100)
+DEFAULT_KW = dict(windows=(3, 6), thresholds=E.DEFAULT_THRESHOLDS, radii=None, min_var=E.DEFAULT_MIN_VAR, frac_bits=12, max_event_len=65536,
+                  max_events=None)
+HAND_KW = dict(DEFAULT_KW, thresholds=(4.0, 4.0), min_var=1.0, frac_bits=0)          # integers: a step of 2 is a long peak alone
+
+
+def kw_of(**more):
+    return dict(DEFAULT_KW, **more)
+
+
+def steps(levels, dwells, T=None):
+    """a piecewise-constant read and its change points"""
+    x = np.repeat(np.asarray(levels, dtype=np.float64), dwells)
+    edges = np.cumsum(dwells)[:-1]
+    return (x if T is None else x[:T]), [int(e) for e in edges if T is None or e < T]
+
+
+def noisy_reads(seed, lengths, L=None, sigma=1.5, mean_dwell=10.0):
+    """ragged_reads-like data: gamma dwells, levels 90 +- 12, Gaussian noise; returns the Case and every read's true boundaries"""
+    rng = np.random.default_rng(seed)
+    L = max(max(lengths), 1) + 3 if L is None else L
+    signal = (90.0 + 12.0 * rng.standard_normal((len(lengths), L))).astype(np.float32)       # what lies past a read is never used
+    truth = []
+    for b, T in enumerate(lengths):
+        n = max(T, 1)
+        dwells = np.maximum(rng.gamma(2.0, mean_dwell / 2.0, size=n).astype(np.int64), 1)
+        x, edges = steps(90.0 + 12.0 * rng.standard_normal(n), dwells, T)
+        signal[b, :T] = (x + sigma * rng.standard_normal(T)).astype(np.float32)
+        truth.append([0] + edges if T else [])
+    return Case(signal, np.asarray(lengths, dtype=np.int32), kw_of(), truth)
+
+
+def batch_of(reads, kw, pad=3, fill=0.0, truth=None):
+    L = max(len(r) for r in reads) + pad
+    signal = np.full((len(reads), L), fill, dtype=np.float32)
+    for b, r in enumerate(reads):
+        signal[b, :len(r)] = np.asarray(r, dtype=np.float32)
+    return Case(signal, np.array([len(r) for r in reads], dtype=np.int32), kw, truth)
+
+
+def seam_case():
+    """steps of 10 (a short peak, and a long one on top of it) and of 2 (a long peak alone) around the seam at 256: a peak on the
+    seam, one sample either side of it, and a short / long pair with the seam between them"""
+    reads, truth = [], []
+    for at in (256, 255, 257):
+        x, e = steps([20, 30, 18], [at, 40, 40])
+        reads.append(x)
+        truth.append([(0, 0), (at, 1), (at + 40, 1)])
+    for first, second, kinds in ((250, 262, (1, 2)), (249, 263, (2, 1))):
+        jump = (10, 2) if kinds == (1, 2) else (2, 10)
+        x, e = steps([20, 20 + jump[0], 20 + jump[0] + jump[1]], [first, second - first, 50])
+        reads.append(x)
+        truth.append([(0, 0), (first, kinds[0]), (second, kinds[1])])
+    return batch_of(reads, dict(HAND_KW), truth=truth)
+
+
+def halo_case():
+    """radii (3, 12): the halo is r_1 + w_1 = 18 samples.  A step of 5 on the seam at 256 (t^2 = 37.5) would be a long peak, were
+    it not for the step of 6 at 244 = 256 - r_1 (t^2 = 54; its neighbours reach 30), whose score needs the sample 238 = 256 - 18:
+    the outermost sample of the halo decides.  The short threshold is out of reach of both steps"""
+    x, _ = steps([40, 46, 51], [244, 12, 60])
+    return batch_of([x], dict(HAND_KW, radii=(3, 12), thresholds=(6.0, 4.0), min_var=4.0), truth=[[(0, 0), (244, 2)]])
+
+
+MERGE_W1 = 6
+
+
+def merge_case():
+    """a step of 10 at 100 (a short peak) and a step of 2 behind it: at distance w_1 the long peak is dropped, at w_1 + 1 it is
+    kept.  The long radius is 2, so that the long peak of the large step does not shade the small one"""
+    reads = [steps([20, 30, 32], [100, d, 60])[0] for d in (MERGE_W1, MERGE_W1 + 1)]
+    return batch_of(reads, dict(HAND_KW, radii=(3, 2)), truth=[[(0, 0), (100, 1)], [(0, 0), (100, 1), (100 + MERGE_W1 + 1, 2)]])
+
+
+TIE_HALF, TIE_FIRST = 3, 20
+
+
+def tie_case():
+    """a square wave of period 6 <= r = 6 from sample 20 to the read's end: every edge has the same score, only the first is a
+    peak"""
+    x = np.full(140, 10.0)
+    for t in range(TIE_FIRST, len(x)):
+        if ((t - TIE_FIRST) // TIE_HALF) % 2 == 0:
+            x[t] = 30.0
+    return batch_of([x], dict(HAND_KW, windows=(3, 0), radii=(6, 1)), truth=[[(0, 0), (TIE_FIRST, 1)]])
+
+
+def width_case():
+    """w = 16, r = 64, samples up to +-(2^23 - 1) at F = 0, vmin = 1: products on both sides of bit 64"""
+    rng = np.random.default_rng(7)
+    alt = np.array([1, -1] * 24)
+    small = rng.integers(-3, 4, size=40)
+    parts = [small, alt * (1 << 22), [-(1 << 22)] * 16, [1 << 22] * 16, alt * QMAX, [-QMAX] * 16, [QMAX] * 16, small[::-1]]
+    wide = np.concatenate([np.asarray(p, dtype=np.int64) for p in parts])
+    noise = rng.integers(-QMAX, QMAX + 1, size=300)
+    return batch_of([wide, noise], dict(HAND_KW, windows=(16, 16), thresholds=(1.0, 2.0), radii=(64, 64), min_var=0.0))
+
+
+def noise_free_case():
+    """piecewise-constant reads of distinct levels, dwells in 13..39: the true change points and nothing else, all of kind 1"""
+    rng = np.random.default_rng(11)
+    reads, truth = [], []
+    for n in (12, 30, 41):
+        levels = [90.0]
+        while len(levels) < n:
+            v = round(90.0 + 12.0 * rng.standard_normal(), 2)
+            if abs(v - levels[-1]) >= 1.0:
+                levels.append(v)
+        x, edges = steps(levels, rng.integers(13, 40, size=n))
+        reads.append(x)
+        truth.append([(0, 0)] + [(e, 1) for e in edges])
+    return batch_of(reads, kw_of(), truth=truth)
+
+
+def forced_small_case():
+    return batch_of([np.full(3 * 64 + 5, 50.0), np.full(64, 50.0), np.full(65, 50.0)], kw_of(max_event_len=64),
+                    truth=[[(0, 0), (64, 3), (128, 3), (192, 3)], [(0, 0)], [(0, 0), (64, 3)]])
+
+
+def forced_gap_case(max_event_len):
+    """1500 constant samples, a step, 300 more: the gap before the step holds more forced splits than one thread writes alone, and
+    so does the read's end; beside them noisy reads, whose short events are split too when max_event_len is below a word's 64"""
+    noisy = noisy_reads(41, [700, 130])
+    x, _ = steps([50, 70], [1500, 300])
+    reads = [x, noisy.signal[0, :700], noisy.signal[1, :130], np.full(1000, 50.0)]
+    return batch_of(reads, kw_of(max_event_len=max_event_len))
+
+
+DENSE_T = 66000                         # 1032 words: more than one 1024-word step of the ranks launch
+DENSE_DWELLS = ((18, 25), (35, 41), (52, 61))                        # above 16 forced splits inside one 64-sample word at max_event_len 1, 2, 3
+
+
+def dense_splits_case(max_event_len):
+    """three noise-free reads of 66000 samples whose levels change every 18..24, 35..40 and 52..60 samples, run at max_event_len 1,
+    2 or 3: thousands of gaps per 1024-word step that lie inside one word and still hold more than 16 forced splits (up to 62)"""
+    rng = np.random.default_rng(51)
+    reads = []
+    for lo, hi in DENSE_DWELLS:
+        dwells = rng.integers(lo, hi, size=DENSE_T // lo + 1)
+        levels = 90.0 + 6.0 * (np.arange(len(dwells)) % 2) + rng.integers(0, 3, size=len(dwells))      # neighbours at least 4 apart
+        reads.append(steps(levels, dwells, DENSE_T)[0])
+    return batch_of(reads, kw_of(windows=(3, 0), max_event_len=max_event_len))
+
+
+def forced_large_case():
+    """constant reads of +-(2^23 - 1) with T = 2 * 65536 + 3: sums of squares of 65536 (2^23 - 1)^2, just below 2^62"""
+    T = 2 * 65536 + 3
+    return batch_of([np.full(T, float(QMAX)), np.full(T, float(-QMAX))], dict(HAND_KW, windows=(3, 0), max_events=8), pad=0,
+                    truth=[[(0, 0), (65536, 3), (131072, 3)]] * 2)
+
+
+BAD_READS = ("good", "nan_interior", "nan_on_seam", "nan_before_seam", "good_too", "nan_last", "range", "length_above", "length_negative",
+             "good_empty", "good_nan_past_the_read", "good_at_the_limit", "good_last")
+BAD_GOOD = {n for n in BAD_READS if n.startswith("good")}
+
+
+def bad_case():
+    case = noisy_reads(21, [600] * len(BAD_READS), L=604)
+    signal, sl = case.signal.copy(), case.signal_lengths.copy()
+    r = BAD_READS.index
+    signal[r("nan_interior"), 100] = np.nan
+    signal[r("nan_on_seam"), 256] = np.inf
+    signal[r("nan_before_seam"), 511] = np.nan
+    sl[r("nan_last")] = 300
+    signal[r("nan_last"), 299] = np.nan
+    signal[r("range"), 17] = 2048.0                                  # 2048 * 2^12 = 2^23: the first value out of range
+    sl[r("length_above")] = signal.shape[1] + 1
+    sl[r("length_negative")] = -1
+    sl[r("good_empty")] = 0
+    signal[r("good_empty"), 0] = np.nan                              # never read
+    sl[r("good_nan_past_the_read")] = 500
+    signal[r("good_nan_past_the_read"), 500:] = np.nan
+    signal[r("good_at_the_limit"), 40] = 2047.99
+    return Case(signal, sl, case.kw, None)
+
+
+def _cases():
+    c = {"lengths": noisy_reads(3, list(LENGTHS)), "seams": seam_case(), "halo": halo_case(), "merge": merge_case(), "ties": tie_case(),
+         "width": width_case(),
+         "noise_free": noise_free_case(), "forced_small": forced_small_case(), "forced_large": forced_large_case(),
+         "forced_gap_64": forced_gap_case(64), "forced_gap_5": forced_gap_case(5),
+         "dense_1": dense_splits_case(1), "dense_2": dense_splits_case(2), "dense_3": dense_splits_case(3), "bad": bad_case()}
+    c["truncated"] = Case(c["lengths"].signal, c["lengths"].signal_lengths, kw_of(max_events=7), None)
+    return c
+
+
+CASES = _cases()
+
+
+def detectors_of(kw):
+    return R.detectors(kw["windows"], kw["thresholds"], kw["radii"], kw["min_var"], kw["frac_bits"])
+
+
+def call_ref(case, signal=None, scale_shift=None, **how):
+    kw = case.kw
+    return R.event_detect_ref(case.signal if signal is None else signal, case.signal_lengths, detectors_of(kw), kw["frac_bits"],
+                              kw["max_event_len"], kw["max_events"], scale_shift=scale_shift, **how)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    return call_ref(CASES[name])
+
+
+def boundaries(ref, b):
+    """[(position, kind)] of read b of a reference (or of device outputs turned into the same dict)"""
+    n = int(ref["n_events"][b])
+    return [(int(ref["starts"][b, e]), int(ref["kind"][b, e])) for e in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def int16_form(name):
+    """(raw int16 [B, L], scale_shift float32 [B, 2]) of a case"""
+    case = CASES[name]
+    rng = np.random.default_rng(99)
+    raw = np.rint(case.signal.astype(np.float64) * 8.0).astype(np.int16)
+    B = raw.shape[0]
+    ss = np.stack([0.125 * (1.0 + 0.01 * rng.standard_normal(B)), 3.0 * rng.standard_normal(B)], axis=1).astype(np.float32)
+    return raw, ss
+
+
+@functools.lru_cache(maxsize=None)
+def int16_reference(name):
+    raw, ss = int16_form(name)
+    return call_ref(CASES[name], signal=raw, scale_shift=ss)
+
+
+# ---- composition: raw reads -> events -> signal_map -> signal_align, on reads whose bases nobody supplied
+COMPOSE_K, COMPOSE_STATES, COMPOSE_F = 3, 60, 12
+
+
+@functools.lru_cache(maxsize=None)
+def composition():
+    """A 2000-base random reference, a 3-mer table of pairwise distinct levels (quarter units, so every number is exact), and four
+    noise-free reads of 60 states from known loci of either strand, dwells in 13..39.  Returns a dict: bases, joined, means, stdvs,
+    signal [4, L] float32, signal_lengths, start_state (in the joined sequence), strand, dwells."""
+    from tests import signal_map_ref as M
+    from tests.kmer_events_ref import kmer_index
+    rng = np.random.default_rng(31)
+    bases = rng.integers(1, 5, size=2000).astype(np.int32)
+    for i in range(COMPOSE_K, len(bases)):                           # no base four times in a row: consecutive 3-mers differ
+        if (bases[i - COMPOSE_K:i] == bases[i]).all():
+            bases[i] = bases[i] % 4 + 1
+    joined = np.array(M.join_strands(bases.tolist()), dtype=np.int32)
+    means = 60.0 + 0.25 * rng.permutation(4 ** COMPOSE_K) * 3.0      # steps of 0.75 at the least
+    stdvs = np.full(4 ** COMPOSE_K, 1.5)
+    picks = [(300, 0), (1500, 1), (42, 1), (1900, 0)]
+    start_state = np.array([p if s == 0 else 2001 + p for p, s in picks], dtype=np.int64)
+    reads, dwells = [], []
+    for s in start_state:
+        codes = [kmer_index(joined[j:j + COMPOSE_K].tolist()) for j in range(s, s + COMPOSE_STATES)]
+        d = rng.integers(13, 40, size=COMPOSE_STATES)
+        reads.append(np.repeat(means[codes], d))
+        dwells.append(d)
+    case = batch_of(reads, kw_of(frac_bits=COMPOSE_F, max_events=COMPOSE_STATES + 4))
+    return dict(bases=bases, joined=joined, means=means, stdvs=stdvs, signal=case.signal, signal_lengths=case.signal_lengths, kw=case.kw,
+                start_state=start_state, strand=np.array([s for _, s in picks]), dwells=np.array(dwells))

@@ -20,6 +20,14 @@ align -> kmer_events -> fit_kmer_model -> align again is Viterbi training of the
     al = signal_align(reads.signal, reads.signal_lengths, reads.bases, reads.base_lengths, model, first=2, band=128)
     ev = kmer_events(reads.signal, reads.signal_lengths, reads.bases, reads.base_lengths, starts=al.starts, k=al.k, first=al.first)
     model = signal_model(*fit_kmer_model(ev.kmer_stats, prior=standin_kmer_table())[:2])
+
+Where not even the bases exist, detect_events (csrc/wn_eventdetect.hip through wn_event_detect) cuts a bare read
+into events -- where its level changes, by Welch's t^2 at two window lengths -- and its event means are a shorter read for
+mapping.signal_map and signal_align:
+
+    found = detect_events(signal, signal_lengths, max_events=4096)                         # n_events, starts, sum, sumsq, kind
+    means, counts = found.as_signal()
+    hit = signal_map(means, counts, map_reference(lambda_bases, model))                    # 4096 events instead of 4096 samples
 """
 import math
 from collections import namedtuple
@@ -419,7 +427,8 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
     `band` k-mers around the diagonal.
 
     signal          [B, L] or [B, 1, L], float32 or int16; a view is passed by its row stride (unit stride along L)
-    signal_lengths  [B]; labels [B, n] bases in 1..4 (int32 or int64) with label_lengths [B]
+    signal_lengths  [B]; labels [B, n] bases in 1..4 (int32 or int64) with label_lengths [B].  The event means of
+                    detect_events(...).as_signal() go in as a shorter read: one row per event instead of one per sample
     model           a SignalModel (signal_model(means, stdvs), or filled by hand); its k and frac_bits are the call's
     first           read b has label_lengths[b] - (k - 1) - 2 first states, state j the k-mer labels[j + first .. j + first + k);
                     first = 2 / 0: the generator's "loader" / "generator" windows
@@ -464,3 +473,135 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
                        "a non-finite or out-of-range sample or a model row out of range" % n)
     return SignalAlignment(starts, score, band_hits, states, k=k, first=first, frac_bits=model.frac_bits, cost_bits=model.cost_bits,
                            band=band)
+
+
+MAX_DETECT_WINDOW, MAX_DETECT_RADIUS, MAX_DETECT_VMIN, MAX_EVENT_LEN = 16, 64, 1 << 55, 65536
+MAX_DETECT_SIGNAL = MAX_DETECT_EVENTS = 1 << 24
+MIN_CHUNK, MAX_CHUNK = 256, 16384
+DEFAULT_THRESHOLDS, DEFAULT_MIN_VAR = (4.0, 6.0), 0.01
+
+_DetectFields = namedtuple("DetectedEvents", "n_events starts sum sumsq kind")
+
+
+class DetectedEvents(_DetectFields):
+    """n_events [B] int32: the events of each read -- the true count, even above max_events (the rows then hold the first
+    max_events events whole), -1 for a bad read; starts [B, max_events + 1] int32: event e is the samples [starts[b, e],
+    starts[b, e + 1]), every entry past the last event is signal_lengths[b] (SignalAlignment.starts' convention, so it goes into
+    kmer_events(starts=...) as it is); sum, sumsq [B, max_events] int64: the sums of q = round(v 2^frac_bits) and of q^2 over the
+    event, 0 past the last one; kind [B, max_events] int32: why the event begins -- 0 the read's start, 1 a peak of the short
+    detector, 2 of the long one, 3 a forced split -- and -1 past the last event.  A bad read: starts -1, sums 0, kind -1.  Device
+    tensors.  frac_bits and max_events of the call ride along as attributes."""
+
+    def __new__(cls, *fields, frac_bits=12):
+        self = super().__new__(cls, *fields)
+        self.frac_bits, self.max_events = int(frac_bits), int(fields[2].shape[1])
+        return self
+
+    @property
+    def held(self):
+        """[B] int32: the events the rows hold, min(n_events, max_events); 0 for a bad read"""
+        return self.n_events.clamp(min=0, max=self.max_events)
+
+    @property
+    def truncated(self):
+        """[B] bool: the read has more events than the rows hold"""
+        return self.n_events > self.max_events
+
+    @property
+    def length(self):
+        """[B, max_events] int32: the samples of every event, 0 past the last one"""
+        e = torch.arange(self.max_events, device=self.starts.device)[None, :]
+        return torch.where(e < self.held[:, None], self.starts[:, 1:] - self.starts[:, :-1], torch.zeros_like(self.kind))
+
+    @property
+    def mean(self):
+        """[B, max_events] float64: the level of every event in the units of v, NaN past the last one (one division of exact
+        integers)"""
+        return self.sum.double() / (self.length.double() * float(1 << self.frac_bits))
+
+    @property
+    def stdv(self):
+        """[B, max_events] float64: the population standard deviation of every event, NaN past the last one; formed as
+        KmerEvents.stdv"""
+        n = self.length.double()
+        m = self.sum.double() / n
+        var = (self.sumsq.double() / n - m * m).clamp_(min=0.0)
+        return var.sqrt() / float(1 << self.frac_bits)
+
+    def as_signal(self):
+        """(means [B, max_events] float32, lengths [B] int32): the event means as a shorter "read" -- 0 past the last event, and
+        `held` events per read -- for signal_map and signal_align in place of the samples"""
+        return torch.nan_to_num(self.mean, nan=0.0).float(), self.held.int()
+
+
+def detect_events(signal, signal_lengths, scale_shift=None, frac_bits=12, windows=(3, 6), thresholds=DEFAULT_THRESHOLDS, radii=None,
+                  min_var=DEFAULT_MIN_VAR, max_event_len=65536, max_events=None, chunk=None):
+    """Event detection: where the level of a raw read changes, from the samples alone -- no bases, no
+    network, no model -- and the table of the events between the changes.
+
+    signal          [B, L] or [B, 1, L], float32 or int16; a view is passed by its row stride (unit stride along L)
+    signal_lengths  [B]; scale_shift [B, 2] float32 or None, frac_bits: as kmer_events (q = round(v 2^frac_bits), |q| < 2^23)
+    windows         (w_short, w_long), 1..16; w_long = 0 switches the long detector off.  The score of a position is Welch's t^2
+                    between the w samples before it and the w samples from it on
+    thresholds      (t_short, t_long) on t, as scrappie's; a position passes iff its t^2 is at least round(t^2 256) / 256
+    radii           (r_short, r_long), 1..64 (None: the windows): a peak is the arg-max of its +-r neighbourhood, ties to the
+                    smaller index
+    min_var         the floor on var_1 + var_2 of the two windows in the units of v^2: a noise-free step has a finite score
+    max_event_len   1..65536: a longer event is split every max_event_len samples
+    max_events      the events the rows hold per read (None: L, which is always enough); n_events is the true count regardless
+    chunk           the positions one workgroup decides, a multiple of 256 in [256, 16384] (None: chosen from L and B).  A tuning
+                    argument: no output depends on it
+    The boundaries are position 0, every short peak and every long peak with no short peak within +-w_long.  Integer arithmetic,
+    exact 128-bit comparisons, bitwise reproducible, no host synchronisation (capturable with fixed shapes).  A bad read (a
+    length out of range, a non-finite or out-of-range sample before signal_lengths[b]) is reported through check_device_flags().
+    HIP only.  Returns DetectedEvents; its as_signal() goes into signal_map / signal_align as a read of event means."""
+    what = "detect_events"
+    signal = _args.signal_rows(signal, what)
+    dev = signal.device
+    B, L = int(signal.shape[0]), int(signal.shape[1])
+    with torch.cuda.device(dev):
+        signal_lengths = _args.lengths(signal_lengths, B, dev, what, "signal_lengths", flatten=True)
+        scale_shift = _args.scale_shift(scale_shift, B, dev, what)
+    F = int(frac_bits)
+    radii = windows if radii is None else radii
+    try:
+        (w0, w1), (r0, r1), (t0, t1) = (int(v) for v in windows), (int(v) for v in radii), (float(v) for v in thresholds)
+    except (TypeError, ValueError):
+        raise ValueError("wavenet_speech_amd.%s: windows, thresholds and radii must be pairs (short, long)" % what) from None
+    if not 0 <= F <= MAX_FRAC_BITS or not 1 <= w0 <= MAX_DETECT_WINDOW or not 0 <= w1 <= MAX_DETECT_WINDOW:
+        raise ValueError("wavenet_speech_amd.%s: frac_bits in [0, %d], windows[0] in [1, %d], windows[1] in [0, %d]"
+                         % (what, MAX_FRAC_BITS, MAX_DETECT_WINDOW, MAX_DETECT_WINDOW))
+    if w1 == 0:
+        r1, t1 = 1, 1.0                                              # unused
+    min_var = float(min_var)
+    if not all(1 <= r <= MAX_DETECT_RADIUS for r in (r0, r1)) or not all(math.isfinite(t) and t > 0 for t in (t0, t1)) \
+            or not (math.isfinite(min_var) and min_var >= 0):
+        raise ValueError("wavenet_speech_amd.%s: radii in [1, %d], thresholds finite and positive, min_var finite and >= 0"
+                         % (what, MAX_DETECT_RADIUS))
+    theta = [max(1, round(t * t * 256)) for t in (t0, t1)]
+    vmin = [max(1, round(min_var * 4 ** F * w * w)) for w in (w0, max(w1, 1))]
+    if max(theta) >= 2 ** 31 or max(vmin) > MAX_DETECT_VMIN:
+        raise ValueError("wavenet_speech_amd.%s: round(t^2 256) must stay below 2^31 and round(min_var 4^frac_bits w^2) within 2^55" % what)
+    max_event_len = int(max_event_len)
+    N = L if max_events is None else int(max_events)
+    chunk = 0 if chunk is None else int(chunk)
+    chunk_ok = chunk == 0 or (chunk % 256 == 0 and MIN_CHUNK <= chunk <= MAX_CHUNK)
+    if not 1 <= max_event_len <= MAX_EVENT_LEN or not 1 <= N <= MAX_DETECT_EVENTS or not chunk_ok:
+        raise ValueError("wavenet_speech_amd.%s: max_event_len in [1, %d], max_events in [1, 2^24], chunk None or a multiple of 256 in "
+                         "[%d, %d]" % (what, MAX_EVENT_LEN, MIN_CHUNK, MAX_CHUNK))
+    if L > MAX_DETECT_SIGNAL or B > 65535:
+        raise ValueError("wavenet_speech_amd.%s: at most 2^24 samples per read and 65535 reads, got %d and %d" % (what, L, B))
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        n_events, starts, kind = torch.empty(B, **i32), torch.empty(B, N + 1, **i32), torch.empty(B, N, **i32)
+        ev_sum, ev_sumsq = torch.empty(B, N, **i64), torch.empty(B, N, **i64)
+        bad = torch.zeros(1, **i32)
+        ws = _alloc_bytes(lib.wn_event_detect_workspace_bytes(B, L), "wn_event_detect_workspace_bytes", dev, status=-2)
+        _lib.check(lib.wn_event_detect(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
+                                       B, L, F, w0, w1, r0, r1, theta[0], theta[1], vmin[0], vmin[1], max_event_len, N, chunk,
+                                       _p(n_events), _p(starts), _p(ev_sum), _p(ev_sumsq), _p(kind), _p(ws), ws.numel(), _p(bad),
+                                       _stream()), "wn_event_detect")
+        _args.note_bad(bad, lambda n: "wavenet_speech_amd.detect_events: %d bad read(s): a length out of range or a non-finite or "
+                       "out-of-range sample" % n)
+    return DetectedEvents(n_events, starts, ev_sum, ev_sumsq, kind, frac_bits=F)

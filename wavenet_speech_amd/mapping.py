@@ -153,7 +153,8 @@ def signal_map(signal, signal_lengths, reference, scale_shift=None, max_cost=Non
     stepping to the next one (no skips), never through a break.
 
     signal          [B, L] or [B, 1, L], float32 or int16, L <= 4096; a view is passed by its row stride (unit stride along L)
-    signal_lengths  [B]: the samples of each read that are mapped (hand in the prefix you want mapped: about a second of signal)
+    signal_lengths  [B]: the samples of each read that are mapped (hand in the prefix you want mapped: about a second of signal).
+                    The event means of detect_events(...).as_signal() are such a read too: 4096 events instead of 4096 samples
     reference       a MapReference (map_reference(bases, model)) on the signal's device
     scale_shift     [B, 2] float32 or None, as kmer_events and signal_align
     max_cost        the clamp of a sample's quadratic term, in [1, 2^31 - 1] (None: 2^31 - 1), as signal_align
