@@ -725,6 +725,66 @@ int wn_event_detect(const void* signal, int signal_kind, long long signal_stride
                     int* n_events, int* starts, long long* ev_sum, long long* ev_sumsq, int* ev_kind /* may be NULL */,
                     void* workspace, size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Event alignment with skips (wavenet_speech_amd.events.event_align): the DETECTED events of a read
+ * against the k-mers of its KNOWN bases.  An event may stay in the k-mer of the event before it (the detector cut one k-mer in
+ * two), step to the next one, or skip one or two k-mers (the detector missed boundaries), and an event's cost weighs its length:
+ * what nanopolish `eventalign` does, and what wn_signal_align, which never skips, cannot do for a read with fewer events than
+ * k-mers.  All pointers are DEVICE pointers.
+ * Events of read b: n_events [B] int32, ev_starts [B][max_events + 1] int32, ev_sum and ev_sumsq [B][max_events] int64 -- exactly
+ * what wn_event_detect writes.  E_b = n_events[b]; event e has n = ev_starts[e + 1] - ev_starts[e] samples, S = ev_sum[e] (the sum
+ * of its quantised samples q) and Q = ev_sumsq[e] (of q^2); T_b = ev_starts[E_b].  A caller whose table is truncated passes
+ * min(n_events, max_events).
+ * Bases: labels, labels_stride, label_lengths, k, first as wn_signal_align: N_b = label_lengths[b] - (k - 1) - 2 first STATES, state
+ * j the k-mer labels[j + first .. j + first + k), index sum_i (label_i - 1) 4^(k-1-i).
+ * Model: model [4^k][3] int32 (level, weight, offset), frac_bits F, weight_shift S and max_cost as wn_signal_align (F only says
+ * in what units the events and the levels are; it is range-checked and otherwise unused).
+ * Moves: move_cost0 .. move_cost3, the cost of advancing by 0 (stay), 1 (step), 2 or 3 states between consecutive events, each
+ * in [0, 2^30) or -1 for a move that is FORBIDDEN; the step must be allowed.
+ * Arithmetic (the definition; tests/event_align_ref.py mirrors it in Python integers).  In a state with the row (level, weight,
+ * offset), D = Q - 2 level S + n level^2, the exact sum of (q - level)^2 over the event's samples; 0 <= D < 65536 (2^24 - 2)^2 <
+ * 2^64 for a valid event, so D is formed modulo 2^64.  The cost of the event in the state is
+ *   min((D weight) >> S, n max_cost) + n offset,
+ * the product in full (95 bits) and compared before it is narrowed.  For n = 1 this is wn_signal_align's cost of the sample q.
+ * A path gives every event a state: s_0 = 0, s_(E-1) = N - 1, s_e - s_(e-1) in {0, 1, 2, 3} and allowed.  Its cost is the sum of
+ * its event costs and of move_cost[s_e - s_(e-1)] over e >= 1 (below 2^24 (2^31 + 2^30) + 2^20 2^30 in magnitude: int64).  The
+ * result is the minimum-cost path INSIDE THE BAND, W = band:
+ *   c(e) = ((2 e + 1) N) / (2 E) in 64-bit integer division;   lo(e) = clamp(c(e) - W / 2, 0, max(N - W, 0));
+ *   state j is allowed at event e if and only if lo(e) <= j < lo(e) + W.
+ * Ties: at (e, j) the stay is taken first, then each larger move only if strictly cheaper, its move cost included.
+ * Outputs:
+ *   starts        [B][max_states + 1] int32   starts[j] = the first SAMPLE of state j (ev_starts of its first event), the
+ *                 convention of wn_reads_plan; a skipped state is empty, starts[j] = starts[j + 1]; every entry j >= N_b is T_b.
+ *                 It goes into wn_kmer_events as it stands
+ *   score         [B] int64   the cost of the path
+ *   event_state   [B][max_events] int32, may be NULL   the state of every event, -1 past E_b
+ *   move_counts   [B][4] int32   the events that arrived by each move: 1 + sum = E_b, counts[1] + 2 counts[2] + 3 counts[3] = N_b - 1
+ *   band_hits     [B] int32   the events e whose state is lo(e) with lo(e) > 0, or lo(e) + W - 1 with lo(e) + W < N
+ * Checked on the device, in this order.  (1) A read is BAD when n_events[b] is outside [0, max_events], label_lengths[b] outside
+ * [0, max_labels] or N_b > max_states (nothing else of it is then read): score LLONG_MIN, every other output -1, counted once in
+ * *bad (DEVICE int, caller-zeroed, may be NULL).  (2) E_b < 1, N_b < 1 or N_b - 1 > (the largest allowed move) (E_b - 1) gives
+ * NO ALIGNMENT: score LLONG_MAX, starts and event_state -1, move_counts and band_hits 0; nothing else of it is read and it is not
+ * bad.  (3) Every other read is bad (as above) when a label in labels[first .. first + N_b + k - 1) is outside 1..4, the model
+ * row of one of its k-mers has weight < 1, |level| >= 2^23 or |offset| >= 2^30, ev_starts[0] < 0 or T_b > 2^24, or an event in
+ * [0, E_b) has n outside [1, 65536], |S| > n (2^23 - 1), Q < 0, Q > n (2^23 - 1)^2 or S^2 > n Q (compared exactly in 128 bits:
+ * this is what makes D >= 0).  (4) A good read with no allowed path inside the band gives no alignment.  No bad value is used as
+ * an index; events past E_b are never read.
+ * One launch, one workgroup per read: E_b sequential steps over band / 8 threads, then the trace.  Integer arithmetic only, two
+ * runs are bitwise identical; nothing is read back and nothing is allocated, so the call can be captured into a HIP graph.
+ * workspace: wn_event_align_workspace_bytes(batch, max_events, band) bytes, 16-byte aligned (2 bits per event and band slot); 0
+ * for an argument out of range.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_events, max_labels or max_states < 1, a negative
+ * stride.  WN_ERR_UNSUPPORTED: k outside 1..6, first outside 0..8, F outside 0..20, S outside 16..63, max_cost < 1, band not a
+ * multiple of 64 in [64, 2048], move_cost1 < 0, a move cost that is neither -1 nor in [0, 2^30), batch > 65535, max_events or
+ * max_states > 2^20.  WN_ERR_NULL: n_events, ev_starts, ev_sum, ev_sumsq, labels, label_lengths, model, starts, score,
+ * move_counts, band_hits or the workspace.  WN_ERR_WORKSPACE: a workspace too small or not 16-byte aligned. */
+size_t wn_event_align_workspace_bytes(int batch, int max_events, int band);
+int wn_event_align(const int* n_events, const int* ev_starts, const long long* ev_sum, const long long* ev_sumsq,
+                   const int* labels, long long labels_stride, const int* label_lengths, const int* model, int batch,
+                   int max_events, int max_labels, int max_states, int k, int first, int frac_bits, int weight_shift, int max_cost,
+                   int band, int move_cost0, int move_cost1, int move_cost2, int move_cost3, int* starts, long long* score,
+                   int* event_state /* may be NULL */, int* move_counts, int* band_hits, void* workspace, size_t workspace_bytes,
+                   int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

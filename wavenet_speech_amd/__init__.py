@@ -24,6 +24,7 @@ from .normalise import read_med_mad, read_normalisation, read_order_statistics, 
 from .events import KmerEvents, eventalign_rows, fit_dwell_model, fit_kmer_model, kmer_events  # noqa: F401
 from .events import SignalAlignment, SignalModel, signal_align, signal_model  # noqa: F401
 from .events import DetectedEvents, detect_events  # noqa: F401
+from .events import DEFAULT_MOVES, EventAlignment, event_align, fit_moves, move_costs  # noqa: F401
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

@@ -28,6 +28,14 @@ mapping.signal_map and signal_align:
     found = detect_events(signal, signal_lengths, max_events=4096)                         # n_events, starts, sum, sumsq, kind
     means, counts = found.as_signal()
     hit = signal_map(means, counts, map_reference(lambda_bases, model))                    # 4096 events instead of 4096 samples
+
+On noisy reads the detector misses boundaries, so a read has fewer events than k-mers and signal_align, which never skips, has no
+alignment for it.  event_align (csrc/wn_eventalign.hip through wn_event_align) aligns the events themselves --
+stay, step, or skip one or two k-mers, an event's cost weighing its length -- and its starts, in samples, go into kmer_events:
+
+    al = event_align(found, bases, base_lengths, model, first=2)                           # EventAlignment: starts, score, moves
+    ev = kmer_events(signal, signal_lengths, bases, base_lengths, starts=al.starts, k=al.k, first=al.first)
+    al = event_align(found, bases, base_lengths, model, first=2, moves=fit_moves(al.moves))
 """
 import math
 from collections import namedtuple
@@ -605,3 +613,164 @@ def detect_events(signal, signal_lengths, scale_shift=None, frac_bits=12, window
         _args.note_bad(bad, lambda n: "wavenet_speech_amd.detect_events: %d bad read(s): a length out of range or a non-finite or "
                        "out-of-range sample" % n)
     return DetectedEvents(n_events, starts, ev_sum, ev_sumsq, kind, frac_bits=F)
+
+
+MAX_MOVE_COST = 1 << 30
+DEFAULT_MOVES = (0.14, 0.62, 0.20, 0.04)
+
+_EventAlignFields = namedtuple("EventAlignment", "starts score band_hits moves states")
+
+
+class EventAlignment(_EventAlignFields):
+    """starts [B, N + 1] int32: starts[b, j] is the first SAMPLE of state (k-mer) j -- RaggedReads.starts' convention, so it goes
+    into kmer_events(starts=...) as it is; a skipped state is empty (starts[b, j] == starts[b, j + 1]; kmer_events gives it the code
+    -2 and does not call the read bad) and every entry past the read's last state is the read's last sample + 1; score [B] int64: the
+    cost of the path, move costs included, LLONG_MAX where there is no alignment and LLONG_MIN for a bad read; band_hits [B] int32:
+    the events whose state lies on the band's edge while the band could still have been wider there; moves [B, 4] int32: the events
+    that arrived by a stay, a step, a skip of one and a skip of two k-mers (1 + their sum is the read's events); states
+    [B, max_events] int32 with want_states, else None: the state of every event, -1 past the read's events.  No alignment: starts
+    and states -1, band_hits and moves 0; a bad read: everything -1.  Device tensors.  k, first, frac_bits, cost_bits, band and
+    move_costs (the four integers the call ran with) ride along as attributes."""
+
+    def __new__(cls, *fields, k=5, first=0, frac_bits=12, cost_bits=8, band=512, move_costs=(0, 0, 0, 0)):
+        self = super().__new__(cls, *fields)
+        self.k, self.first, self.frac_bits, self.cost_bits, self.band = int(k), int(first), int(frac_bits), int(cost_bits), int(band)
+        self.move_costs = tuple(int(c) for c in move_costs)
+        return self
+
+    @property
+    def nats(self):
+        """[B] float64: score / 2^cost_bits (+-inf-like sentinels stay huge: mask with score first)"""
+        return self.score.double() / float(1 << self.cost_bits)
+
+
+def move_costs(probs, cost_bits=8):
+    """The four integer move costs of event_align from the probabilities of advancing by 0 (stay), 1 (step), 2 and 3 k-mers
+    between consecutive events: round(-ln p * 2^cost_bits), ties to even, in the units of a SignalModel with the same cost_bits;
+    p = 0 forbids the move (-1).  The four need not sum to one.  Refused: anything but four finite values in [0, 1], a forbidden
+    step, a cost at or above 2^30."""
+    what = "move_costs"
+    try:
+        pp = [float(p) for p in probs]
+    except (TypeError, ValueError):
+        raise ValueError("wavenet_speech_amd.%s: probs must be four numbers" % what) from None
+    cb = int(cost_bits)
+    if len(pp) != 4 or not all(math.isfinite(p) and 0.0 <= p <= 1.0 for p in pp) or not 0 <= cb <= 16:
+        raise ValueError("wavenet_speech_amd.%s: four finite probabilities in [0, 1] and cost_bits in [0, 16]" % what)
+    if pp[1] == 0.0:
+        raise ValueError("wavenet_speech_amd.%s: the step (probs[1]) cannot be forbidden" % what)
+    out = tuple(-1 if p == 0.0 else round(-math.log(p) * (1 << cb)) + 0 for p in pp)          # + 0: no negative zero
+    if max(out) >= MAX_MOVE_COST:
+        raise ValueError("wavenet_speech_amd.%s: a move cost at or above 2^30" % what)
+    return out
+
+
+def fit_moves(move_counts):
+    """The frequencies of the four moves over the good reads of an alignment: move_counts is EventAlignment.moves ([B, 4]
+    integers; reads with a negative row -- bad ones -- are left out, reads without an alignment add nothing).  Returns four floats
+    that sum to one, for event_align(moves=...): align -> fit_moves -> align re-estimates the move probabilities as align ->
+    kmer_events -> fit_kmer_model re-estimates the table.  Raises if no move was counted or no step was."""
+    rows = _host_table(move_counts, "fit_moves", "move_counts", 4)
+    total = [sum(r[m] for r in rows if min(r) >= 0) for m in range(4)]
+    if sum(total) < 1 or total[1] < 1:
+        raise ValueError("wavenet_speech_amd.fit_moves: no move, or no step, among the good reads")
+    return tuple(t / sum(total) for t in total)
+
+
+def event_align(events, labels, label_lengths, model, first=0, band=512, moves=DEFAULT_MOVES, max_cost=None, want_states=False,
+                frac_bits=None):
+    """Align DETECTED events to the k-mers of known bases under a SignalModel: the minimum-cost path in
+    which an event stays in the k-mer of the event before it (the detector cut one k-mer in two), steps to the next, or skips one
+    or two k-mers (the detector missed boundaries), inside a band of `band` k-mers around the diagonal.  What nanopolish
+    `eventalign` does; signal_align, which never skips, has no alignment for a read with fewer events than k-mers.
+
+    events          a DetectedEvents (detect_events' result), or the tuple (n_events [B], starts [B, M + 1], sum [B, M], sumsq
+                    [B, M]) with frac_bits=.  Of a DetectedEvents its `held` is passed as the count: a read that detection called
+                    bad has no events and gets no alignment; a truncated read aligns the events its rows hold
+    labels          [B, n] bases in 1..4 (int32 or int64) with label_lengths [B]
+    model           a SignalModel; its k is the call's and its frac_bits must be the events'
+    first           read b has label_lengths[b] - (k - 1) - 2 first states, as signal_align
+    band            a multiple of 64 in [64, 2048]; state j is allowed at event e iff lo(e) <= j < lo(e) + band, lo(e) =
+                    clamp(((2 e + 1) N) // (2 E) - band / 2, 0, max(N - band, 0))
+    moves           four probabilities (floats), turned into costs by move_costs(moves, model.cost_bits), or four ints taken as
+                    costs as they are (-1 forbids a move).  DEFAULT_MOVES = (0.14, 0.62, 0.20, 0.04): the stay and the total skip
+                    mass are read off one sweep of the detector at noise 1.5 (14 % of the detected boundaries spurious, 28 % of
+                    the true ones missed -- the latter a rate per true boundary used as a rate per event, an approximation) and
+                    the split of the skips between one and two k-mers is a guess.  Nothing derives these numbers: fit_moves on a
+                    first alignment gives the data's own
+    max_cost        the clamp of a SAMPLE's quadratic term, in [1, 2^31 - 1] (None: 2^31 - 1); an event of n samples is clamped
+                    at n max_cost
+    want_states     also return the state of every event
+    An event of n samples with sum S and sum of squares Q costs min((Q - 2 level S + n level^2) weight >> weight_shift,
+    n max_cost) + n offset in a state: the exact sum of what signal_align charges its samples, up to one floor instead of n.
+    Integer arithmetic, ties to the smallest move, bitwise reproducible, no host synchronisation (capturable with fixed shapes
+    once the model has been used on the device).  A bad read (a length out of range, a label of the used window outside 1..4, a
+    model row out of range, an event table that no samples could have made) is reported through check_device_flags().  HIP only.
+    Returns EventAlignment."""
+    what = "event_align"
+    if isinstance(events, DetectedEvents):
+        if frac_bits is not None and int(frac_bits) != events.frac_bits:
+            raise ValueError("wavenet_speech_amd.%s: frac_bits=%d, but the events were made with %d" % (what, int(frac_bits), events.frac_bits))
+        count, ev_starts, ev_sum, ev_sumsq, F = events.held, events.starts, events.sum, events.sumsq, events.frac_bits
+    else:
+        if not isinstance(events, (tuple, list)) or len(events) != 4 or frac_bits is None:
+            raise ValueError("wavenet_speech_amd.%s: events must be a DetectedEvents, or (n_events, starts, sum, sumsq) with frac_bits=" % what)
+        count, ev_starts, ev_sum, ev_sumsq = events
+        F = int(frac_bits)
+    if not isinstance(model, SignalModel):
+        raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
+    if F != model.frac_bits:
+        raise ValueError("wavenet_speech_amd.%s: the events have frac_bits %d and the model %d" % (what, F, model.frac_bits))
+    first, band = int(first), int(band)
+    max_cost = 2 ** 31 - 1 if max_cost is None else int(max_cost)
+    if not 0 <= first <= MAX_FIRST or not MIN_BAND <= band <= MAX_BAND or band % 64 or not 1 <= max_cost <= 2 ** 31 - 1:
+        raise ValueError("wavenet_speech_amd.%s: first in [0, %d], band a multiple of 64 in [%d, %d], max_cost in [1, 2^31 - 1]"
+                         % (what, MAX_FIRST, MIN_BAND, MAX_BAND))
+    try:
+        moves = tuple(moves)
+    except TypeError:
+        raise ValueError("wavenet_speech_amd.%s: moves must be four probabilities or four integer costs" % what) from None
+    if len(moves) == 4 and all(isinstance(m, int) and not isinstance(m, bool) for m in moves):
+        costs = moves
+        if costs[1] < 0 or not all(c == -1 or 0 <= c < MAX_MOVE_COST for c in costs):
+            raise ValueError("wavenet_speech_amd.%s: a move cost is -1 (forbidden) or in [0, 2^30), and the step's is not -1" % what)
+    else:
+        costs = move_costs(moves, model.cost_bits)
+    ev_starts = _args.gpu_tensor(ev_starts, what, "events.starts", (torch.int32,), ValueError)
+    dev = ev_starts.device
+    if ev_starts.dim() != 2 or ev_starts.shape[1] < 2:
+        raise ValueError("wavenet_speech_amd.%s: events.starts must be [B, max_events + 1 >= 2], got %s" % (what, tuple(ev_starts.shape)))
+    B, M = int(ev_starts.shape[0]), int(ev_starts.shape[1]) - 1
+    ev_starts = ev_starts.contiguous()
+    sums = []
+    for name, t in (("sum", ev_sum), ("sumsq", ev_sumsq)):
+        t = _args.gpu_tensor(t, what, "events." + name, (torch.int64,), ValueError, dev)
+        if tuple(t.shape) != (B, M):
+            raise ValueError("wavenet_speech_amd.%s: events.%s must be [%d, %d], got %s" % (what, name, B, M, tuple(t.shape)))
+        sums.append(t.contiguous())
+    labels = _args.int_rows(labels, what, "labels", B=B, shape="(%d, n >= 1)" % B, min_width=1, device=dev)
+    with torch.cuda.device(dev):
+        count = _args.lengths(count, B, dev, what, "n_events", flatten=True)
+        label_lengths = _args.lengths(label_lengths, B, dev, what, "label_lengths", flatten=True)
+    k = model.k
+    N = max(int(labels.shape[1]) - (k - 1) - 2 * first, 1)
+    if M > MAX_ALIGN_EVENTS or N > MAX_ALIGN_EVENTS or B > 65535:
+        raise ValueError("wavenet_speech_amd.%s: at most 2^20 events and 2^20 k-mers per read and 65535 reads" % what)
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        table = model.on(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        starts = torch.empty(B, N + 1, **i32)
+        score = torch.empty(B, dtype=torch.int64, device=dev)
+        band_hits, counts = torch.empty(B, **i32), torch.empty(B, 4, **i32)
+        states = torch.empty(B, M, **i32) if want_states else None
+        bad = torch.zeros(1, **i32)
+        ws = _alloc_bytes(lib.wn_event_align_workspace_bytes(B, M, band), "wn_event_align_workspace_bytes", dev, status=-2)
+        _lib.check(lib.wn_event_align(_p(count), _p(ev_starts), _p(sums[0]), _p(sums[1]), _p(labels), labels.stride(0), _p(label_lengths),
+                                      _p(table), B, M, int(labels.shape[1]), N, k, first, F, model.weight_shift, max_cost, band, costs[0],
+                                      costs[1], costs[2], costs[3], _p(starts), _p(score), _p(states), _p(counts), _p(band_hits), _p(ws),
+                                      ws.numel(), _p(bad), _stream()), "wn_event_align")
+        _args.note_bad(bad, lambda n: "wavenet_speech_amd.event_align: %d bad read(s): a length out of range, a label outside 1..4, a model "
+                       "row out of range or an event whose length, sum and sum of squares no samples could have made" % n)
+    return EventAlignment(starts, score, band_hits, counts, states, k=k, first=first, frac_bits=F, cost_bits=model.cost_bits, band=band,
+                          move_costs=costs)
