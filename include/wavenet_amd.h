@@ -785,6 +785,50 @@ int wn_event_align(const int* n_events, const int* ev_starts, const long long* e
                    int* event_state /* may be NULL */, int* move_counts, int* band_hits, void* workspace, size_t workspace_bytes,
                    int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Barcode demultiplexing and adapter trimming of decoded reads (csrc/wn_demux.hip): which sample a
+ * read belongs to, and where its adapters and barcodes end -- what guppy, dorado, porechop and qcat do right after basecalling.
+ * Two launches; all pointers are DEVICE pointers; int32 and exact.
+ *   wn_demux_scores: SEMI-GLOBAL alignment with affine gaps of each of K patterns against the front or the rear WINDOW of each of
+ *   B reads.  labels [B] rows of labels_stride elements with lengths [B] (the decoders' rows, read in place): int32, compared for
+ *   equality only; values past lengths[b] are never read.  patterns [K] rows of pattern_stride elements with pattern_lengths [K];
+ *   patterns [0, n_front) belong to the FRONT of the read, [n_front, K) to its REAR (the caller sorts them by end).  For a read of
+ *   length n the front window is labels[0 .. min(n, window)), the rear window labels[max(0, n - window) .. n).
+ *   The pattern (rows i = 1..P) is consumed whole; its start and end in the window (columns j = 1..W) are free.  A gap of n columns
+ *   costs gap_open + (n - 1) gap_extend.  Every cell is a pair (score, start) and every maximum is lexicographic on (score, -start):
+ *     H[0][j] = (0, j);  H[i][0] = F[i][0] = (-(go + (i-1) ge), 0);  E[0][j] = F[0][j] = E[i][0] = -infinity
+ *     E[i][j] = max(H[i][j-1] - go, E[i][j-1] - ge);   F[i][j] = max(H[i-1][j] - go, F[i-1][j] - ge)
+ *     H[i][j] = max(H[i-1][j-1] + (equal ? match : mismatch), E[i][j], F[i][j])
+ *     result  = max over j in [0, W] of (H[P][j].score, -start, -j)
+ *   which does not depend on the order of the candidates: the greatest score over all semi-global alignments, among those the
+ *   smallest start, then the smallest end (tests/demux_ref.py holds the same definition).
+ *   score, start, end [B][K] int32: start and end = j in READ coordinates, end exclusive; start == end: the pattern met only gaps.
+ *   A read length outside [0, max_len] poisons its row, a pattern length outside [1, max_pattern_len] its column: score INT_MIN,
+ *   start and end -1, every poisoned entry counted in *bad (DEVICE int, caller-zeroed, may be NULL); no bad value is used as an
+ *   index.  Length 0 is valid: the window is empty and every score is -(go + (P-1) ge).
+ *   Limits: window <= 512, n_patterns <= 1024, max_pattern_len <= 128, max_len <= 2^24, batch <= 65535, 0 <= gap_extend <= gap_open
+ *   <= 1024, |match|, |mismatch| <= 1024 (WN_ERR_UNSUPPORTED, nothing launched).  No workspace.
+ *   wn_demux_pick: one decision per read from those tables.  pattern_group [K] >= 0: the barcode or adapter a pattern stands for;
+ *   min_score [K]; min_margin >= 0.  Per end (front: patterns [0, n_front), rear: the others; a poisoned entry is no candidate):
+ *   the HIT is the greatest score, ties to the lower pattern index; the RUNNER-UP the greatest score among that end's patterns of
+ *   another group, INT_MIN if there is none; the hit PASSES if score >= min_score[hit] and score - runner_up >= min_margin (with no
+ *   runner-up the margin holds).
+ *     barcode   [B]        require_both: the group of the front hit if both ends pass and agree, else -1; otherwise the group of the
+ *                          passing end with the greater score, a tie to the front, -1 if neither passes
+ *     trim      [B][2]     trim_start = the end of the front hit if it passes, else 0; trim_end = max(trim_start, the start of the
+ *                          rear hit) if it passes, else lengths[b] as it stands
+ *     hits      [B][2][4]  per end (pattern, score, start, end); four times -1 where the end has no candidate
+ *     runner_up [B][2]
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch or n_patterns < 1, n_front outside [0, n_patterns], (scores)
+ * max_len, max_pattern_len or window < 1, a negative stride.  WN_ERR_UNSUPPORTED: a limit above, (pick) min_margin < 0.
+ * WN_ERR_NULL: any pointer but bad.  Nothing is read back or allocated: both calls can be captured into a HIP graph. */
+int wn_demux_scores(const int* labels, long long labels_stride, const int* lengths, const int* patterns, long long pattern_stride,
+                    const int* pattern_lengths, int batch, int max_len, int n_patterns, int n_front, int max_pattern_len,
+                    int window, int match, int mismatch, int gap_open, int gap_extend, int* score, int* start, int* end,
+                    int* bad /* may be NULL */, wn_stream_t stream);
+int wn_demux_pick(const int* score, const int* start, const int* end, const int* lengths, const int* pattern_group,
+                  const int* min_score, int batch, int n_patterns, int n_front, int min_margin, int require_both, int* barcode,
+                  int* trim, int* hits, int* runner_up, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *
