@@ -829,6 +829,57 @@ int wn_demux_pick(const int* score, const int* start, const int* end, const int*
                   const int* min_score, int batch, int n_patterns, int n_front, int min_margin, int require_both, int* barcode,
                   int* trim, int* hits, int* runner_up, wn_stream_t stream);
 
+/* ---- Read mapping in base space (csrc/wn_readmap.hip): which stretch of a reference, on which strand, a
+ * decoded read came from -- minimizer seeds looked up in an index of the reference and chained, the step minimap2 runs after
+ * basecalling.  Three launches; all pointers are DEVICE pointers; everything written is an integer and exact.  Labels: int32, 1..4
+ * are bases with complement 5 - v; anything else, 0 included, is a break.  tests/readmap_ref.py holds the same definition as plain
+ * loops.
+ *   K-MERS      the k-mer at p in [0, n - k]: forward code f = sum_i (label[p+i] - 1) 4^(k-1-i), reverse-complement code
+ *               r = sum_i (4 - label[p+i]) 4^i (uint32).  INVALID if a label is outside 1..4 or f == r (a palindrome); else canon =
+ *               min(f, r), strand = (r < f), hash = fmix32(canon) (murmur3's finaliser: x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13;
+ *               x *= 0xC2B2AE35; x ^= x >> 16), key = (hash, p).
+ *   MINIMIZERS  n_k = n - k + 1 >= 1; the windows are [s, s + w) for s in [0, n_k - w], or the single window [0, n_k) if n_k < w.
+ *               p is a minimizer iff it holds a valid k-mer whose key is the lexicographic minimum over the valid k-mers of at least
+ *               one window (equal hashes: the smallest position).  No result depends on how the row is cut into chunks.
+ *   wn_minimizers: labels [B] rows of labels_stride elements with lengths [B] -> code [B][max_len] (the canon code of a minimizer, 0
+ *   elsewhere) and flag [B][max_len] bytes (0 none, 1 the forward code is canonical, 2 the reverse complement's); every element of
+ *   both is written.  chunk: positions per workgroup, 0 = chosen by the library; a tuning argument, no output depends on it.
+ *   INDEX       `index` [n_index] int64, ascending: canon << 28 | pos << 1 | strand of every minimizer of the reference, i.e.
+ *               sorted by (canon, pos); the caller builds it from wn_minimizers of the reference (batch 1) and sorts.
+ *   ANCHORS     of a read of length n: its minimizers in ascending position q; for each the index entries of equal canon in
+ *               ascending pos, all dropped if there are more than max_occ.  An anchor is (s, r, q'): s = strand_read ^ strand_ref,
+ *               r = pos, q' = q if s == 0 else n - k - q.  The first anchors_per_read anchors of this enumeration are kept.
+ *   wn_read_seeds: code, flag [B][max_len] of the reads (as wn_minimizers wrote them, same k) -> keys [B][anchors_per_read] int64, one
+ *   word s << 43 | r << 16 | q' per kept anchor -- the first anchors_per_read of the enumeration, SORTED ascending (keys are distinct:
+ *   one result), which is the order wn_chain reads -- then INT64_MAX; n_minimizers, n_anchors (kept), truncated (1 if there were more) [B].
+ *   CHAINING    each strand on its own, its anchors in (r, q') order.  f(i) = max over candidates of (score, j), lexicographic: the
+ *               fresh start (16 k, i); and every j in [max(0, i - h), i) with dr = r_i - r_j, dq = q'_i - q'_j, 0 < dr <= max_dist,
+ *               0 < dq <= max_dist and dd = |dr - dq| <= bandwidth as (f(j) + 16 min(dr, dq, k) - gap(dd), j), gap(0) = 0, else
+ *               gap(dd) = gap_base dd + gap_log floor(log2 dd).  A fresh start beats an equal extension; of equal extensions the
+ *               nearest wins.  root(i) = i or root(pred); count(i) = 1 or count(pred) + 1.  16 k <= f <= 16 * 16 * 32768 = 2^23.
+ *   wn_chain: keys [B][anchors_per_read] sorted rows with n_anchors [B], lengths [B] (the reads') -> result [B][8] int32: score,
+ *   strand, ref_start, ref_end, query_start, query_end, n_anchors, runner_up.  The best anchor is the maximum of f over both strands,
+ *   ties to the forward strand, then to the smallest i; ref_start = r_root, ref_end = r_best + k; query span in read orientation:
+ *   forward [q'_root, q'_best + k), reverse [n - k - q'_best, n - q'_root); n_anchors = count; runner_up = the greatest f over all
+ *   anchors whose (strand, root) differs from the best one's, INT_MIN if none.  No anchors: INT_MIN, five times -1, 0, INT_MIN.
+ *   f, pred [B][anchors_per_read] int32 (both or neither): the whole table, pred an index into the sorted row, -1 for a fresh
+ *   start; past n_anchors INT_MIN and -1.
+ * A length outside [0, max_len] (wn_chain: also n_anchors outside [0, anchors_per_read]) makes the read one without anchors and is
+ * counted in *bad (DEVICE int, caller-zeroed, may be NULL); no such value is used as an index.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch or max_len < 1, a negative stride, chunk or n_index.
+ * WN_ERR_UNSUPPORTED: outside 1 <= k <= 16, 1 <= w <= 64, chunk <= 2048, 1 <= max_occ <= 64, 1 <= h <= 1024, 1 <= anchors_per_read
+ * <= 32768, 1 <= max_dist, bandwidth <= 2^26, 0 <= gap_base, gap_log <= 1024, batch <= 65535, max_len <= 2^26 (wn_minimizers) or
+ * 65535 (the reads of wn_read_seeds and wn_chain), n_index <= 2^26.  WN_ERR_NULL: any pointer but bad (f and pred: one without the
+ * other).  No workspace; nothing is read back or allocated: every call can be captured into a HIP graph. */
+int wn_minimizers(const int* labels, long long labels_stride, const int* lengths, int batch, int max_len, int k, int w, int chunk,
+                  unsigned* code, unsigned char* flag, int* bad /* may be NULL */, wn_stream_t stream);
+int wn_read_seeds(const unsigned* code, const unsigned char* flag, const int* lengths, const long long* index, int n_index, int batch,
+                  int max_len, int k, int max_occ, int anchors_per_read, long long* keys, int* n_minimizers, int* n_anchors,
+                  int* truncated, int* bad /* may be NULL */, wn_stream_t stream);
+int wn_chain(const long long* keys, const int* n_anchors, const int* lengths, int batch, int max_len, int anchors_per_read, int k,
+             int h, int max_dist, int bandwidth, int gap_base, int gap_log, int* result, int* f /* may be NULL */,
+             int* pred /* may be NULL */, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -8,7 +8,7 @@ modules.classifier.WaveNetClassifier, modules.conv_ops.*).
 All arithmetic of the hot path runs in hand-written HIP kernels (csrc/, gfx950) reached through the C ABI of
 libwavenet_amd.so (include/wavenet_amd.h).  No CPU fallback exists.
 """
-from . import basecalling, decoding, demux, events, functional, graphs, mapping, modules, normalise, series  # noqa: F401
+from . import basecalling, decoding, demux, events, functional, graphs, mapping, modules, normalise, readmap, series  # noqa: F401
 from .modules import (CausalConv1d, NonCausalConv1d, RawCTCNet, ResidualBlock, WaveNet,  # noqa: F401
                       WaveNetClassifier)
 from .modules.block import freeze_for_inference, set_precision  # noqa: F401
@@ -27,6 +27,8 @@ from .events import DetectedEvents, detect_events  # noqa: F401
 from .events import DEFAULT_MOVES, EventAlignment, event_align, fit_moves, move_costs  # noqa: F401
 from .demux import (BarcodeSet, Demultiplexed, DemuxScores, demultiplex, demux_scores, reverse_complement,  # noqa: F401
                     trim_reads)
+from .readmap import (Anchors, Minimizers, ReadIndex, ReadMapping, chain_anchors, map_reads, minimizers, paf_records,  # noqa: F401
+                      read_index, seed_anchors)
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 
