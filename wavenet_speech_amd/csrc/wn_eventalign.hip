@@ -4,25 +4,22 @@
 // sum over its samples of what wn_signal_align (section 7k) charges a sample -- formed from (n, sum q, sum q^2) alone.  What
 // nanopolish `eventalign` is.  Everything is an integer.
 //
-//   event_align_kernel   one workgroup per read, band / 8 threads at work (rounded up to whole waves), two phases in one launch.
+//   event_align_kernel   one workgroup per read on the banded-path core of wn_band_dev.h (slots, band entry, closing, trace
+//                        windows), two phases in one launch.  What is this kernel's own:
 //
 //     forward   cost_e(j) = min_m (cost_{e-1}(j - m) + move_cost[m]) + event_cost(e, model[kmer_j]), m in 0..3, over the states of
-//               the band [lo(e), lo(e) + W).  State j lives in SLOT j mod W and every thread owns 8 consecutive slots with their
-//               running costs (int64) and their three model integers in registers, as in section 7k.  lo rises by up to THREE
-//               per event (N <= 3 (E - 1) + 1): the centre is carried incrementally, rem += 2 N and up to three subtractions of
-//               2 E per step, no division; the up to three slots of the states that left are re-armed for the states that enter,
-//               their model rows fetched through the k-mer codes staged 256 at a time.  A predecessor j - m is taken only if it
-//               lay inside the band of event e - 1: with pj = j - lo(e - 1), iff 0 <= pj - m < W -- this one test covers the state
-//               that has just entered (its slot still holds the cost of the state that left), the states below the old band
-//               and the wrap of the slots.  THREE values cross threads per step: the last three slots of the left neighbour,
-//               cyclic over the band, through a double-buffered LDS row and ONE workgroup barrier per step.  The eight 2-bit
-//               backpointers of a thread are one 16-bit store to the workspace, bp[b][e][W / 8].  Events are staged 256 at a time
-//               into LDS as (n, sum, sumsq) and validated there, S^2 <= n Q in a 128-bit product.
-//     trace     backwards in chunks of 64 events.  The path moves at most three states per event, so a chunk that ends in state
-//               s reads the backpointers of the states (s - 192, s] only: 49 bytes per event, loaded into LDS by all threads; one
-//               lane walks the 64 steps in LDS, then the threads write event_state, the starts (in samples, from ev_starts) of
-//               the states that begin in the chunk -- a skipped state begins where its successor does -- and count the moves
-//               and the events on the band's edge.
+//               the band [lo(e), lo(e) + W).  lo rises by up to THREE per event (N <= 3 (E - 1) + 1), so up to three states enter
+//               the band in one step.  A predecessor j - m is taken only if it lay inside the band of event e - 1: with
+//               pj = j - lo(e - 1), iff 0 <= pj - m < W -- this one test covers the state that has just entered (its slot still
+//               holds the cost of the state that left), the states below the old band and the wrap of the slots.  THREE values
+//               cross threads per step: the last three slots of the left neighbour, cyclic over the band, through a
+//               double-buffered LDS row and ONE workgroup barrier per step.  The eight 2-bit backpointers of a thread are one
+//               16-bit store to the workspace, bp[b][e][W / 8].  Events are staged 256 at a time into LDS as (n, sum, sumsq) and
+//               validated there, S^2 <= n Q in a 128-bit product.
+//     trace     the path moves at most three states per event, so a chunk's window is 49 bytes per event; one lane walks the 64
+//               steps in LDS, then the threads write event_state, the starts (in samples, from ev_starts) of the states that
+//               begin in the chunk -- a skipped state begins where its successor does -- and count the moves and the events on
+//               the band's edge.
 //
 // Ties (tests/event_align_ref.py holds the same rule): the stay first, each larger move only if strictly cheaper, move cost
 // included.  No value of a length, a label or an event is used as an index before it is checked; a read found bad anywhere in the
@@ -30,32 +27,24 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
-#include "wn_signal_dev.h"
+#include "wn_band_dev.h"
 
 namespace wn {
 
-constexpr int kEaPer = 8;                     // consecutive band slots per thread
-constexpr int kEaMaxThreads = 256;            // band 2048
 constexpr int kEaTile = 256;                  // events staged into LDS at a time
-constexpr int kEaCodes = 256;                 // k-mer codes staged for the states that enter the band next
-constexpr int kEaTrace = 64;                  // events walked at a time by the trace
 constexpr int kEaMaxMove = 3;                 // states a path advances per event at the most
-constexpr int kEaWinBytes = kEaMaxMove * kEaTrace / 4 + 1;           // backpointer bytes (4 slots each) per event of a trace window
-constexpr int kEaMinBand = 64;
-constexpr int kEaMaxBand = 2048;
+constexpr int kEaWinBytes = kBandWinBytes<2, kEaMaxMove>;            // 2-bit backpointers, three states per event at the most: 49
 constexpr int kEaMaxSignal = 1 << 24;         // T_b
 constexpr int kEaMaxEvents = 1 << 20;         // events and states per read
 constexpr int kEaMaxEventLen = 65536;
 constexpr int kEaMoveLimit = 1 << 30;         // a move's cost stays below
 constexpr long long kEaQMax = kSigQLimit - 1;
-constexpr long long kEaInf = 1ll << 62;       // a path's cost stays below 2^24 (2^31 + 2^30) + 2^20 2^30 < 2^56
-constexpr long long kEaNoAlignment = 0x7fffffffffffffffll;
-constexpr long long kEaBadRead = -0x7fffffffffffffffll - 1;
+// a path's cost stays below 2^24 (2^31 + 2^30) + 2^20 2^30 < 2^56 < kPathInf
 
 // the dynamic LDS of a workgroup, in this order: int64 first
-constexpr size_t kEaEdgeBytes = 2 * kEaMaxMove * kEaMaxThreads * sizeof(long long);
-constexpr size_t kEaFixedLds = kEaEdgeBytes + 2 * kEaTile * sizeof(long long) + (kEaTile + kEaCodes + kEaTrace + 4) * sizeof(int);
-static_assert(kEaTrace * kEaWinBytes <= (int)kEaEdgeBytes, "the trace window reuses the edge rows");
+constexpr size_t kEaEdgeBytes = 2 * kEaMaxMove * kBandMaxThreads * sizeof(long long);
+constexpr size_t kEaFixedLds = kEaEdgeBytes + 2 * kEaTile * sizeof(long long) + (kEaTile + kBandCodes + kBandTrace + 4) * sizeof(int);
+static_assert(kBandTrace * kEaWinBytes <= (int)kEaEdgeBytes, "the trace window reuses the edge rows");
 
 struct EventAlignArgs {
     const int* n_events;
@@ -77,15 +66,6 @@ struct EventAlignArgs {
     int* bad;
 };
 
-// lo(e): the first state of the band at event e
-__device__ __forceinline__ int ea_band_lo(long long e, int N, int E, int W) {
-    const long long c = ((2 * e + 1) * (long long)N) / (2 * (long long)E);
-    const long long top = N > W ? N - W : 0;
-    long long lo = c - W / 2;
-    lo = lo < 0 ? 0 : lo;
-    return (int)(lo > top ? top : lo);
-}
-
 // min((D weight) >> S, n max_cost) + n offset with D = Q - 2 level S1 + n level^2, the exact sum of (q - level)^2 over the event's
 // samples: 0 <= D < 2^64 for a valid event, so arithmetic modulo 2^64 is exact; the 95-bit product is compared before it is narrowed
 __device__ __forceinline__ long long ea_event_cost(int n, long long s1, long long q2, int level, int weight, int offset, int S,
@@ -106,20 +86,20 @@ __device__ __forceinline__ bool ea_event_ok(long long n, long long s1, long long
     return (unsigned __int128)a * a <= (unsigned __int128)(unsigned long long)n * (unsigned long long)q2;
 }
 
-__global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventAlignArgs a) {
+__global__ __launch_bounds__(kBandMaxThreads) void event_align_kernel(const EventAlignArgs a) {
     extern __shared__ __attribute__((aligned(16))) char ea_smem[];
-    long long* s_edge = reinterpret_cast<long long*>(ea_smem);       // [2][3][kEaMaxThreads]: every thread's last three slots, by step parity
-    long long* s_sum = s_edge + 2 * kEaMaxMove * kEaMaxThreads;      // [kEaTile]
+    long long* s_edge = reinterpret_cast<long long*>(ea_smem);       // [2][3][kBandMaxThreads]: every thread's last three slots, by step parity
+    long long* s_sum = s_edge + 2 * kEaMaxMove * kBandMaxThreads;    // [kEaTile]
     long long* s_sq = s_sum + kEaTile;                               // [kEaTile]
     int* s_len = reinterpret_cast<int*>(s_sq + kEaTile);             // [kEaTile]
-    int* s_code = s_len + kEaTile;                                   // [kEaCodes]
-    int* s_path = s_code + kEaCodes;                                 // [kEaTrace + 1]: [0] the state before the chunk, [1 + f]
-    int* s_model = s_path + kEaTrace + 4;                            // [4^k][3]
-    unsigned char* s_win = reinterpret_cast<unsigned char*>(s_edge); // [kEaTrace][kEaWinBytes]: the trace runs after the last edge row is read
+    int* s_code = s_len + kEaTile;                                   // [kBandCodes]
+    int* s_path = s_code + kBandCodes;                               // [kBandTrace + 1]: [0] the state before the chunk, [1 + f]
+    int* s_model = s_path + kBandTrace + 4;                          // [4^k][3]
+    unsigned char* s_win = reinterpret_cast<unsigned char*>(s_edge); // [kBandTrace][kEaWinBytes]: the trace runs after the last edge row is read
     __shared__ long long s_fin;
     __shared__ int s_bad, s_hits, s_cnt[4];
     const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
-    const int W = a.band, nact = W / kEaPer, k = a.k, S = a.weight_shift;
+    const int W = a.band, nact = W / kBandPer, k = a.k, S = a.weight_shift;
     const int E = a.n_events[b], Lb = a.label_lengths[b];
     const long long n64 = (long long)Lb - (k - 1) - 2 * a.first;
     const bool bad_len = E < 0 || E > a.max_events || Lb < 0 || Lb > a.max_labels || n64 > a.max_states;
@@ -127,41 +107,23 @@ __global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventA
     int* st_out = a.starts + (long long)b * (a.max_states + 1);
     int* es_out = a.event_state ? a.event_state + (long long)b * a.max_events : nullptr;
     if (bad_len || none) {                                           // workgroup-uniform: nothing else of the read is looked at
-        for (int j = tid; j <= a.max_states; j += nthr) st_out[j] = -1;
-        if (es_out)
-            for (int e = tid; e < a.max_events; e += nthr) es_out[e] = -1;
+        band_refuse(bad_len, st_out, a.max_states + 1, es_out, a.max_events, a.score + b, a.band_hits + b, a.bad, tid, nthr);
         if (tid < 4) a.move_counts[4 * b + tid] = bad_len ? -1 : 0;
-        if (tid == 0) {
-            a.score[b] = bad_len ? kEaBadRead : kEaNoAlignment;
-            a.band_hits[b] = bad_len ? -1 : 0;
-            if (bad_len && a.bad) atomicAdd(a.bad, 1);
-        }
         return;
     }
     const int N = (int)n64;                                          // 1 <= N <= max_move (E - 1) + 1
 
     for (int i = tid; i < (3 << (2 * k)); i += nthr) s_model[i] = a.model[i];
-    if (tid == 0) { s_bad = 0; s_hits = 0; s_fin = kEaInf; }
+    if (tid == 0) { s_bad = 0; s_hits = 0; s_fin = kPathInf; }
     if (tid < 4) s_cnt[tid] = 0;
     __syncthreads();
 
-    // this thread's slots 8 tid .. 8 tid + 7 start as the states of the same numbers
     const int* lab = a.labels + (long long)b * a.labels_stride + a.first;        // state j is the window lab[j .. j + k)
-    int lvl[kEaPer], wgt[kEaPer], off[kEaPer];
-    long long d[kEaPer];
-    unsigned alive = 0;
+    int lvl[kBandPer], wgt[kBandPer], off[kBandPer];
+    long long d[kBandPer];
+    unsigned alive;
     bool ok = true;
-#pragma unroll
-    for (int i = 0; i < kEaPer; ++i) {
-        const int j = kEaPer * tid + i;
-        lvl[i] = 0; wgt[i] = 1; off[i] = 0;
-        d[i] = kEaInf;
-        if (tid < nact && j < N) {                                   // j + k <= N + k - 1 = Lb - 2 first: inside the labels
-            const int code = kmer_code(lab + j, k, &ok);
-            sa_model_row(s_model, code, &lvl[i], &wgt[i], &off[i], &ok);
-            alive |= 1u << i;
-        }
-    }
+    band_arm(s_model, lab, k, N, W, tid, lvl, wgt, off, d, alive, ok);           // N + k - 1 = Lb - 2 first: inside the labels
 
     const int* es = a.ev_starts + (long long)b * (a.max_events + 1);
     const long long* esum = a.ev_sum + (long long)b * a.max_events;
@@ -170,10 +132,7 @@ __global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventA
     if (es[0] < 0 || Tb > kEaMaxSignal) ok = false;
     const long long mc0 = a.move_cost[0], mc1 = a.move_cost[1], mc2 = a.move_cost[2], mc3 = a.move_cost[3];
     unsigned char* bprow = a.bp + (long long)b * a.max_events * (W / 4);
-    const long long two_n = 2ll * N, two_e = 2ll * E;
-    const int top = N > W ? N - W : 0;
-    long long rem = N;                                               // (2 e + 1) N = c 2 E + rem
-    int c = 0, lo = 0, lo_slot = 0;                                  // lo_slot = lo mod W
+    BandCursor cur(N, E, W);
     for (int e = 0; e < E; ++e) {
         const int ke = e & (kEaTile - 1);
         if (ke == 0) {                                               // the barrier of step e - 1: the old tile is no longer read
@@ -186,111 +145,65 @@ __global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventA
         }
         int delta = 0;                                               // lo(e) - lo(e - 1), 0..3; workgroup-uniform
         if (e > 0) {
-            rem += two_n;
-            while (rem >= two_e) { rem -= two_e; ++c; }              // N < 3 E: at most three subtractions
-            int ln = c - W / 2;
-            ln = ln < 0 ? 0 : ln;
-            ln = ln > top ? top : ln;
-            delta = ln - lo;
-            for (int i = 0; i < delta; ++i) {
-                const int r = lo + i;                                // state r + W <= N - 1 enters the band in the slot r mod W
-                const int rearm = lo_slot + i >= W ? lo_slot + i - W : lo_slot + i;
-                if ((r & (kEaCodes - 1)) == 0) {
-                    __syncthreads();                                 // the code of state r - 1 + W, fetched in this same step, has been read
-                    for (int u = tid; u < kEaCodes; u += nthr) {
-                        const long long j = (long long)W + r + u;
-                        int code = 0;
-                        if (j < N) code = kmer_code(lab + j, k, &ok);
-                        s_code[u] = code;
-                    }
-                    __syncthreads();
-                }
-                if ((rearm >> 3) == tid) {
-                    int l, w, o;
-                    sa_model_row(s_model, s_code[r & (kEaCodes - 1)], &l, &w, &o, &ok);
-#pragma unroll
-                    for (int u = 0; u < kEaPer; ++u)
-                        if (u == (rearm & 7)) { lvl[u] = l; wgt[u] = w; off[u] = o; }
-                }
-            }
-            lo = ln;
-            lo_slot = lo_slot + delta >= W ? lo_slot + delta - W : lo_slot + delta;
+            const int r = cur.lo, slot = cur.lo_slot;
+            delta = cur.advance();                                   // N < 3 E: at most three
+            for (int i = 0; i < delta; ++i)
+                band_enter(r + i, slot + i >= W ? slot + i - W : slot + i, s_model, s_code, lab, k, N, W, tid, nthr, lvl, wgt, off, ok);
         }
         const int n = s_len[ke];
         const long long s1 = s_sum[ke], q2 = s_sq[ke];
         const unsigned long long cap = (unsigned long long)n * (unsigned)a.max_cost;
-        long long p1 = kEaInf, p2 = kEaInf, p3 = kEaInf;             // cost_{e-1} of the one, two and three slots to the left
+        long long p1 = kPathInf, p2 = kPathInf, p3 = kPathInf;       // cost_{e-1} of the one, two and three slots to the left
         if (e > 0) {
-            const long long* row = s_edge + ((e - 1) & 1) * kEaMaxMove * kEaMaxThreads;
+            const long long* row = s_edge + ((e - 1) & 1) * kEaMaxMove * kBandMaxThreads;
             const int left = tid == 0 ? nact - 1 : tid - 1;
-            p3 = row[left]; p2 = row[kEaMaxThreads + left]; p1 = row[2 * kEaMaxThreads + left];
+            p3 = row[left]; p2 = row[kBandMaxThreads + left]; p1 = row[2 * kBandMaxThreads + left];
         }
-        int rel = kEaPer * tid - lo_slot;                            // this slot's state is lo + rel
+        int rel = kBandPer * tid - cur.lo_slot;                      // this slot's state is lo + rel
         if (rel < 0) rel += W;
         unsigned bits = 0;
 #pragma unroll
-        for (int i = 0; i < kEaPer; ++i) {
+        for (int i = 0; i < kBandPer; ++i) {
             const int pj = rel + delta;                              // the state's place in the band of event e - 1: inside iff 0 <= pj - m < W
             const long long cur = d[i];
-            long long best = kEaInf;
+            long long best = kPathInf;
             unsigned mv = 0;
-            if (mc0 >= 0 && (unsigned)pj < (unsigned)W && cur < kEaInf) best = cur + mc0;
-            if ((unsigned)(pj - 1) < (unsigned)W && p1 < kEaInf && p1 + mc1 < best) { best = p1 + mc1; mv = 1; }
-            if (mc2 >= 0 && (unsigned)(pj - 2) < (unsigned)W && p2 < kEaInf && p2 + mc2 < best) { best = p2 + mc2; mv = 2; }
-            if (mc3 >= 0 && (unsigned)(pj - 3) < (unsigned)W && p3 < kEaInf && p3 + mc3 < best) { best = p3 + mc3; mv = 3; }
-            if (e == 0) { best = kEaPer * tid + i == 0 ? 0 : kEaInf; mv = 0; }      // paths start in state 0
-            long long nd = kEaInf;
-            if (((alive >> i) & 1u) && best < kEaInf) nd = best + ea_event_cost(n, s1, q2, lvl[i], wgt[i], off[i], S, cap);
+            if (mc0 >= 0 && (unsigned)pj < (unsigned)W && cur < kPathInf) best = cur + mc0;
+            if ((unsigned)(pj - 1) < (unsigned)W && p1 < kPathInf && p1 + mc1 < best) { best = p1 + mc1; mv = 1; }
+            if (mc2 >= 0 && (unsigned)(pj - 2) < (unsigned)W && p2 < kPathInf && p2 + mc2 < best) { best = p2 + mc2; mv = 2; }
+            if (mc3 >= 0 && (unsigned)(pj - 3) < (unsigned)W && p3 < kPathInf && p3 + mc3 < best) { best = p3 + mc3; mv = 3; }
+            if (e == 0) { best = kBandPer * tid + i == 0 ? 0 : kPathInf; mv = 0; }      // paths start in state 0
+            long long nd = kPathInf;
+            if (((alive >> i) & 1u) && best < kPathInf) nd = best + ea_event_cost(n, s1, q2, lvl[i], wgt[i], off[i], S, cap);
             d[i] = nd;
             bits |= mv << (2 * i);
             p3 = p2; p2 = p1; p1 = cur;
             rel = rel + 1 == W ? 0 : rel + 1;
         }
         {
-            long long* row = s_edge + (e & 1) * kEaMaxMove * kEaMaxThreads;
-            row[tid] = d[kEaPer - 3]; row[kEaMaxThreads + tid] = d[kEaPer - 2]; row[2 * kEaMaxThreads + tid] = d[kEaPer - 1];
+            long long* row = s_edge + (e & 1) * kEaMaxMove * kBandMaxThreads;
+            row[tid] = d[kBandPer - 3]; row[kBandMaxThreads + tid] = d[kBandPer - 2]; row[2 * kBandMaxThreads + tid] = d[kBandPer - 1];
         }
         if (tid < nact) reinterpret_cast<unsigned short*>(bprow)[(long long)e * nact + tid] = (unsigned short)bits;
         __syncthreads();                                             // one barrier per step: the row of step e - 1 is free again
     }
-    {
-        const int fs = (N - 1) % W;                                  // the slot of the last state
-        if ((fs >> 3) == tid) {
-#pragma unroll
-            for (int i = 0; i < kEaPer; ++i)
-                if (i == (fs & 7)) s_fin = d[i];
-        }
-    }
-    if (!ok) atomicOr(&s_bad, 1);
-    __syncthreads();                                                 // s_fin, s_bad and this workgroup's backpointer rows are visible
+    band_close(d, ok, N, W, tid, &s_fin, &s_bad);
 
     const long long fin = s_fin;
     const bool poisoned = s_bad != 0;
-    if (poisoned || fin >= kEaInf) {
-        for (int j = tid; j <= a.max_states; j += nthr) st_out[j] = -1;
-        if (es_out)
-            for (int e = tid; e < a.max_events; e += nthr) es_out[e] = -1;
+    if (poisoned || fin >= kPathInf) {
+        band_refuse(poisoned, st_out, a.max_states + 1, es_out, a.max_events, a.score + b, a.band_hits + b, a.bad, tid, nthr);
         if (tid < 4) a.move_counts[4 * b + tid] = poisoned ? -1 : 0;
-        if (tid == 0) {
-            a.score[b] = poisoned ? kEaBadRead : kEaNoAlignment;
-            a.band_hits[b] = poisoned ? -1 : 0;
-            if (poisoned && a.bad) atomicAdd(a.bad, 1);
-        }
         return;
     }
     for (int j = N + tid; j <= a.max_states; j += nthr) st_out[j] = Tb;
     if (es_out)
         for (int e = E + tid; e < a.max_events; e += nthr) es_out[e] = -1;
 
-    const int wrow = W / 4;                                          // backpointer bytes per event: the byte of state j is (j mod W) / 4
     int s_end = N - 1, hits = 0;
-    for (int e0 = (E - 1) / kEaTrace * kEaTrace; e0 >= 0; e0 -= kEaTrace) {
-        const int nf = min(kEaTrace, E - e0);
-        const int g0 = max(s_end - (kEaMaxMove * kEaTrace - 1), 0) >> 2;         // first byte of the window (s_end - 192, s_end]
-        for (int i = tid; i < nf * kEaWinBytes; i += nthr) {
-            const int f = i / kEaWinBytes, g = g0 + (i - f * kEaWinBytes);
-            s_win[i] = bprow[(long long)(e0 + f) * wrow + g % wrow];
-        }
+    for (int e0 = (E - 1) / kBandTrace * kBandTrace; e0 >= 0; e0 -= kBandTrace) {
+        const int nf = min(kBandTrace, E - e0);
+        const int g0 = band_load_window<2, kEaMaxMove>(s_win, bprow, e0, nf, s_end, W, tid, nthr);       // (s_end - 192, s_end]
         __syncthreads();                                             // window loaded; s_path of the previous chunk was read
         if (tid == 0) {
             int s = s_end;
@@ -309,8 +222,7 @@ __global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventA
             if (e > 0) atomicAdd(&s_cnt[pi - before], 1);
             const int t = es[e];
             for (int j = before + 1; j <= pi; ++j) st_out[j] = t;    // a skipped state is empty: it begins where its successor does
-            const int le = ea_band_lo(e, N, E, W);
-            if ((pi == le && le > 0) || (pi == le + W - 1 && le + W < N)) ++hits;
+            if (band_on_edge(pi, band_lo(e, N, E, W), N, W)) ++hits;
         }
         s_end = s_path[0];
     }
@@ -323,11 +235,6 @@ __global__ __launch_bounds__(kEaMaxThreads) void event_align_kernel(const EventA
     }
 }
 
-static bool ea_sizes_ok(int batch, int max_events, int band) {
-    return batch >= 1 && batch <= 65535 && max_events >= 1 && max_events <= kEaMaxEvents && band >= kEaMinBand && band <= kEaMaxBand &&
-           band % 64 == 0;
-}
-
 static bool ea_move_ok(int cost) { return cost == -1 || (cost >= 0 && cost < kEaMoveLimit); }
 
 }  // namespace wn
@@ -335,8 +242,7 @@ using namespace wn;
 
 // workspace: backpointers, 2 bits per (event, band slot), [B][max_events][band / 4] bytes
 size_t wn_event_align_workspace_bytes(int batch, int max_events, int band) {
-    if (!ea_sizes_ok(batch, max_events, band)) return 0;
-    return ((size_t)batch * (size_t)max_events * (size_t)(band / 4) + 15) / 16 * 16;
+    return band_sizes_ok(batch, max_events, kEaMaxEvents, band) ? band_workspace_bytes(batch, max_events, band, 2) : 0;
 }
 
 int wn_event_align(const int* n_events, const int* ev_starts, const long long* ev_sum, const long long* ev_sumsq, const int* labels,
@@ -345,9 +251,7 @@ int wn_event_align(const int* n_events, const int* ev_starts, const long long* e
                    int move_cost1, int move_cost2, int move_cost3, int* starts, long long* score, int* event_state, int* move_counts,
                    int* band_hits, void* workspace, size_t workspace_bytes, int* bad, wn_stream_t stream) {
     if (batch < 1 || max_events < 1 || max_labels < 1 || max_states < 1 || labels_stride < 0) return WN_ERR_BAD_SHAPE;
-    if (k < 1 || k > kSigMaxK || first < 0 || first > kSigMaxFirst || frac_bits < 0 || frac_bits > kSigMaxFrac) return WN_ERR_UNSUPPORTED;
-    if (weight_shift < 16 || weight_shift > 63 || max_cost < 1) return WN_ERR_UNSUPPORTED;
-    if (band < kEaMinBand || band > kEaMaxBand || band % 64 != 0) return WN_ERR_UNSUPPORTED;
+    if (const int e = band_check_params(k, first, frac_bits, weight_shift, max_cost, band)) return e;
     if (move_cost1 < 0 || !ea_move_ok(move_cost0) || !ea_move_ok(move_cost1) || !ea_move_ok(move_cost2) || !ea_move_ok(move_cost3))
         return WN_ERR_UNSUPPORTED;
     if (batch > 65535 || max_events > kEaMaxEvents || max_states > kEaMaxEvents) return WN_ERR_UNSUPPORTED;
@@ -367,11 +271,10 @@ int wn_event_align(const int* n_events, const int* ev_starts, const long long* e
     a.bp = (unsigned char*)workspace; a.bad = bad;
 
     hipStream_t st = (hipStream_t)stream;
-    const int threads = (band / kEaPer + 63) / 64 * 64;              // one wave up to band 512, four at 2048
     const size_t lds = kEaFixedLds + (size_t)(3 << (2 * k)) * sizeof(int);       // 18.3 KiB and the table: 66.3 KiB at k = 6
     WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
            "event_align attribute");
-    hipLaunchKernelGGL(event_align_kernel, dim3((unsigned)batch), dim3(threads), lds, st, a);
+    hipLaunchKernelGGL(event_align_kernel, dim3((unsigned)batch), dim3(band_threads(band)), lds, st, a);
     WN_HIP(hipGetLastError(), "event_align");
     return WN_OK;
 }

@@ -179,8 +179,7 @@ __global__ __launch_bounds__(kEdThreads) void event_peaks_kernel(const DetectArg
     const int hq0 = hs0 + a.w[0], hq1 = w1 > 0 ? hs1 + w1 : 0;
     const int hq = hq0 > hq1 ? hq0 : hq1;                            // <= 96
     const T* sig = (const T*)a.signal + (long long)b * a.signal_stride;
-    const bool scaled = a.scale_shift != nullptr;
-    const double scale = scaled ? (double)a.scale_shift[2 * b] : 1.0, shift = scaled ? (double)a.scale_shift[2 * b + 1] : 0.0;
+    const auto [scaled, scale, shift] = read_scale(a.scale_shift, b);
     const int cend = (int)(c0 + a.chunk);
     for (int p0 = (int)c0; p0 < cend && p0 < Tn; p0 += kEdTile) {
         const int pt = cend - p0 < kEdTile ? cend - p0 : kEdTile;    // a multiple of 256
@@ -353,8 +352,7 @@ __global__ __launch_bounds__(kEdThreads) void event_sums_kernel(const DetectArgs
         len = (e + 1 < n ? starts[e + 1] : Tn) - start;
     }
     const T* sig = (const T*)a.signal + (long long)b * a.signal_stride;
-    const bool scaled = a.scale_shift != nullptr;
-    const double scale = scaled ? (double)a.scale_shift[2 * b] : 1.0, shift = scaled ? (double)a.scale_shift[2 * b + 1] : 0.0;
+    const auto [scaled, scale, shift] = read_scale(a.scale_shift, b);
     long long sum = 0, sumsq = 0;
     if (used && len <= kEdShort) {
         for (int t = 0; t < len; ++t) {

@@ -107,8 +107,7 @@ __global__ __launch_bounds__(kEvThreads) void kmer_events_kernel(const EventArgs
 
     // ---- the sums of the events that are used so far
     const T* sig = (const T*)a.signal + (long long)b * a.signal_stride;
-    const bool scaled = a.scale_shift != nullptr;
-    const double scale = scaled ? (double)a.scale_shift[2 * b] : 1.0, shift = scaled ? (double)a.scale_shift[2 * b + 1] : 0.0;
+    const auto [scaled, scale, shift] = read_scale(a.scale_shift, b);
     const bool need = code >= 0;
     long long sum = 0, sumsq = 0;
     if (need && len <= kEvShort) {

@@ -39,9 +39,7 @@ constexpr int kSmMaxSignal = 4096;
 constexpr int kSmMaxRef = 1 << 26;
 constexpr int kSmMaxStrip = 1 << 20;
 constexpr int kSmFullChip = 512;              // two workgroups for each of the MI355X's 256 CUs
-constexpr long long kSmInf = 1ll << 62;       // a finite cost stays below 2^12 (2^31 + 2^30) in magnitude
-constexpr long long kSmNoMapping = 0x7fffffffffffffffll;
-constexpr long long kSmBadRead = -0x7fffffffffffffffll - 1;
+// a finite cost stays below 2^12 (2^31 + 2^30) in magnitude, far below kPathInf (wn_signal_dev.h)
 
 static_assert(kSmBlockLanes * kSmPer == WN_MAP_GRANULE && kSmTile % WN_MAP_GRANULE == 0 && 64 % kSmBlockLanes == 0, "blocks within waves");
 
@@ -116,15 +114,14 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
 
     long long fill = 0;                                              // workgroup-uniform
     if (Tn < 0 || Tn > a.max_signal) {
-        fill = kSmBadRead;                                           // nothing else of the read is looked at
+        fill = kPathBadRead;                                         // nothing else of the read is looked at
     } else if (Tn == 0) {
-        fill = kSmNoMapping;
+        fill = kPathNone;
     } else {
         if (tid == 0) s_bad = 0;
         __syncthreads();
         const T* sig = (const T*)a.signal + (long long)b * a.signal_stride;
-        const bool scaled = a.scale_shift != nullptr;
-        const double scale = scaled ? (double)a.scale_shift[2 * b] : 1.0, shift = scaled ? (double)a.scale_shift[2 * b + 1] : 0.0;
+        const auto [scaled, scale, shift] = read_scale(a.scale_shift, b);
         bool ok = true;
         for (int t = tid; t < Tn; t += kSmThreads) {
             int q = 0;
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
         }
         if (!ok) atomicOr(&s_bad, 1);
         __syncthreads();
-        if (s_bad) fill = kSmBadRead;                                // every workgroup of the read finds the same
+        if (s_bad) fill = kPathBadRead;                              // every workgroup of the read finds the same
     }
     if (fill) {
         for (int g = own0 / WN_MAP_GRANULE + tid; g < (own1 + WN_MAP_GRANULE - 1) / WN_MAP_GRANULE; g += kSmThreads) {
@@ -164,18 +161,18 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
             wgt[i] = a.model[3 * r + 1];
             off[i] = a.model[3 * r + 2];
             if (open) alive |= 1u << i;
-            d[i] = open ? 0 : kSmInf;                                // before sample 0: the start is free, a wall never opens
+            d[i] = open ? 0 : kPathInf;                              // before sample 0: the start is free, a wall never opens
             o[i] = col;
         }
         // thread 0's view of the previous tile's rightmost column: la = its cell at t - 1 (used now), lb = at t (used next step)
-        long long la = kSmInf, lb = kSmInf;
+        long long la = kPathInf, lb = kPathInf;
         int oa = -1, ob = -1;
         if (tid == 0 && !leftmost) { lb = s_bc[0]; ob = s_bo[0]; }
         __syncthreads();                                             // entry 0 is read before the last thread overwrites it
 
         for (int t = 0; t < Tn; ++t) {
             const int q = s_q[t];
-            long long lc = kSmInf;
+            long long lc = kPathInf;
             int oc = -1;
             if (tid == 0 && !leftmost && t + 1 < Tn) { lc = s_bc[t + 1]; oc = s_bo[t + 1]; }
             long long prev = __shfl_up(d[kSmPer - 1], 1);            // cost_{t-1} and origin of the state to the left
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
                     prev = s_ec[(t - 1) & 1][wave - 1];
                     prevo = s_eo[(t - 1) & 1][wave - 1];
                 } else {
-                    prev = kSmInf;                                   // at t = 0 nothing steps
+                    prev = kPathInf;                                 // at t = 0 nothing steps
                 }
             }
 #pragma unroll
@@ -200,8 +197,8 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
                 prev = d[i];
                 prevo = o[i];
                 if (step < m) { m = step; mo = stepo; }              // the stay first; the step only if strictly smaller
-                long long n = kSmInf;
-                if (((alive >> i) & 1u) && m < kSmInf) n = m + sa_sample_cost(q, lvl[i], wgt[i], off[i], S, max_cost);
+                long long n = kPathInf;
+                if (((alive >> i) & 1u) && m < kPathInf) n = m + sa_sample_cost(q, lvl[i], wgt[i], off[i], S, max_cost);
                 d[i] = n;
                 o[i] = mo;
             }
@@ -216,13 +213,13 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
         }
 
         // the last row of this tile: end_cost, and the 64-state blocks of the owned columns
-        long long best = kSmNoMapping;
+        long long best = kPathNone;
         int best_end = 0x7fffffff, best_origin = -1;
 #pragma unroll
         for (int i = 0; i < kSmPer; ++i) {
             const int col = c0 + kSmPer * tid + i;
-            const bool finite = d[i] < kSmInf;                       // only a state below M is ever finite
-            if (ec_out && col >= own0 && col < own1) ec_out[col] = finite ? d[i] : kSmNoMapping;
+            const bool finite = d[i] < kPathInf;                     // only a state below M is ever finite
+            if (ec_out && col >= own0 && col < own1) ec_out[col] = finite ? d[i] : kPathNone;
             if (finite && d[i] < best) { best = d[i]; best_end = col; best_origin = o[i]; }
         }
 #pragma unroll
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_kernel(const SigMapArgs
         const int block0 = c0 + kSmPer * tid;                        // of this thread's states
         if ((lane & (kSmBlockLanes - 1)) == 0 && block0 >= own0 && block0 < own1) {
             const int g = block0 / WN_MAP_GRANULE;
-            const bool any = best < kSmNoMapping;
+            const bool any = best < kPathNone;
             bc_out[g] = best;
             be_out[g] = any ? best_end : -1;
             bo_out[g] = any ? best_origin : -1;
@@ -249,16 +246,16 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_pick_kernel(const SigMa
     const int Tn = a.signal_lengths[b];
     const long long* bc = a.block_cost + (long long)b * G;
     const bool bad_len = Tn < 0 || Tn > a.max_signal;
-    if (bad_len || Tn == 0 || bc[0] == kSmBadRead) {                 // workgroup-uniform; the strips have filled the tables
+    if (bad_len || Tn == 0 || bc[0] == kPathBadRead) {               // workgroup-uniform; the strips have filled the tables
         if (tid == 0) {
             const bool is_bad = bad_len || Tn != 0;
-            a.score[b] = a.runner_up[b] = is_bad ? kSmBadRead : kSmNoMapping;
+            a.score[b] = a.runner_up[b] = is_bad ? kPathBadRead : kPathNone;
             a.end[b] = a.start[b] = -1;
             if (is_bad && a.bad) atomicAdd(a.bad, 1);
         }
         return;
     }
-    long long best = kSmNoMapping;
+    long long best = kPathNone;
     int best_g = 0x7fffffff;
     for (int g = tid; g < G; g += kSmThreads) {
         const long long c = bc[g];
@@ -278,9 +275,9 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_pick_kernel(const SigMa
     best = s_c[0];
     best_g = s_g[0];
     __syncthreads();                                                 // s_c is reused below
-    if (best == kSmNoMapping) {                                      // no finite cell in the last row
+    if (best == kPathNone) {                                         // no finite cell in the last row
         if (tid == 0) {
-            a.score[b] = a.runner_up[b] = kSmNoMapping;
+            a.score[b] = a.runner_up[b] = kPathNone;
             a.end[b] = a.start[b] = -1;
         }
         return;
@@ -288,7 +285,7 @@ __global__ __launch_bounds__(kSmThreads) void signal_map_pick_kernel(const SigMa
     const int end = a.block_end[(long long)b * G + best_g];
     // the best block whose states all lie T_b or more from `end`: two such paths share no state
     const long long left = (long long)end - Tn, right = (long long)end + Tn;
-    long long other = kSmNoMapping;
+    long long other = kPathNone;
     for (int g = tid; g < G; g += kSmThreads) {
         const long long g0 = (long long)g * WN_MAP_GRANULE;
         if (g0 + WN_MAP_GRANULE - 1 <= left || g0 >= right) {

@@ -1,6 +1,6 @@
 // What the event tables (wn_events.hip), the signal alignment (wn_sigalign.hip, section 7k) and the signal
 // mapping (wn_sigmap.hip, section 7l) share: the quantisation of a sample, the index of a k-mer window, the cost of a sample in a
-// state with the check of a model row, and their limits.  ONE definition each: the alignment makes the segmentation that the event
+// state with the check of a model row, a read's scale pair, the sentinels of a path's cost, and their limits.  ONE definition each: the alignment makes the segmentation that the event
 // tables consume, so both must quantise a sample to the same bits, and a mapping must cost what the alignment of its span costs.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,21 @@ constexpr int kSigMaxFirst = 8;               // |first|: the offset of a window
 constexpr int kSigMaxFrac = 20;               // frac_bits
 constexpr int kSigQLimit = 1 << 23;           // |q| (and a model's |level|) stay below
 constexpr int kSaOffsetLimit = 1 << 30;       // a model's |offset| stays below
+
+// the sentinels of a path's cost; every user proves beside its own limits that its finite costs stay below kPathInf
+constexpr long long kPathInf = 1ll << 62;     // no path reaches this state
+constexpr long long kPathNone = 0x7fffffffffffffffll;                // a read's score: no alignment / no mapping (LLONG_MAX)
+constexpr long long kPathBadRead = -0x7fffffffffffffffll - 1;        // a read's score: a bad read (LLONG_MIN)
+
+// read b's (scale, shift) of scale_shift [B][2]; nullptr: samples are taken as they are
+struct ReadScale {
+    bool scaled;
+    double scale, shift;
+};
+__device__ __forceinline__ ReadScale read_scale(const float* scale_shift, int b) {
+    const bool scaled = scale_shift != nullptr;
+    return {scaled, scaled ? (double)scale_shift[2 * b] : 1.0, scaled ? (double)scale_shift[2 * b + 1] : 0.0};
+}
 
 // q = llrint(v 2^F), v = x scale + shift in double with one rounding; false for a non-finite v or |q| >= 2^23
 template <typename T>

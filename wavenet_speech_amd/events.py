@@ -405,10 +405,43 @@ def signal_model(means, stdvs, frac_bits=12, cost_bits=8):
     return SignalModel(torch.tensor(rows, dtype=torch.int64), S, F, cb)
 
 
+class _Nats:
+    @property
+    def nats(self):
+        """[B] float64: score / 2^cost_bits (+-inf-like sentinels stay huge: mask with score first)"""
+        return self.score.double() / float(1 << self.cost_bits)
+
+
+class _BandCall:
+    """What a call of signal_align and of event_align share, raised in the caller's name: the checks of model, first, band and
+    max_cost (and of the events' frac_bits against the model's, where there are events), the number of states, and the outputs
+    that every banded alignment has."""
+
+    def __init__(self, what, model, first, band, max_cost, events_frac_bits=None):
+        if not isinstance(model, SignalModel):
+            raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
+        if events_frac_bits is not None and events_frac_bits != model.frac_bits:
+            raise ValueError("wavenet_speech_amd.%s: the events have frac_bits %d and the model %d" % (what, events_frac_bits, model.frac_bits))
+        first, band = int(first), int(band)
+        max_cost = 2 ** 31 - 1 if max_cost is None else int(max_cost)
+        if not 0 <= first <= MAX_FIRST or not MIN_BAND <= band <= MAX_BAND or band % 64 or not 1 <= max_cost <= 2 ** 31 - 1:
+            raise ValueError("wavenet_speech_amd.%s: first in [0, %d], band a multiple of 64 in [%d, %d], max_cost in [1, 2^31 - 1]"
+                             % (what, MAX_FIRST, MIN_BAND, MAX_BAND))
+        self.k, self.first, self.band, self.max_cost = model.k, first, band, max_cost
+
+    def states(self, labels):            # of a read that uses all of labels' columns, at least 1: the width of starts - 1
+        return max(int(labels.shape[1]) - (self.k - 1) - 2 * self.first, 1)
+
+    @staticmethod
+    def outputs(B, N, dev):              # starts, score, band_hits, bad
+        i32 = dict(dtype=torch.int32, device=dev)
+        return torch.empty(B, N + 1, **i32), torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, **i32), torch.zeros(1, **i32)
+
+
 _AlignFields = namedtuple("SignalAlignment", "starts score band_hits states")
 
 
-class SignalAlignment(_AlignFields):
+class SignalAlignment(_Nats, _AlignFields):
     """starts [B, N + 1] int32: starts[b, j] is the first sample of state (k-mer) j, every entry past the read's last state is
     signal_lengths[b] -- RaggedReads.starts' convention, so it goes into kmer_events(starts=...) as it is; score [B] int64: the cost
     of the path, LLONG_MAX where there is no alignment (no state, or fewer samples than states) and LLONG_MIN for a bad read;
@@ -421,11 +454,6 @@ class SignalAlignment(_AlignFields):
         self = super().__new__(cls, *fields)
         self.k, self.first, self.frac_bits, self.cost_bits, self.band = int(k), int(first), int(frac_bits), int(cost_bits), int(band)
         return self
-
-    @property
-    def nats(self):
-        """[B] float64: score / 2^cost_bits (+-inf-like sentinels stay huge: mask with score first)"""
-        return self.score.double() / float(1 << self.cost_bits)
 
 
 def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, band=512, scale_shift=None, max_cost=None,
@@ -452,26 +480,15 @@ def signal_align(signal, signal_lengths, labels, label_lengths, model, first=0, 
     what = "signal_align"
     signal, signal_lengths, labels, label_lengths, scale_shift, B, L, dev = _read_inputs(what, signal, signal_lengths, labels,
                                                                                          label_lengths, scale_shift)
-    if not isinstance(model, SignalModel):
-        raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
-    first, band = int(first), int(band)
-    max_cost = 2 ** 31 - 1 if max_cost is None else int(max_cost)
-    if not 0 <= first <= MAX_FIRST or not MIN_BAND <= band <= MAX_BAND or band % 64 or not 1 <= max_cost <= 2 ** 31 - 1:
-        raise ValueError("wavenet_speech_amd.%s: first in [0, %d], band a multiple of 64 in [%d, %d], max_cost in [1, 2^31 - 1]"
-                         % (what, MAX_FIRST, MIN_BAND, MAX_BAND))
-    k = model.k
-    N = max(int(labels.shape[1]) - (k - 1) - 2 * first, 1)
+    call = _BandCall(what, model, first, band, max_cost)
+    k, first, band, max_cost, N = call.k, call.first, call.band, call.max_cost, call.states(labels)
     if L > MAX_ALIGN_SIGNAL or N > MAX_ALIGN_EVENTS or B > 65535:
         raise ValueError("wavenet_speech_amd.%s: at most 2^24 samples and 2^20 k-mers per read and 65535 reads" % what)
     with torch.cuda.device(dev):
         lib = _lib.load()
         table = model.on(dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        starts = torch.empty(B, N + 1, **i32)
-        score = torch.empty(B, dtype=torch.int64, device=dev)
-        band_hits = torch.empty(B, **i32)
-        states = torch.empty(B, L, **i32) if want_states else None
-        bad = torch.zeros(1, **i32)
+        starts, score, band_hits, bad = call.outputs(B, N, dev)
+        states = torch.empty(B, L, dtype=torch.int32, device=dev) if want_states else None
         ws = _alloc_bytes(lib.wn_signal_align_workspace_bytes(B, L, band), "wn_signal_align_workspace_bytes", dev, status=-2)
         _lib.check(lib.wn_signal_align(_p(signal), int(signal.dtype == torch.int16), signal.stride(0), _p(signal_lengths), _p(scale_shift),
                                        _p(labels), labels.stride(0), _p(label_lengths), _p(table), B, L, int(labels.shape[1]), N, k, first,
@@ -621,7 +638,7 @@ DEFAULT_MOVES = (0.14, 0.62, 0.20, 0.04)
 _EventAlignFields = namedtuple("EventAlignment", "starts score band_hits moves states")
 
 
-class EventAlignment(_EventAlignFields):
+class EventAlignment(_Nats, _EventAlignFields):
     """starts [B, N + 1] int32: starts[b, j] is the first SAMPLE of state (k-mer) j -- RaggedReads.starts' convention, so it goes
     into kmer_events(starts=...) as it is; a skipped state is empty (starts[b, j] == starts[b, j + 1]; kmer_events gives it the code
     -2 and does not call the read bad) and every entry past the read's last state is the read's last sample + 1; score [B] int64: the
@@ -637,11 +654,6 @@ class EventAlignment(_EventAlignFields):
         self.k, self.first, self.frac_bits, self.cost_bits, self.band = int(k), int(first), int(frac_bits), int(cost_bits), int(band)
         self.move_costs = tuple(int(c) for c in move_costs)
         return self
-
-    @property
-    def nats(self):
-        """[B] float64: score / 2^cost_bits (+-inf-like sentinels stay huge: mask with score first)"""
-        return self.score.double() / float(1 << self.cost_bits)
 
 
 def move_costs(probs, cost_bits=8):
@@ -717,15 +729,8 @@ def event_align(events, labels, label_lengths, model, first=0, band=512, moves=D
             raise ValueError("wavenet_speech_amd.%s: events must be a DetectedEvents, or (n_events, starts, sum, sumsq) with frac_bits=" % what)
         count, ev_starts, ev_sum, ev_sumsq = events
         F = int(frac_bits)
-    if not isinstance(model, SignalModel):
-        raise ValueError("wavenet_speech_amd.%s: model must be a SignalModel (signal_model(means, stdvs)), got %s" % (what, type(model).__name__))
-    if F != model.frac_bits:
-        raise ValueError("wavenet_speech_amd.%s: the events have frac_bits %d and the model %d" % (what, F, model.frac_bits))
-    first, band = int(first), int(band)
-    max_cost = 2 ** 31 - 1 if max_cost is None else int(max_cost)
-    if not 0 <= first <= MAX_FIRST or not MIN_BAND <= band <= MAX_BAND or band % 64 or not 1 <= max_cost <= 2 ** 31 - 1:
-        raise ValueError("wavenet_speech_amd.%s: first in [0, %d], band a multiple of 64 in [%d, %d], max_cost in [1, 2^31 - 1]"
-                         % (what, MAX_FIRST, MIN_BAND, MAX_BAND))
+    call = _BandCall(what, model, first, band, max_cost, events_frac_bits=F)
+    k, first, band, max_cost = call.k, call.first, call.band, call.max_cost
     try:
         moves = tuple(moves)
     except TypeError:
@@ -752,19 +757,15 @@ def event_align(events, labels, label_lengths, model, first=0, band=512, moves=D
     with torch.cuda.device(dev):
         count = _args.lengths(count, B, dev, what, "n_events", flatten=True)
         label_lengths = _args.lengths(label_lengths, B, dev, what, "label_lengths", flatten=True)
-    k = model.k
-    N = max(int(labels.shape[1]) - (k - 1) - 2 * first, 1)
+    N = call.states(labels)
     if M > MAX_ALIGN_EVENTS or N > MAX_ALIGN_EVENTS or B > 65535:
         raise ValueError("wavenet_speech_amd.%s: at most 2^20 events and 2^20 k-mers per read and 65535 reads" % what)
     with torch.cuda.device(dev):
         lib = _lib.load()
         table = model.on(dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        starts = torch.empty(B, N + 1, **i32)
-        score = torch.empty(B, dtype=torch.int64, device=dev)
-        band_hits, counts = torch.empty(B, **i32), torch.empty(B, 4, **i32)
-        states = torch.empty(B, M, **i32) if want_states else None
-        bad = torch.zeros(1, **i32)
+        starts, score, band_hits, bad = call.outputs(B, N, dev)
+        counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        states = torch.empty(B, M, dtype=torch.int32, device=dev) if want_states else None
         ws = _alloc_bytes(lib.wn_event_align_workspace_bytes(B, M, band), "wn_event_align_workspace_bytes", dev, status=-2)
         _lib.check(lib.wn_event_align(_p(count), _p(ev_starts), _p(sums[0]), _p(sums[1]), _p(labels), labels.stride(0), _p(label_lengths),
                                       _p(table), B, M, int(labels.shape[1]), N, k, first, F, model.weight_shift, max_cost, band, costs[0],
