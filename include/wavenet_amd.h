@@ -880,6 +880,69 @@ int wn_chain(const long long* keys, const int* n_anchors, const int* lengths, in
              int h, int max_dist, int bandwidth, int gap_base, int gap_log, int* result, int* f /* may be NULL */,
              int* pred /* may be NULL */, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Pileup, consensus and variant calls from mapped reads (wavenet_speech_amd/pileup.py): what the reads
+ * of a locus show together -- the counting step of samtools mpileup / consensus and bcftools call.  Integer arithmetic only; all
+ * pointers are DEVICE pointers.  Labels 1..4 are bases with complement 5 - v.  tests/pileup_ref.py holds the same definitions as
+ * plain loops.
+ *   wn_pileup: read b is query row b (query_stride elements, query_lengths[b] labels; qual rows of qual_stride bytes beside it)
+ *   aligned by the ops of row b (ops_stride bytes, ops_len[b] of them, as wn_pair_align wrote them) against the window
+ *   [lo[b], lo[b] + ref_lengths[b]) of the reference's forward strand IN READ ORIENTATION: on strand[b] = 1 reference index i of
+ *   the ops is forward position lo + ref_lengths - 1 - i and the read's labels are complemented.  With i_c / j_c the reference /
+ *   query index of column c as for wn_quality_profile, and [first, last] the first and last column whose op is 1 or 2:
+ *     counts      [R][2][6] int32   [forward position][strand][A, G, C, T, deletion, other]: a column in [first, last] with op 1 or
+ *                                   2 adds 1 at its position under the forward-strand base of its query label, or under `other`
+ *                                   if the label is outside 1..4 or its qual is below min_qual (only with qual); with op 3 under
+ *                                   `deletion`
+ *     ins_lengths [R][max_ins + 1]  a maximal run of l op-4 columns inside (first, last) lies between forward positions p and
+ *                                   p + 1 and adds 1 at [p][min(l, max_ins + 1) - 1]
+ *     ins_bases   [R][max_ins][4]   the k-th label of that run IN FORWARD ORDER, k < max_ins, adds 1 at [p][k][base] unless it is
+ *                                   outside 1..4 or below min_qual
+ *     used        [B] int8          1 added; 0 skipped: strand < 0, ref_lengths == 0, keep[b] == 0 (nothing else of such a read is
+ *                                   looked at), or no column with op 1 or 2; -1 bad
+ *   The tables are ADDED INTO (32-bit integer atomics: a position holds fewer than 2^31 reads), never cleared.  Columns outside
+ *   [first, last] enter nothing.  Two runs are bitwise identical.  A read that is not skipped is BAD when strand > 1, lo < 0,
+ *   ref_lengths < 0, lo + ref_lengths > reference_len, query_lengths outside [0, max_query_len], ops_len outside [0, max_ops], an
+ *   op is outside 1..4, the ops do not consume exactly ref_lengths and query_lengths labels, or a qual before query_lengths is
+ *   above 93: it adds nothing and counts once in *bad (DEVICE int, caller-zeroed, may be NULL).  No bad value is used as an index.
+ *   One workgroup per read, two passes over its ops; no workspace.
+ *   wn_consensus_call: per position p, with c[k] = counts[p][0][k] + counts[p][1][k] and d = c[0] + ... + c[4], r = reference[p]
+ *   (clamped to [0, 255]):
+ *     d < min_depth: the call is r, flag LOW_DEPTH.  Else the candidate is the k in 0..4 of greatest c[k], ties first to r - 1 (if r
+ *     is 1..4), then to the smallest k; if c[k] den > num d it is called (label k + 1, or 0 for k = 4: deleted; flag DELETION, or
+ *     SUBSTITUTION if the label is not r), else the call is r, flag AMBIGUOUS.  alt_count [R][2]: counts[p][.][k] of the called k
+ *     (of r - 1 where r was kept; 0 if r is no base).
+ *     The insertion after p, with n the sum of ins_lengths[p]: if d >= min_depth and n den > num d, its length is min(l + 1,
+ *     max_ins) for the fullest column l (ties to the smallest l), the label of slot k the fullest of ins_bases[p][k] (ties to the
+ *     smallest), and the first slot without any count ends it; ins_len [R] bytes its length, ins_out [R][max_ins] bytes the labels
+ *     then 0; flag INSERTION if the length is at least 1.
+ *   call, flags [R] bytes.  tile_offsets [ceil(R / 256)] int32: the exclusive prefix sum over tiles of 256 positions of the emitted
+ *   labels (call != 0) + ins_len; *total their sum (the length of the consensus).  Two launches: the calls with the tile totals, then
+ *   one workgroup that scans the totals.
+ *   wn_consensus_emit: offsets[p], p < R: where position p lands in the consensus; consensus: the labels -- the call if it is
+ *   not 0, then the insertion after p -- of which only indices below `capacity` are written.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_query_len, max_ops or reference_len < 1, a negative
+ * stride, min_qual, max_ins, num or capacity, min_depth or den < 1.  WN_ERR_UNSUPPORTED: batch > 65535, max_query_len > 8192, max_ops
+ * > 65535 + 8192, reference_len > 2^26, min_qual > 93, max_ins > 8, den > 2^15, num > den.  WN_ERR_NULL: any pointer but qual, keep
+ * and bad; ins_bases and ins_out only with max_ins > 0, consensus only with capacity > 0.  Nothing is read back or allocated. */
+#define WN_CALL_LOW_DEPTH 1
+#define WN_CALL_AMBIGUOUS 2
+#define WN_CALL_SUBSTITUTION 4
+#define WN_CALL_DELETION 8
+#define WN_CALL_INSERTION 16
+int wn_pileup(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+              const int* strand, const int* query, long long query_stride, const int* query_lengths,
+              const unsigned char* qual /* may be NULL */, long long qual_stride, const unsigned char* keep /* may be NULL */,
+              int batch, int max_query_len, int max_ops, int reference_len, int min_qual, int max_ins, int* counts,
+              int* ins_lengths, int* ins_bases /* with max_ins > 0 */, signed char* used, int* bad /* may be NULL */,
+              wn_stream_t stream);
+int wn_consensus_call(const int* counts, const int* ins_lengths, const int* ins_bases /* with max_ins > 0 */,
+                      const int* reference, int reference_len, int max_ins, int min_depth, int num, int den, unsigned char* call,
+                      unsigned char* ins_len, unsigned char* ins_out /* with max_ins > 0 */, unsigned char* flags, int* alt_count,
+                      int* tile_offsets, int* total, wn_stream_t stream);
+int wn_consensus_emit(const unsigned char* call, const unsigned char* ins_len, const unsigned char* ins_out /* with max_ins > 0 */,
+                      const int* tile_offsets, int reference_len, int max_ins, int capacity, int* offsets,
+                      int* consensus /* with capacity > 0 */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

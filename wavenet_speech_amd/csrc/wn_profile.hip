@@ -7,7 +7,8 @@
 //                            columns.  Column c of a tile belongs to thread c % 256.  Its reference index i_c / query index j_c
 //                            is the number of earlier columns that consume a reference / query label: per tile one wave ballot
 //                            each, the popcount of the lanes below, the four wave totals through LDS (two slots, by tile
-//                            parity: one barrier per tile), and a running base carried from tile to tile.
+//                            parity: one barrier per tile), and a running base carried from tile to tile (tile_scan in
+//                            wn_opscan.h, shared with wn_pileup.hip).
 //                            Pass 1 validates every column (op code, i_c / j_c against the lengths BEFORE the loads, the labels
 //                            against [0, classes), op 1 / 2 against the labels, qual <= 93, dwell >= 0), finds the first and
 //                            last match-or-mismatch column and the two totals.  A bad read stops there: its rows are cleared,
@@ -22,17 +23,13 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_opscan.h"
 #include <limits.h>
 
 namespace wn {
 
-constexpr int kPThreads = 256;
-constexpr int kPWaves = kPThreads / 64;
 constexpr int kPMaxClasses = 64;
-constexpr int kPQualRows = 94;                // qual 0..93
 constexpr int kPDwellRows = 33;               // dwell 0..31, and 32 for everything above
-constexpr int kPMaxQuery = 8192;              // wn_pair_align's limits
-constexpr int kPMaxRef = 65535;
 constexpr int kPTableMax = (kPMaxClasses + 1) * (kPMaxClasses + 1) + 3 * kPQualRows + 3 * kPDwellRows;
 
 struct ProfileArgs {
@@ -54,33 +51,6 @@ struct ProfileArgs {
     int* bad;
     int B, N, M, max_ops, C, count_ends;
 };
-
-// The exclusive prefix sums of two 0/1 values over the 256 columns of a tile, on top of the running bases, which move on by
-// the tile's totals.  Every thread of the workgroup calls it; `slot` alternates from tile to tile.
-__device__ __forceinline__ void tile_scan(bool is_ref, bool is_query, int tid, int (*slot)[kPWaves], int* base_ref,
-                                          int* base_query, int* i_c, int* j_c) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const unsigned long long m_ref = __ballot(is_ref), m_query = __ballot(is_query);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (lane == 0) {
-        slot[0][wave] = __popcll(m_ref);
-        slot[1][wave] = __popcll(m_query);
-    }
-    __syncthreads();
-    int off_ref = 0, off_query = 0, tot_ref = 0, tot_query = 0;
-#pragma unroll
-    for (int w = 0; w < kPWaves; ++w) {
-        const int r = slot[0][w], q = slot[1][w];
-        off_ref += w < wave ? r : 0;
-        off_query += w < wave ? q : 0;
-        tot_ref += r;
-        tot_query += q;
-    }
-    *i_c = *base_ref + off_ref + __popcll(m_ref & below);
-    *j_c = *base_query + off_query + __popcll(m_query & below);
-    *base_ref += tot_ref;
-    *base_query += tot_query;
-}
 
 __global__ __launch_bounds__(kPThreads) void quality_profile_kernel(const ProfileArgs a) {
     __shared__ int s_table[kPTableMax];

@@ -297,6 +297,19 @@ class ReadMapping(_MapFields):
         rows = torch.where(rev & (rows >= 1) & (rows <= 4), 5 - rows, rows)
         return torch.where(col < length[:, None], rows, torch.zeros_like(rows)).contiguous(), length.int()
 
+    def window(self, flank=0):
+        """(lo [B] int32, length [B] int32) on the device: the forward-strand position of the first base of the window that
+        labels(flank) cuts out, and the window's length (0 where unmapped).  Column c of the row labels(flank) returns is forward
+        position lo + c on strand 0 and lo + length - 1 - c on strand 1: what pileup() takes beside the alignment of that row.  No
+        host synchronisation."""
+        what = "ReadMapping.window"
+        if self.reference is None:
+            raise ValueError("wavenet_speech_amd.%s: these anchors were not seeded from a ReadIndex" % what)
+        flank = _int_in(what, "flank", flank, 0, MAX_REFERENCE)
+        lo = (self.ref_start.long() - flank).clamp(min=0)
+        hi = (self.ref_end.long() + flank).clamp(max=self.reference.R)
+        return lo.int(), torch.where(self.mapped, hi - lo, torch.zeros_like(lo)).int()
+
     def mapq(self):
         """[B] float32 on the device: minimap2's formula 40 (1 - runner_up / score) min(1, n_anchors / 10) ln(score / 16), clamped to
         [0, 60]; a missing runner-up counts as 0; 0 where unmapped.  A CHOICE taken over from minimap2, not calibrated here."""
