@@ -124,6 +124,13 @@ def test_into_table():
         Earlier.other = table
         with pytest.raises(ValueError, match="into.other must be a contiguous int64 tensor"):
             _args.into_table(Earlier, "other", shape, CPU, "tool")
+    # the int32 tables of pileup: the same rules with the dtype named
+    fresh = _args.into_table(None, "counts", (4, 5), CPU, "tool", torch.int32)
+    assert fresh.dtype == torch.int32 and tuple(fresh.shape) == (4, 5) and int(fresh.abs().sum()) == 0
+    Earlier.small = torch.ones(4, 5, dtype=torch.int32)
+    assert _args.into_table(Earlier, "small", (4, 5), CPU, "tool", torch.int32) is Earlier.small
+    with pytest.raises(ValueError, match="into.counts must be a contiguous int32 tensor"):
+        _args.into_table(Earlier, "counts", (4, 5), CPU, "tool", torch.int32)
 
 
 def test_note_bad_without_a_counter_is_a_no_op(monkeypatch):

@@ -212,7 +212,7 @@ def _profile(ops, ref, query, qual, dwell, count_ends):
 
 @pytest.mark.parametrize("count_ends", [False, True])
 def test_profile_of_the_longest_alignments(count_ends):
-    """the aligner's own ops at kPMaxQuery (8192 matches) and at kPMaxRef (65535 columns), through quality_profile"""
+    """the aligner's own ops at kPaMaxQuery (8192 matches) and at kPaMaxRef (65535 columns), through quality_profile"""
     a, b = C.identical_rows(C.SELF_CLOSED)
     _, _, ops, ops_len = _align([a], [b], R.EMBOSS, True)
     qual, dwell = C.profile_inputs(661, len(b))

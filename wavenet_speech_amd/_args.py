@@ -114,14 +114,32 @@ def scale_shift(x, B, device, what):
     return x.contiguous()
 
 
-def into_table(into, field, shape, device, what):
-    """the int64 table a call accumulates into: into.<field> itself (checked), or fresh zeros without one"""
+def into_table(into, field, shape, device, what, dtype=torch.int64):
+    """the table of `dtype` a call accumulates into: into.<field> itself (checked), or fresh zeros without one"""
     t = getattr(into, field) if into is not None else None
     if t is None:
-        return torch.zeros(shape, dtype=torch.int64, device=device)
-    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int64 tensor of shape %s on %s" % (what, field, shape, device))
+        return torch.zeros(shape, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous %s tensor of shape %s on %s"
+                         % (what, field, _names((dtype,)), shape, device))
     return t
+
+
+MAX_AFFINE_COST = 1024        # of the doubled integer costs
+
+
+def affine_costs(what, match, mismatch, gap_open, gap_extend):
+    """the four costs of an affine-gap alignment (pairwise_align, demux) as the kernels' integers, in half units"""
+    costs = []
+    for name, v in (("match", match), ("mismatch", mismatch), ("gap_open", gap_open), ("gap_extend", gap_extend)):
+        d = 2.0 * float(v)
+        if d != int(d):
+            raise ValueError("wavenet_speech_amd.%s: %s must be a multiple of 0.5, got %r" % (what, name, v))
+        costs.append(int(d))
+    if not (0 <= costs[3] <= costs[2] <= MAX_AFFINE_COST) or max(abs(costs[0]), abs(costs[1])) > MAX_AFFINE_COST:
+        raise ValueError("wavenet_speech_amd.%s: need 0 <= gap_extend <= gap_open <= %g and |match|, |mismatch| <= %g, got %r"
+                         % (what, MAX_AFFINE_COST / 2, MAX_AFFINE_COST / 2, (match, mismatch, gap_open, gap_extend)))
+    return costs
 
 
 def note_bad(bad, message, at_once=False):

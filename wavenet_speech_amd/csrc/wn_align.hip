@@ -26,6 +26,7 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
@@ -51,13 +52,6 @@ struct AlignArgs {
     int* bad;
     int B, C, T, Lmax, row_threads, blank, kind;   // kind: 0 logits, 1 probabilities, 2 log-probabilities
 };
-
-// lane i receives lane i-1's value (DPP wave_shr:1); lane 0 keeps `fill`
-__device__ __forceinline__ double wave_shift_right(double v, double fill) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 
 template <bool kMulti>
 __global__ __launch_bounds__(kMulti ? kAlnMaxThreads : 64) void ctc_align_kernel(const AlignArgs a) {
@@ -143,8 +137,8 @@ __global__ __launch_bounds__(kMulti ? kAlnMaxThreads : 64) void ctc_align_kernel
                 for (int i = 0; i < kAlnPer; ++i) n[i] = kNegInf;
                 if (tid == 0) { n[0] = eb; n[1] = S > 1 ? el[0] : kNegInf; }
             } else {
-                double left = wave_shift_right(d[kAlnPer - 1], kNegInf); // the left neighbour's last state
-                if (kMulti && lane == 0 && wave > 0) left = edge[(t - 1) & 1][wave - 1];
+                double left = wave_shr1(d[kAlnPer - 1], kNegInf);        // the left neighbour's last state
+                if (kMulti && lane == 0 && wave > 0) left = edge_left(edge, t, wave);
 #pragma unroll
                 for (int i = 0; i < kAlnPer; ++i) {
                     double m = d[i];
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(kMulti ? kAlnMaxThreads : 64) void ctc_align_kernel
 #pragma unroll
             for (int i = 0; i < kAlnPer; ++i) d[i] = n[i];
             if (kMulti) {
-                if (lane == 63) edge[t & 1][wave] = d[kAlnPer - 1];
+                edge_publish(edge, t, lane, wave, d[kAlnPer - 1]);
                 __syncthreads();                                         // one barrier per step: the slot of step t-1 is free again
             }
             if (tid < a.row_threads) bprow[(long long)t * a.row_threads + tid] = (unsigned short)bpw;

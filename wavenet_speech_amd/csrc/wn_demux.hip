@@ -41,13 +41,13 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
 constexpr int kDxMaxWindow = 512;
 constexpr int kDxMaxPatterns = 1024;
 constexpr int kDxMaxPatLen = 128;
-constexpr int kDxMaxCost = 1024;
 constexpr int kDxMaxLen = 1 << 24;
 constexpr int kDxShift = 10;                     // key = score << 10 | (1023 - start)
 constexpr int kDxStartMask = (1 << kDxShift) - 1;
@@ -97,10 +97,7 @@ __global__ __launch_bounds__(64) void demux_score_kernel(const DemuxScoreArgs a)
         const int* prow = a.patterns + (long long)k * a.pattern_stride;
         for (int i = 0; i < P; ++i) pat[i][lane] = prow[i];
     }
-    int pmax = P;                                                        // the longest pattern of the wave
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) pmax = max(pmax, __shfl_xor(pmax, m));
-    pmax = __builtin_amdgcn_readfirstlane(pmax);
+    const int pmax = __builtin_amdgcn_readfirstlane(wave_reduce(P, OpMax()));    // the longest pattern of the wave
     __syncthreads();
 
     const int go = a.go << kDxShift, ge = a.ge << kDxShift, ma = a.match << kDxShift, mi = a.mismatch << kDxShift;
@@ -160,17 +157,6 @@ struct DemuxPickArgs {
     int B, K, n_front, min_margin, require_both;
 };
 
-__device__ __forceinline__ long long dx_wave_max(long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ int dx_wave_max(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-
 __global__ __launch_bounds__(64) void demux_pick_kernel(const DemuxPickArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int* sc = a.score + (long long)b * a.K;
@@ -184,13 +170,13 @@ __global__ __launch_bounds__(64) void demux_pick_kernel(const DemuxPickArgs a) {
             const int s = sc[k];
             if (s != INT_MIN) key = max(key, (long long)s * 4096 + (4095 - k));
         }
-        key = dx_wave_max(key);
+        key = wave_reduce(key, OpMax());
         if (key == LLONG_MIN) { hit[end] = -1; hs[end] = -1; hb[end] = -1; he[end] = -1; ru[end] = INT_MIN; pass[end] = false; continue; }
         const int kb = 4095 - (int)(key & 4095), g = a.group[kb];
         int r = INT_MIN;
         for (int k = k0 + lane; k < k1; k += 64)
             if (a.group[k] != g) r = max(r, sc[k]);
-        r = dx_wave_max(r);
+        r = wave_reduce(r, OpMax());
         const int s = sc[kb];
         hit[end] = kb; hs[end] = s; ru[end] = r;
         hb[end] = a.start[(long long)b * a.K + kb]; he[end] = a.end[(long long)b * a.K + kb];
@@ -234,9 +220,7 @@ int wn_demux_scores(const int* labels, long long labels_stride, const int* lengt
     if (max_len <= 0 || max_pattern_len <= 0 || window <= 0 || labels_stride < 0 || pattern_stride < 0) return WN_ERR_BAD_SHAPE;
     if (batch > 65535 || max_len > kDxMaxLen || n_patterns > kDxMaxPatterns || max_pattern_len > kDxMaxPatLen || window > kDxMaxWindow)
         return WN_ERR_UNSUPPORTED;
-    if (gap_extend < 0 || gap_extend > gap_open || gap_open > kDxMaxCost || match > kDxMaxCost || match < -kDxMaxCost ||
-        mismatch > kDxMaxCost || mismatch < -kDxMaxCost)
-        return WN_ERR_UNSUPPORTED;
+    if (const int s = check_affine_costs(match, mismatch, gap_open, gap_extend)) return s;
     if (!labels || !lengths || !patterns || !pattern_lengths || !score || !start || !end) return WN_ERR_NULL;
     DemuxScoreArgs a = {};
     a.labels = labels; a.labels_stride = labels_stride; a.lengths = lengths;

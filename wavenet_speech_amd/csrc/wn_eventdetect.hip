@@ -42,6 +42,7 @@
 #include "wn_host.h"
 #include "wn_kernels.h"
 #include "wn_signal_dev.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
@@ -213,36 +214,6 @@ __global__ __launch_bounds__(kEdThreads) void event_peaks_kernel(const DetectArg
     }
 }
 
-// inclusive scan over the workgroup (sum, or max with kMax); *total: the last thread's value.  s_wave: 16 ints
-template <bool kMax>
-__device__ __forceinline__ int ed_block_scan(int v, int* s_wave, int tid, int identity, int* exclusive, int* total) {
-    const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(v, off);
-        if (lane >= off) v = kMax ? (t > v ? t : v) : v + t;
-    }
-    int ex = __shfl_up(v, 1);
-    if (lane == 0) ex = identity;
-    if (lane == 63) s_wave[wv] = v;
-    __syncthreads();
-    if (wv == 0) {
-        int x = lane < kEdRankThreads / 64 ? s_wave[lane] : identity;
-#pragma unroll
-        for (int off = 1; off < kEdRankThreads / 64; off <<= 1) {
-            const int t = __shfl_up(x, off);
-            if (lane >= off) x = kMax ? (t > x ? t : x) : x + t;
-        }
-        if (lane < kEdRankThreads / 64) s_wave[lane] = x;
-    }
-    __syncthreads();
-    const int before = wv > 0 ? s_wave[wv - 1] : identity;
-    *total = s_wave[kEdRankThreads / 64 - 1];
-    __syncthreads();                                                 // s_wave is free again
-    *exclusive = kMax ? (before > ex ? before : ex) : before + ex;
-    return kMax ? (before > v ? before : v) : before + v;
-}
-
 // the forced splits between a boundary and its predecessor; no division for the common gap within max_event_len
 __device__ __forceinline__ int ed_splits(int p, int prev, int M) { return p - prev > M ? (p - prev - 1) / M : 0; }
 
@@ -284,7 +255,8 @@ __global__ __launch_bounds__(kEdRankThreads) void event_ranks_kernel(const Detec
         }
         if (tid == 0) s_nbig = 0;
         int before, total_last;
-        ed_block_scan<true>(word ? wd * 64 + 63 - __clzll((long long)word) : -1, s_wave, tid, -1, &before, &total_last);
+        before = block_scan<kEdRankThreads / 64>(word ? wd * 64 + 63 - __clzll((long long)word) : -1, tid, s_wave, &total_last, OpMax(), -1);
+        __syncthreads();                                             // s_wave is free again
         if (before < last) before = last;
         int mine = 0, prev = before;
         if (M >= 64) {                                               // a gap inside a word is below 64 <= M: only the first boundary has splits
@@ -296,8 +268,9 @@ __global__ __launch_bounds__(kEdRankThreads) void event_ranks_kernel(const Detec
                 prev = p;
             }
         }
-        int ex, total;
-        ed_block_scan<false>(mine, s_wave, tid, 0, &ex, &total);
+        int total;
+        const int ex = block_scan<kEdRankThreads / 64>(mine, tid, s_wave, &total);
+        __syncthreads();                                             // s_wave is free again
         int rank = count + ex;
         prev = before;
         for (u64 rest = word; rest; rest &= rest - 1) {
@@ -374,11 +347,7 @@ __global__ __launch_bounds__(kEdThreads) void event_sums_kernel(const DetectArgs
             s1 += q;
             s2 += (long long)q * q;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s1 += __shfl_xor(s1, off);
-            s2 += __shfl_xor(s2, off);
-        }
+        wave_reduce_each(OpAdd(), s1, s2);
         if (lane == src) { sum = s1; sumsq = s2; }
     }
     if (!row) return;

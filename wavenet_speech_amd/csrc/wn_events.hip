@@ -22,6 +22,7 @@
 #include "wn_host.h"
 #include "wn_kernels.h"
 #include "wn_signal_dev.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
@@ -131,12 +132,8 @@ __global__ __launch_bounds__(kEvThreads) void kmer_events_kernel(const EventArgs
             s += q;
             s2 += (long long)q * q;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s += __shfl_xor(s, off);
-            s2 += __shfl_xor(s2, off);
-            bd |= __shfl_xor(bd, off);
-        }
+        wave_reduce_each(OpAdd(), s, s2);
+        bd = wave_reduce(bd, OpOr());
         if (lane == src) { sum = s; sumsq = s2; bad = bad || bd != 0; }
     }
     if (bad) { code = -4; sum = 0; sumsq = 0; }                      // the read is bad: the second launch rewrites its rows
@@ -144,9 +141,7 @@ __global__ __launch_bounds__(kEvThreads) void kmer_events_kernel(const EventArgs
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(a.flag + b, 1);
     const int n_used = __popcll(__ballot(code >= 0)), n_off = __popcll(__ballot(code == -1));
     const int n_skip = __popcll(__ballot(code == -2 || code == -3));
-    int n_samples = code >= 0 ? len : 0;                             // <= 64 * 65536 per wave
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n_samples += __shfl_xor(n_samples, off);
+    const int n_samples = wave_reduce(code >= 0 ? len : 0, OpAdd());     // <= 64 * 65536 per wave
     if (lane == 0) {
         if (n_used) atomicAdd(a.counts + 4 * b + 0, n_used);
         if (n_off) atomicAdd(a.counts + 4 * b + 1, n_off);

@@ -109,4 +109,12 @@ inline int check_taps(int in_channels, int out_channels, int skip_rows, int kern
     return WN_OK;
 }
 
+// wn_pair_align's limits, which the tools that walk its op strings (quality profile, pileup) share
+constexpr int kPaMaxQuery = 8192, kPaMaxRef = 65535;
+// the affine costs of wn_pair_align and wn_demux_scores: 0 <= gap_extend <= gap_open <= 1024, |match|, |mismatch| <= 1024
+inline int check_affine_costs(int match, int mismatch, int gap_open, int gap_extend) {
+    const auto in = [](int v) { return v >= -1024 && v <= 1024; };       // no abs: INT_MIN is a possible argument
+    return 0 <= gap_extend && gap_extend <= gap_open && gap_open <= 1024 && in(match) && in(mismatch) ? WN_OK : WN_ERR_UNSUPPORTED;
+}
+
 }  // namespace wn

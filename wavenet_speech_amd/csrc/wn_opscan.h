@@ -3,12 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wn_wave_dev.h"
+
 namespace wn {
 
 constexpr int kPThreads = 256;                // threads of a workgroup = op columns of a tile
 constexpr int kPWaves = kPThreads / 64;
-constexpr int kPMaxQuery = 8192;              // wn_pair_align's limits
-constexpr int kPMaxRef = 65535;
 constexpr int kPQualRows = 94;                // qual 0..93
 
 // The exclusive prefix sums of two 0/1 values over the 256 columns of a tile, on top of the running bases, which move on by
@@ -23,15 +23,9 @@ __device__ __forceinline__ void tile_scan(bool is_ref, bool is_query, int tid, i
         slot[1][wave] = __popcll(m_query);
     }
     __syncthreads();
-    int off_ref = 0, off_query = 0, tot_ref = 0, tot_query = 0;
-#pragma unroll
-    for (int w = 0; w < kPWaves; ++w) {
-        const int r = slot[0][w], q = slot[1][w];
-        off_ref += w < wave ? r : 0;
-        off_query += w < wave ? q : 0;
-        tot_ref += r;
-        tot_query += q;
-    }
+    int off_ref, off_query, tot_ref, tot_query;
+    wave_offsets<kPWaves>(slot[0], wave, &off_ref, &tot_ref);
+    wave_offsets<kPWaves>(slot[1], wave, &off_query, &tot_query);
     *i_c = *base_ref + off_ref + __popcll(m_ref & below);
     *j_c = *base_query + off_query + __popcll(m_query & below);
     *base_ref += tot_ref;

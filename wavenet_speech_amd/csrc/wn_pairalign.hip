@@ -38,14 +38,13 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
 constexpr int kPaPer = 8;                // consecutive query columns per thread
 constexpr int kPaMaxThreads = 1024;      // 8192 columns
-constexpr int kPaMaxQuery = kPaPer * kPaMaxThreads;
-constexpr int kPaMaxRef = 65535;
-constexpr int kPaMaxCost = 1024;
+static_assert(kPaMaxQuery == kPaPer * kPaMaxThreads);            // the limits themselves: wn_host.h
 constexpr int kPaRing = 2048;            // reference rows in LDS: two halves of 1024, loaded alternately
 constexpr int kPaChunk = 64;             // backpointer lookups of the trace per LDS window
 constexpr int kPaWinThreads = kPaChunk / kPaPer + 1;             // threads' words a chunk can touch: 9
@@ -70,11 +69,6 @@ struct PairAlignArgs {
     int B, N, M, W;                      // W = threads that own a column of the widest query
     int match, mismatch, go, ge, free_ends;
 };
-
-// lane i receives lane i-1's value (DPP wave_shr:1); lane 0 keeps `fill`
-__device__ __forceinline__ int pa_shift_right(int v, int fill) {
-    return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false);
-}
 
 template <bool kMulti>
 __global__ __launch_bounds__(kMulti ? kPaMaxThreads : 64) void pair_align_kernel(const PairAlignArgs a) {
@@ -119,8 +113,8 @@ __global__ __launch_bounds__(kMulti ? kPaMaxThreads : 64) void pair_align_kernel
             for (int i = tid; i < kPaRing / 2; i += nthr) ring[(k + i) & (kPaRing - 1)] = k + i < Nb ? ar[k + i] : 0;
             __syncthreads();
         }
-        int hl = pa_shift_right(send_h, 0), el = pa_shift_right(send_e, kPaNeg);
-        if (kMulti && lane == 0 && wave > 0) { const int2 v = edge[(k - 1) & 1][wave - 1]; hl = v.x; el = v.y; }
+        int hl = wave_shr1(send_h, 0), el = wave_shr1(send_e, kPaNeg);
+        if (kMulti && lane == 0 && wave > 0) { const int2 v = edge_left(edge, k, wave); hl = v.x; el = v.y; }
         if (tid == 0) { hl = border(k + 1); el = kPaNeg; }
         const int row = k - tid;                                         // this step's row is i = row + 1
         if (row >= 0 && row < Nb && tid < nact) {
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(kMulti ? kPaMaxThreads : 64) void pair_align_kernel
             }
         }
         if (kMulti) {
-            if (lane == 63) edge[k & 1][wave] = make_int2(send_h, send_e);
+            edge_publish(edge, k, lane, wave, make_int2(send_h, send_e));
             __syncthreads();                                             // one barrier per step: the slot of step k-1 is free again
         }
     }
@@ -284,9 +278,7 @@ int wn_pair_align(const int* ref, long long ref_stride, const int* ref_lengths, 
                   size_t workspace_bytes, int* bad, wn_stream_t stream) {
     const int rc = check_pair_align(batch, max_ref_len, max_query_len);
     if (rc != WN_OK) return rc;
-    if (gap_extend < 0 || gap_extend > gap_open || gap_open > kPaMaxCost || match > kPaMaxCost || match < -kPaMaxCost ||
-        mismatch > kPaMaxCost || mismatch < -kPaMaxCost)
-        return WN_ERR_UNSUPPORTED;
+    if (const int s = check_affine_costs(match, mismatch, gap_open, gap_extend)) return s;
     if (!ref || !ref_lengths || !query || !query_lengths || !score || (ops != nullptr) != (ops_len != nullptr)) return WN_ERR_NULL;
     const bool trace = ops || stats;
     if (trace) {

@@ -15,7 +15,7 @@
 //                          tile to tile).  The first column after a run adds the run's length, w - 1 - prev.  All adds are
 //                          32-bit integer atomics to global memory: integer addition commutes, so two runs are bitwise identical.
 //   consensus_call_kernel  grid (tiles of 256 positions), one position per thread: the call, the insertion, the flags, and the
-//                          tile's emitted total (a wave shuffle scan, the four wave totals through LDS).
+//                          tile's emitted total (block_scan of wn_wave_dev.h).
 //   consensus_scan_kernel  one workgroup: the exclusive prefix sum of the tile totals in place, the grand total to offsets[R].
 //   consensus_emit_kernel  grid (tiles): offsets[p] = the tile's offset + the scan within the tile, then the labels.
 // Three launches in stream order; no workgroup waits on another.  No floating point, no workspace, no scratch.  No value of an op,
@@ -29,7 +29,7 @@ namespace wn {
 
 constexpr int kUMaxIns = 8;
 constexpr int kUMaxReference = 1 << 26;
-constexpr int kUMaxOps = kPMaxRef + kPMaxQuery;
+constexpr int kUMaxOps = kPaMaxRef + kPaMaxQuery;
 constexpr int kUMaxDen = 1 << 15;
 constexpr int kUScanTile = kPThreads;         // positions per workgroup of the call and emit kernels
 
@@ -160,28 +160,6 @@ __global__ __launch_bounds__(kPThreads) void pileup_kernel(const PileupArgs a) {
     }
 }
 
-// exclusive prefix sum of v over the 256 threads of a workgroup and the workgroup's total; s_w: kPWaves ints of LDS
-__device__ __forceinline__ int block_scan(int v, int tid, int* s_w, int* total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kPWaves; ++w) {
-        const int t = s_w[w];
-        off += w < wave ? t : 0;
-        tot += t;
-    }
-    *total = tot;
-    return off + inc - v;
-}
-
 struct CallArgs {
     const int* counts;
     const int* ins_lengths;
@@ -280,7 +258,7 @@ __global__ __launch_bounds__(kPThreads) void consensus_call_kernel(const CallArg
         emitted = (label != 0 ? 1 : 0) + n_out;
     }
     int total;
-    block_scan(emitted, tid, s_w, &total);
+    block_scan<kPWaves>(emitted, tid, s_w, &total);
     if (tid == 0) a.tile_offsets[blockIdx.x] = total;
 }
 
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(kPThreads) void consensus_scan_kernel(int* tile_off
     int sum = 0;
     for (int t = t0; t < t1; ++t) sum += tile_offsets[t];
     int total;
-    int run = block_scan(sum, tid, s_w, &total);
+    int run = block_scan<kPWaves>(sum, tid, s_w, &total);
     for (int t = t0; t < t1; ++t) {
         const int v = tile_offsets[t];
         tile_offsets[t] = run;
@@ -324,7 +302,7 @@ __global__ __launch_bounds__(kPThreads) void consensus_emit_kernel(const EmitArg
         n_out = n_out < a.max_ins ? n_out : a.max_ins;
     }
     int total;
-    long long at = (long long)a.tile_offsets[blockIdx.x] + block_scan((label != 0 ? 1 : 0) + n_out, tid, s_w, &total);
+    long long at = (long long)a.tile_offsets[blockIdx.x] + block_scan<kPWaves>((label != 0 ? 1 : 0) + n_out, tid, s_w, &total);
     if (p >= a.R) return;
     a.offsets[p] = (int)at;
     if (label != 0) {
@@ -345,7 +323,7 @@ int wn_pileup(const unsigned char* ops, long long ops_stride, const int* ops_len
               wn_stream_t stream) {
     if (batch < 1 || max_query_len < 1 || max_ops < 1 || reference_len < 1) return WN_ERR_BAD_SHAPE;
     if (ops_stride < 0 || query_stride < 0 || qual_stride < 0 || min_qual < 0 || max_ins < 0) return WN_ERR_BAD_SHAPE;
-    if (batch > 65535 || max_query_len > kPMaxQuery || max_ops > kUMaxOps || reference_len > kUMaxReference) return WN_ERR_UNSUPPORTED;
+    if (batch > 65535 || max_query_len > kPaMaxQuery || max_ops > kUMaxOps || reference_len > kUMaxReference) return WN_ERR_UNSUPPORTED;
     if (min_qual >= kPQualRows || max_ins > kUMaxIns) return WN_ERR_UNSUPPORTED;
     if (!ops || !ops_len || !lo || !ref_lengths || !strand || !query || !query_lengths || !counts || !ins_lengths || !used)
         return WN_ERR_NULL;

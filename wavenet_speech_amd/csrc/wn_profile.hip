@@ -201,7 +201,7 @@ int wn_quality_profile(const unsigned char* ops, long long ops_stride, const int
     if (batch < 1 || max_ref_len < 1 || max_query_len < 1 || max_ops < 1 || classes < 1) return WN_ERR_BAD_SHAPE;
     if (ops_stride < 0 || ref_stride < 0 || query_stride < 0 || qual_stride < 0 || dwell_stride < 0) return WN_ERR_BAD_SHAPE;
     if (count_ends < 0 || count_ends > 1) return WN_ERR_BAD_SHAPE;
-    if (classes > kPMaxClasses || max_query_len > kPMaxQuery || max_ref_len > kPMaxRef) return WN_ERR_UNSUPPORTED;
+    if (classes > kPMaxClasses || max_query_len > kPaMaxQuery || max_ref_len > kPaMaxRef) return WN_ERR_UNSUPPORTED;
     if (max_ops > max_ref_len + max_query_len || batch > 65535) return WN_ERR_UNSUPPORTED;
     if (!ops || !ops_len || !ref || !ref_lengths || !query || !query_lengths) return WN_ERR_NULL;
     if ((q_counts != nullptr) != (qual != nullptr) || (dwell_counts != nullptr) != (dwell != nullptr)) return WN_ERR_NULL;

@@ -29,6 +29,7 @@
 #include "wn_host.h"
 #include "wn_kernels.h"
 #include "wn_philox.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
@@ -86,7 +87,7 @@ __device__ __forceinline__ int gamma_dwell(unsigned long long seed, unsigned lon
 
 __global__ __launch_bounds__(kRdTile) void reads_plan_kernel(const ReadsPlanArgs a) {
     __shared__ int wave_total[kRdTile / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int mb = a.max_bases, trim = 2 * a.window;
     const long long row = (long long)b * mb;
 
@@ -153,22 +154,9 @@ __global__ __launch_bounds__(kRdTile) void reads_plan_kernel(const ReadsPlanArgs
             if (d > a.max_dwell) { d = a.max_dwell; ++nclamped; }
             a.dwell[row + p] = d;
         }
-        int incl = d;                                                    // inclusive prefix inside the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        int before = carry, chunk = 0;
-#pragma unroll
-        for (int w = 0; w < kRdTile / 64; ++w) {
-            const int t = wave_total[w];
-            before += w < wave ? t : 0;
-            chunk += t;
-        }
-        if (p < K) a.starts[row + p] = before + incl - d;
+        int chunk, incl;
+        block_scan<kRdTile / 64>(d, tid, wave_total, &chunk, OpAdd(), 0, &incl);
+        if (p < K) a.starts[row + p] = carry + incl - d;                 // in this order the code is what it was before block_scan
         carry += chunk;
         __syncthreads();                                                 // wave_total is free again
     }

@@ -29,6 +29,7 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_wave_dev.h"
 
 namespace wn {
 
@@ -74,12 +75,7 @@ __device__ inline float sel_value(unsigned key) {
 __device__ inline void sel_scan(const unsigned* __restrict__ hist, unsigned rem, int lane, unsigned& digit, unsigned& rest) {
     const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];
     const unsigned s1 = h.x, s2 = s1 + h.y, s3 = s2 + h.z, s4 = s3 + h.w;
-    unsigned incl = s4;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
+    const unsigned incl = wave_scan(s4, lane, OpAdd());
     const unsigned excl = incl - s4;
     const unsigned long long mine = __ballot(rem >= excl && rem < incl);
     const int src = mine ? __ffsll((long long)mine) - 1 : 0;         // exactly one lane whenever rem < total

@@ -184,7 +184,6 @@ def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, in
 
 MAX_PAIR_QUERY = 8192
 MAX_PAIR_REF = 65535
-MAX_PAIR_COST = 1024          # of the doubled integer costs
 OP_PAD, OP_MATCH, OP_MISMATCH, OP_REF_GAP, OP_QUERY_GAP = 0, 1, 2, 3, 4
 
 
@@ -251,15 +250,7 @@ def pairwise_align(ref, ref_lengths, query, query_lengths, match=5, mismatch=-4,
     another one of the same score.  A length outside its range poisons the pair (score -2^30, counts -1, ops_len 0) and is
     reported through check_device_flags()."""
     what = "pairwise_align"
-    costs = []
-    for name, v in (("match", match), ("mismatch", mismatch), ("gap_open", gap_open), ("gap_extend", gap_extend)):
-        d = 2.0 * float(v)
-        if d != int(d):
-            raise ValueError("wavenet_speech_amd.%s: %s must be a multiple of 0.5, got %r" % (what, name, v))
-        costs.append(int(d))
-    if not (0 <= costs[3] <= costs[2] <= MAX_PAIR_COST) or max(abs(costs[0]), abs(costs[1])) > MAX_PAIR_COST:
-        raise ValueError("wavenet_speech_amd.%s: need 0 <= gap_extend <= gap_open <= %g and |match|, |mismatch| <= %g, got %r"
-                         % (what, MAX_PAIR_COST / 2, MAX_PAIR_COST / 2, (match, mismatch, gap_open, gap_extend)))
+    costs = _args.affine_costs(what, match, mismatch, gap_open, gap_extend)
     score, stats, ops, ops_len = _pair_align(what, ref, ref_lengths, query, query_lengths, costs, end_gaps_free, True, return_ops)
     if ops is not None:
         ops = ops[:, :int(ref.shape[1]) + int(query.shape[1])]       # a row without columns went in as one unused column

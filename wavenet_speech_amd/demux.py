@@ -28,7 +28,6 @@ from .decoding import DEFAULT_ALPHABET
 MAX_WINDOW = 512
 MAX_PATTERNS = 1024
 MAX_PATTERN_LEN = 128
-MAX_COST = 1024               # of the doubled integer costs
 MAX_READ_LEN = 1 << 24
 DEFAULT_COMPLEMENT = (0, 4, 3, 2, 1)          # of " AGCT": A <-> T, G <-> C, the blank stays
 # porechop's scoring scheme (match 3, mismatch -6, gap open -5, gap extend -2): a CHOICE in the spirit of porechop and guppy, not a
@@ -180,19 +179,6 @@ class Demultiplexed(namedtuple("Demultiplexed", "barcode trim hits runner_up sco
                 for g in self.barcode.cpu().tolist()]
 
 
-def _costs(what, match, mismatch, gap_open, gap_extend):
-    costs = []
-    for name, v in (("match", match), ("mismatch", mismatch), ("gap_open", gap_open), ("gap_extend", gap_extend)):
-        d = 2.0 * float(v)
-        if d != int(d):
-            raise ValueError("wavenet_speech_amd.%s: %s must be a multiple of 0.5, got %r" % (what, name, v))
-        costs.append(int(d))
-    if not (0 <= costs[3] <= costs[2] <= MAX_COST) or max(abs(costs[0]), abs(costs[1])) > MAX_COST:
-        raise ValueError("wavenet_speech_amd.%s: need 0 <= gap_extend <= gap_open <= %g and |match|, |mismatch| <= %g, got %r"
-                         % (what, MAX_COST / 2, MAX_COST / 2, (match, mismatch, gap_open, gap_extend)))
-    return costs
-
-
 def _scores(what, labels, lengths, patterns, window, costs):
     """the integer tables of wn_demux_scores with the checked rows and lengths they were made from"""
     if not isinstance(patterns, BarcodeSet):
@@ -229,7 +215,7 @@ def demux_scores(labels, lengths, patterns, window=150, match=DEFAULT_COSTS["mat
     calibrated for this basecaller.  Returns DemuxScores.  A read whose length is outside [0, L] poisons its row and is reported
     through check_device_flags()."""
     what = "demux_scores"
-    costs = _costs(what, match, mismatch, gap_open, gap_extend)
+    costs = _args.affine_costs(what, match, mismatch, gap_open, gap_extend)
     score, start, end, _ = _scores(what, labels, lengths, patterns, window, costs)
     return DemuxScores(score.float() * 0.5, start, end)
 
@@ -246,7 +232,7 @@ def demultiplex(labels, lengths, patterns, window=150, match=DEFAULT_COSTS["matc
     trim_start) if it passes, else the length).  min_fraction=0.6 and min_margin=6 (two matches) are a choice in the spirit of
     porechop's identity thresholds, not calibrated values.  Returns Demultiplexed."""
     what = "demultiplex"
-    costs = _costs(what, match, mismatch, gap_open, gap_extend)
+    costs = _args.affine_costs(what, match, mismatch, gap_open, gap_extend)
     if not isinstance(patterns, BarcodeSet):
         raise ValueError("wavenet_speech_amd.%s: patterns must be a BarcodeSet" % what)
     if not (isinstance(min_fraction, (int, float)) and 0.0 <= float(min_fraction) <= 1.0):

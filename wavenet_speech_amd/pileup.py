@@ -77,15 +77,6 @@ writes them (an indel with its anchor base); depth, alt_count: DP and AC; forwar
 insertion: those are not split by strand)."""
 
 
-def _table(into, field, shape, device, what):
-    t = getattr(into, field) if into is not None else None
-    if t is None:
-        return torch.zeros(shape, dtype=torch.int32, device=device)
-    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError("wavenet_speech_amd.%s: into.%s must be a contiguous int32 tensor of shape %s on %s" % (what, field, shape, device))
-    return t
-
-
 def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=None, min_qual=0, max_ins=4, keep=None, into=None):
     """Adds every read of a batch into the tables over the reference, one launch.
     alignment: a PairwiseAlignment with ops of the read against its window IN READ ORIENTATION, exactly as
@@ -138,9 +129,9 @@ def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=Non
         raise ValueError("wavenet_speech_amd.%s: into must be a Pileup, got %s" % (what, type(into).__name__))
     lib = _lib.load()
     with torch.cuda.device(dev):
-        counts = _table(into, "counts", (R, 2, 6), dev, what)
-        ins_lengths = _table(into, "ins_lengths", (R, max_ins + 1), dev, what)
-        ins_bases = _table(into, "ins_bases", (R, max_ins, 4), dev, what)
+        counts = _args.into_table(into, "counts", (R, 2, 6), dev, what, torch.int32)
+        ins_lengths = _args.into_table(into, "ins_lengths", (R, max_ins + 1), dev, what, torch.int32)
+        ins_bases = _args.into_table(into, "ins_bases", (R, max_ins, 4), dev, what, torch.int32)
         used = torch.empty(B, dtype=torch.int8, device=dev)
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
         _lib.check(lib.wn_pileup(_p(ops), ops.stride(0), _p(ops_len), _p(lo), _p(ref_lengths), _p(strand), _p(query), query.stride(0),
