@@ -943,6 +943,41 @@ int wn_consensus_emit(const unsigned char* call, const unsigned char* ins_len, c
                       const int* tile_offsets, int reference_len, int max_ins, int capacity, int* offsets,
                       int* consensus /* with capacity > 0 */, wn_stream_t stream);
 
+/* ---- Indel left-alignment of op strings (wavenet_speech_amd/leftalign.py): the step between wn_pair_align and
+ * wn_pileup that bcftools norm and GATK LeftAlignIndels run.  Every gap run of a row moves as far toward the START OF THE FORWARD
+ * STRAND as the sequences allow, so that forward and reverse reads place the gap of a repeat alike.  Integer comparisons only; all
+ * pointers are DEVICE pointers; tests/leftalign_ref.py holds the same definition as plain loops.
+ *   Row b of ops_in (ops_stride bytes, ops_len[b] ops as wn_pair_align wrote them: 1 match, 2 mismatch, 3 reference label against a
+ *   gap, 4 query label against a gap) aligns ref row b (ref_stride elements, ref_lengths[b] labels: the window IN READ ORIENTATION,
+ *   as wn_pair_align took it) with query row b.  WALK ORIENTATION is wn_pileup's: the row as it stands on strand[b] = 0; the row
+ *   and both sequences read back to front on strand[b] = 1 (no complement: labels are only compared).  In walk orientation, with
+ *   [first, last] the first and last column whose op is 1 or 2 and i_c / j_c the reference / query index of column c, one PASS is:
+ *     a run is a maximal stretch [c, c + l) of one gap op v strictly inside (first, last) (3s next to 4s are two runs); its barrier
+ *     g is the last column before c whose op is 3 or 4, or `first` if there is none after it; with (seq, x) = (ref, i_c) for v = 3
+ *     and (query, j_c) for v = 4, its shift s is the largest s <= c - g - 1 with seq[x - t] == seq[x - t + l] for t = 1..s; the
+ *     run's columns become [c - s, c - s + l) and the s aligned columns it passed follow it with their ops in the same order.
+ *   All runs of a pass are decided on the pass's input (their territories (g, c + l) are disjoint).  Passes repeat until one moves
+ *   nothing or max_passes have run; the result goes to row b of ops_out (out_stride bytes) turned back into read orientation.  The
+ *   multiset of ops, and so ops_len and every count of wn_pair_align, is kept; the score under affine costs never drops.
+ *     passes  [B] int32  the passes that moved a run (0: the row was normalised already)
+ *     settled [B] int8   1 a pass moved nothing: a fixed point; 0 max_passes ran and each moved something: the row is that many
+ *                        passes along and still a valid alignment; -1 bad
+ *   All max_ops bytes of a row are copied to ops_out first, whatever they hold.  A read with strand < 0 or ref_lengths == 0 is
+ *   SKIPPED: nothing else of it is looked at, passes 0, settled 1.  A read that is not skipped is BAD when strand > 1, ref_lengths
+ *   outside [1, max_ref_len], query_lengths outside [0, max_query_len], ops_len outside [0, max_ops], an op is outside 1..4, or
+ *   the ops do not consume exactly ref_lengths and query_lengths labels (a poisoned pair of wn_pair_align is one): its row stays
+ *   the copy, passes 0, settled -1, and it counts once in *bad (DEVICE int, caller-zeroed, may be NULL).  No bad value is used as
+ *   an index.  One launch, one workgroup per read, every pass in place on ops_out; nothing is read back or allocated.  ops_out must
+ *   not overlap ops_in.  workspace is not used (NULL and 0 are fine): there is no wn_gap_left_align_workspace_bytes.
+ * Checked before the launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_ref_len, max_query_len, max_ops or max_passes < 1, a
+ * negative stride.  WN_ERR_UNSUPPORTED: batch > 65535, max_query_len > 8192, max_ref_len > 65535, max_ops > 65535 + 8192,
+ * max_passes > 64.  WN_ERR_NULL: any pointer but workspace and bad.  WN_ERR_UNSUPPORTED: ops_out == ops_in. */
+int wn_gap_left_align(const unsigned char* ops_in, long long ops_stride, const int* ops_len, const int* ref, long long ref_stride,
+                      const int* ref_lengths, const int* query, long long query_stride, const int* query_lengths, const int* strand,
+                      int batch, int max_ref_len, int max_query_len, int max_ops, int max_passes, unsigned char* ops_out,
+                      long long out_stride, int* passes, signed char* settled, void* workspace /* may be NULL */,
+                      size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

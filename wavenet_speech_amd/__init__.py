@@ -30,6 +30,7 @@ from .demux import (BarcodeSet, Demultiplexed, DemuxScores, demultiplex, demux_s
 from .readmap import (Anchors, Minimizers, ReadIndex, ReadMapping, chain_anchors, map_reads, minimizers, paf_records,  # noqa: F401
                       read_index, seed_anchors)
 from .pileup import ConsensusCalls, Pileup, Variant, call_consensus, pileup, variant_records, vcf_records  # noqa: F401
+from .leftalign import LeftAligned, left_align  # noqa: F401
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

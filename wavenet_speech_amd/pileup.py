@@ -19,9 +19,10 @@ once, to size the consensus.  There is no CPU fallback: CPU tensors raise (the h
 tensors on any device).
 
 Labels are the decoders': 1..4 = A, G, C, T (DEFAULT_ALPHABET " AGCT"), the complement of v is 5 - v.
-Not built: realignment or left-normalisation of indels (a gap inside a repeat is placed by pairwise_align's tie rule in READ
-orientation, so forward and reverse reads may place it at opposite ends of the repeat and split its support), genotype
-likelihoods, diploid calling, a strand split for insertions, more than one reference ([R] positions of one row).
+A gap inside a repeat is placed by pairwise_align's tie rule in READ orientation, so forward and reverse reads may place it at
+opposite ends of the repeat and split its support: left_align (leftalign.py) between pairwise_align and pileup normalises that.
+Not built: realignment against candidate haplotypes, genotype likelihoods, diploid calling, a strand split for insertions, more
+than one reference ([R] positions of one row).
 """
 from collections import namedtuple
 
