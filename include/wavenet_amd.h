@@ -978,6 +978,63 @@ int wn_gap_left_align(const unsigned char* ops_in, long long ops_stride, const i
                       long long out_stride, int* passes, signed char* settled, void* workspace /* may be NULL */,
                       size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Genotype likelihoods and diploid calls (wavenet_speech_amd/genotype.py): what bcftools call and GATK
+ * do after the pileup -- every base weighed by its quality, and a genotype of two alleles per position with its quality.  Integer
+ * arithmetic only; all pointers are DEVICE pointers except weights_host.  tests/genotype_ref.py holds the same definitions as plain
+ * loops.
+ *   weights_host [3][94] int32 on the HOST: rows HOM, HET, MIS, columns qual 0..93, in units of 1/scale Phred, every entry in
+ *   [0, 2^20].  It is read during the call and travels to the kernel by value: no allocation, no copy.  The model (which weights)
+ *   is the caller's: genotype_weights() of the Python surface builds HOM = -10 log10(1 - e), HET = -10 log10((1 - e) / 2 + e / 6),
+ *   MIS = -10 log10(e / 3) with e = min(10^(-q / 10), 3 / 4), times scale, rounded.
+ *   wn_pileup_evidence: the walk of wn_pileup -- the same arguments, ops, end columns, orientation and complement, the same
+ *   skipped and bad reads, the same `used` and *bad:
+ *     evidence [R][5][3] int64   [forward position][A, G, C, T, deletion][HOM, HET, MIS]: a column that wn_pileup counts under base
+ *                                k adds weights[.][min(q, cap[b])] at [p][k][.], q the base's qual, or flat_qual without qual; a
+ *                                deletion column adds weights[.][min(gap_qual, cap[b])] at [p][4][.].  cap [B] bytes (the mapping
+ *                                quality as a ceiling; NULL: none).  min_qual is compared with the UNCAPPED qual, as in wn_pileup:
+ *                                the same columns go to `other` in both.  `other` and insertion columns add nothing.
+ *   The table is ADDED INTO (64-bit integer atomics: sums stay below 2^51 for fewer than 2^31 reads), never cleared.  Two runs are
+ *   bitwise identical.  One workgroup per read, two passes over its ops; no workspace.
+ *   wn_genotype_call: per position p, with E = evidence[p], d the depth of wn_consensus_call from counts[p], r = reference[p]
+ *   (clamped to [0, 255]), over the 15 unordered pairs (a <= b) of allele indices 0..4 in lexicographic order:
+ *     L(a, a) = E[a][HOM] + sum over x != a of E[x][MIS];  L(a, b) = E[a][HET] + E[b][HET] + sum over x not in {a, b} of E[x][MIS]
+ *     cost = L + alt_prior for every genotype but (r - 1, r - 1); with r outside 1..4 there is no such genotype and no prior is added
+ *     costs   [R][15] int64 (may be NULL)
+ *     alleles [R][2] bytes: the labels (k + 1, or 0 for the deletion) of the genotype least by (cost, is not (r - 1, r - 1), index),
+ *                           in allele-index order;  gq [R] int32: the second-least cost minus the least;  qual [R] int32: the cost
+ *                           of (r - 1, r - 1) minus the least; both clamped to 2^31 - 1
+ *     flags   [R] bytes: SUBSTITUTION if a called allele is a base other than r, DELETION if one is the deletion, HET if the two
+ *                           differ.  d < min_depth (looked at first): alleles (r, r), gq = qual = 0, flags LOW_DEPTH.  Else r
+ *                           outside 1..4: alleles (r, r), gq = qual = 0, no flag.  costs are written in either case.
+ *     The insertion after p, with n the sum of ins_lengths[p], m = max(d - n, 0) and HOM, HET, MIS the weights of gap_qual:
+ *     c0 = n MIS + m HOM, c1 = (n + m) HET + alt_prior, c2 = n HOM + m MIS + alt_prior (64-bit products).  ins_copies [R] bytes: the
+ *     index of the least, ties to fewer copies; ins_gq: the second least minus the least; ins_qual: c0 minus the least (clamped as
+ *     above).  With copies >= 1 the length and the labels are wn_consensus_call's (the fullest length column, the fullest base per
+ *     slot, the first empty slot ends it) without its fraction test, to ins_len [R] and ins_out [R][max_ins] bytes.  d < min_depth,
+ *     or copies >= 1 with an empty sequence: copies, length, ins_gq and ins_qual are 0.  Flags INSERTION with copies >= 1, and
+ *     INS_HET with copies == 1, whatever r is.
+ *   One launch, one position per thread; nothing is read back or allocated.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_query_len, max_ops or reference_len < 1, a negative
+ * stride, min_qual, flat_qual, gap_qual or max_ins, min_depth < 1.  WN_ERR_UNSUPPORTED: batch > 65535, max_query_len > 8192, max_ops
+ * > 65535 + 8192, reference_len > 2^26, min_qual, flat_qual or gap_qual > 93, max_ins > 8, alt_prior outside [0, 2^30].
+ * WN_ERR_NULL: any pointer but qual, keep, cap, bad and costs; ins_bases and ins_out only with max_ins > 0.  WN_ERR_UNSUPPORTED: a
+ * weight outside [0, 2^20] (the table is read only once it is known not to be NULL). */
+#define WN_CALL_HET 32
+#define WN_CALL_INS_HET 64
+int wn_pileup_evidence(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+                       const int* strand, const int* query, long long query_stride, const int* query_lengths,
+                       const unsigned char* qual /* may be NULL */, long long qual_stride,
+                       const unsigned char* keep /* may be NULL */, int batch, int max_query_len, int max_ops, int reference_len,
+                       const unsigned char* cap /* may be NULL */, const int* weights_host /* 3 * 94, HOST */, int flat_qual,
+                       int gap_qual, int min_qual, long long* evidence, signed char* used, int* bad /* may be NULL */,
+                       wn_stream_t stream);
+int wn_genotype_call(const long long* evidence, const int* counts, const int* ins_lengths,
+                     const int* ins_bases /* with max_ins > 0 */, const int* reference, int reference_len, int max_ins,
+                     int min_depth, int alt_prior, const int* weights_host /* 3 * 94, HOST */, int gap_qual,
+                     unsigned char* alleles, int* gq, int* qual, unsigned char* flags, unsigned char* ins_copies,
+                     unsigned char* ins_len, unsigned char* ins_out /* with max_ins > 0 */, int* ins_gq, int* ins_qual,
+                     long long* costs /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -31,6 +31,8 @@ from .readmap import (Anchors, Minimizers, ReadIndex, ReadMapping, chain_anchors
                       read_index, seed_anchors)
 from .pileup import ConsensusCalls, Pileup, Variant, call_consensus, pileup, variant_records, vcf_records  # noqa: F401
 from .leftalign import LeftAligned, left_align  # noqa: F401
+from .genotype import (Evidence, GenotypeRecord, Genotypes, GenotypeWeights, call_genotypes, genotype_records, genotype_weights,  # noqa: F401
+                       pileup_evidence, vcf_genotype_records)
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

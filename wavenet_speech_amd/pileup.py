@@ -21,8 +21,9 @@ tensors on any device).
 Labels are the decoders': 1..4 = A, G, C, T (DEFAULT_ALPHABET " AGCT"), the complement of v is 5 - v.
 A gap inside a repeat is placed by pairwise_align's tie rule in READ orientation, so forward and reverse reads may place it at
 opposite ends of the repeat and split its support: left_align (leftalign.py) between pairwise_align and pileup normalises that.
-Not built: realignment against candidate haplotypes, genotype likelihoods, diploid calling, a strand split for insertions, more
-than one reference ([R] positions of one row).
+Genotype likelihoods and diploid calls with QUAL are genotype.py's, on the same reads beside these tables.
+Not built: realignment against candidate haplotypes, a strand split for insertions, more than one reference ([R] positions of one
+row).
 """
 from collections import namedtuple
 
@@ -78,26 +79,14 @@ writes them (an indel with its anchor base); depth, alt_count: DP and AC; forwar
 insertion: those are not split by strand)."""
 
 
-def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=None, min_qual=0, max_ins=4, keep=None, into=None):
-    """Adds every read of a batch into the tables over the reference (DESIGN.md section 7q), one launch.
-    alignment: a PairwiseAlignment with ops of the read against its window IN READ ORIENTATION, exactly as
-    pairwise_align(*mapping.labels(flank), query, query_lengths) returns it; lo, ref_lengths, strand [B]: mapping.window(flank) and
-    mapping.strand; query [B, M] int32 or int64 GPU rows (M <= 8192) with query_lengths [B]; R: the reference's length, 1 to 2^26;
-    qual [B, >= M] uint8: BaseQualities.qual; min_qual in [0, 93]: a base below it counts as `other` (only with qual); max_ins in
-    [0, 8]; keep [B] bool: reads to add (mapping.mapq() >= 20, ...); into: an earlier Pileup of the same R and max_ins whose tables
-    are accumulated in place (and returned; `used` is replaced).
-    Ops 1 and 2 are alike an aligned pair (reference labels are not needed).  End columns -- everything before the first and after
-    the last aligned column -- enter nothing.  A reverse-strand read is counted as it reads on the forward strand: complemented,
-    insertions in forward order.  Adds are 32-bit: a position holds fewer than 2^31 reads.
-    Returns Pileup.  used is 0 for a read with strand < 0, ref_lengths == 0, keep false or no aligned column.  A pair whose ops do not
-    fit (an op outside 1..4, ops_len outside its row, labels not consumed exactly, strand > 1, a window outside [0, R], a qual above
-    93; a poisoned pair of pairwise_align) has used -1, adds nothing and is reported through check_device_flags()."""
-    what = "pileup"
+def _read_args(what, alignment, lo, ref_lengths, strand, query, query_lengths, R, qual, min_qual, keep):
+    """the checks and preparations of the reads of a batch that pileup and pileup_evidence (genotype.py) share: the two walk the same
+    columns of the same reads, so they refuse the same inputs in the same words -> (R, min_qual, ops, ops_len, lo, ref_lengths,
+    strand, query, query_lengths, qual, keep) as the C ABI takes them"""
     if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
         raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
     R = _int_in(what, "R", R, 1, MAX_REFERENCE)
     min_qual = _int_in(what, "min_qual", min_qual, 0, MAX_QUAL)
-    max_ins = _int_in(what, "max_ins", max_ins, 0, MAX_INS)
     ops, ops_len = _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
     width = int(query.shape[1]) if isinstance(query, torch.Tensor) and query.dim() == 2 else 0
     query, query_lengths = _pair_rows(query, query_lengths, what, "query")
@@ -126,6 +115,28 @@ def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=Non
         if keep.dtype != torch.bool or keep.shape != (B,):
             raise ValueError("wavenet_speech_amd.%s: keep must be bool of shape (%d,), got %s %s" % (what, B, keep.dtype, tuple(keep.shape)))
         keep = keep.to(device=dev, dtype=torch.uint8).contiguous()
+    return R, min_qual, ops, ops_len, lo, ref_lengths, strand, query, query_lengths, qual, keep
+
+
+def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=None, min_qual=0, max_ins=4, keep=None, into=None):
+    """Adds every read of a batch into the tables over the reference (DESIGN.md section 7q), one launch.
+    alignment: a PairwiseAlignment with ops of the read against its window IN READ ORIENTATION, exactly as
+    pairwise_align(*mapping.labels(flank), query, query_lengths) returns it; lo, ref_lengths, strand [B]: mapping.window(flank) and
+    mapping.strand; query [B, M] int32 or int64 GPU rows (M <= 8192) with query_lengths [B]; R: the reference's length, 1 to 2^26;
+    qual [B, >= M] uint8: BaseQualities.qual; min_qual in [0, 93]: a base below it counts as `other` (only with qual); max_ins in
+    [0, 8]; keep [B] bool: reads to add (mapping.mapq() >= 20, ...); into: an earlier Pileup of the same R and max_ins whose tables
+    are accumulated in place (and returned; `used` is replaced).
+    Ops 1 and 2 are alike an aligned pair (reference labels are not needed).  End columns -- everything before the first and after
+    the last aligned column -- enter nothing.  A reverse-strand read is counted as it reads on the forward strand: complemented,
+    insertions in forward order.  Adds are 32-bit: a position holds fewer than 2^31 reads.
+    Returns Pileup.  used is 0 for a read with strand < 0, ref_lengths == 0, keep false or no aligned column.  A pair whose ops do not
+    fit (an op outside 1..4, ops_len outside its row, labels not consumed exactly, strand > 1, a window outside [0, R], a qual above
+    93; a poisoned pair of pairwise_align) has used -1, adds nothing and is reported through check_device_flags()."""
+    what = "pileup"
+    max_ins = _int_in(what, "max_ins", max_ins, 0, MAX_INS)
+    R, min_qual, ops, ops_len, lo, ref_lengths, strand, query, query_lengths, qual, keep = _read_args(
+        what, alignment, lo, ref_lengths, strand, query, query_lengths, R, qual, min_qual, keep)
+    B, M, max_ops, dev = int(query.shape[0]), int(query.shape[1]), int(ops.shape[1]), query.device
     if into is not None and not isinstance(into, Pileup):
         raise ValueError("wavenet_speech_amd.%s: into must be a Pileup, got %s" % (what, type(into).__name__))
     lib = _lib.load()
