@@ -20,6 +20,7 @@
 //  * blockIdx -> (column tile, slab) mapping keeps all slabs of one column tile on one XCD
 //    (blocks b and b+8 share an XCD/L2), so the activation tile is fetched into one L2 only.
 #include <cstdlib>
+#include <type_traits>
 
 #include "wn_kernels.h"
 
@@ -225,6 +226,17 @@ __global__ __launch_bounds__(64, WPS) void series_gemm_kernel(const GemmArgs a) 
             if (c0 + t >= a.L) v[t] = 0.0f;
         return v;
     };
+    // The batched epilogues (EPI_ACCUM, EPI_DMASK, EPI_DGATE) come in two forms, chosen per wave by a wave-uniform test: a tile
+    // whose rows all lie below the destination's row count and whose columns all lie below L takes the FULL form -- no per-row
+    // condition, no row clamp in the fetch, no clip -- and every other tile the ragged one.  vmcnt counts loads and stores
+    // together, in issue order; at the join of a branch around a row's stores hipcc must assume the skipped stores were never
+    // issued, so every wait of the ragged form also covers the previous batch's stores and most of the look-ahead loads it
+    // has just issued.  The full form is straight-line code and its waits are the exact counts
+    // (tests/test_f32_epilogue_codegen.py).  Same arithmetic in the same order: the stored values are the same bits.
+    [[maybe_unused]] auto both_forms = [&](int rows, auto&& body) {
+        if (sl.row0 + 32 * MT <= rows && t0 + COLS <= a.L) body(std::true_type{});
+        else body(std::false_type{});
+    };
 
     if constexpr (EPI == EPI_LINEAR) {
         const GemmDst d = a.dst[sl.dst];
@@ -248,35 +260,38 @@ __global__ __launch_bounds__(64, WPS) void series_gemm_kernel(const GemmArgs a) 
         // used -- row-by-row load->add->store chains cost 45 us of a 112 us wave (tools/block_stamps.py)
         const GemmDst d = a.dst[sl.dst];
         constexpr int RB = 8, BPT = 16 / RB, NBATCH = MT * BPT;
-        breg_t old[2][RB];
         float* const tile = d.base + (long)b * d.cp * ld + colbase;
-        auto fetch = [&](int bi, breg_t (&dst)[RB]) {
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
+        both_forms(d.rows, [&](auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            breg_t old[2][RB];
+            auto fetch = [&](int bi, breg_t (&dst)[RB]) {
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
 #pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                int row = sl.row0 + 32 * m + rowof(r0 + i, h);
-                row = row < d.rows ? row : d.rows - 1;   // rows past the end are never stored: clamp, don't branch
-                dst[i] = *reinterpret_cast<const breg_t*>(tile + (long)row * ld);
-            }
-        };
-        fetch(0, old[0]);
-#pragma unroll
-        for (int bi = 0; bi < NBATCH; ++bi) {
-            if (bi + 1 < NBATCH) fetch(bi + 1, old[(bi + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                const int row = sl.row0 + 32 * m + rowof(r0 + i, h);
-                if (row < d.rows) {
-                    breg_t v;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) v[t] = acc[m][t][r0 + i] + old[bi & 1][i][t];
-                    *reinterpret_cast<breg_t*>(tile + (long)row * ld) = clip(v);
+                for (int i = 0; i < RB; ++i) {
+                    int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                    if constexpr (!FULL) row = row < d.rows ? row : d.rows - 1;   // rows past the end are never stored: clamp, don't branch
+                    dst[i] = *reinterpret_cast<const breg_t*>(tile + (long)row * ld);
                 }
+            };
+            fetch(0, old[0]);
+#pragma unroll
+            for (int bi = 0; bi < NBATCH; ++bi) {
+                if (bi + 1 < NBATCH) fetch(bi + 1, old[(bi + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                    if (FULL || row < d.rows) {
+                        breg_t v;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) v[t] = acc[m][t][r0 + i] + old[bi & 1][i][t];
+                        *reinterpret_cast<breg_t*>(tile + (long)row * ld) = FULL ? v : clip(v);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        });
     } else if constexpr (EPI == EPI_GATE) {
         // tiles (2i, 2i+1) hold a and g of the same 32 channels
 #pragma unroll
@@ -329,87 +344,100 @@ __global__ __launch_bounds__(64, WPS) void series_gemm_kernel(const GemmArgs a) 
         const GemmDst d = a.dst[sl.dst];
         const float slope = a.slope;
         constexpr int RB = 8, BPT = 16 / RB, NBATCH = MT * BPT;
-        breg_t msk[2][RB];
         const long tile_off = (long)b * d.cp * ld + colbase;
         float* const tile = d.base + tile_off;
         const float* const mtile = a.mask + tile_off;
-        auto fetch = [&](int bi, breg_t (&dst)[RB]) {
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
+        both_forms(d.rows, [&](auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            breg_t msk[2][RB];
+            auto fetch = [&](int bi, breg_t (&dst)[RB]) {
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
 #pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                int row = sl.row0 + 32 * m + rowof(r0 + i, h);
-                row = row < d.rows ? row : d.rows - 1;   // rows past the end are never stored: clamp, don't branch
-                dst[i] = *reinterpret_cast<const breg_t*>(mtile + (long)row * ld);
-            }
-        };
-        fetch(0, msk[0]);
-#pragma unroll
-        for (int bi = 0; bi < NBATCH; ++bi) {
-            if (bi + 1 < NBATCH) fetch(bi + 1, msk[(bi + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                const int row = sl.row0 + 32 * m + rowof(r0 + i, h);
-                if (row < d.rows) {
-                    breg_t v;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const float g = acc[m][t][r0 + i];
-                        v[t] = msk[bi & 1][i][t] > 0.0f ? g : g * slope;
-                    }
-                    *reinterpret_cast<breg_t*>(tile + (long)row * ld) = clip(v);
+                for (int i = 0; i < RB; ++i) {
+                    int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                    if constexpr (!FULL) row = row < d.rows ? row : d.rows - 1;   // rows past the end are never stored: clamp, don't branch
+                    dst[i] = *reinterpret_cast<const breg_t*>(mtile + (long)row * ld);
                 }
+            };
+            fetch(0, msk[0]);
+#pragma unroll
+            for (int bi = 0; bi < NBATCH; ++bi) {
+                if (bi + 1 < NBATCH) fetch(bi + 1, msk[(bi + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const int row = sl.row0 + 32 * m + rowof(r0 + i, h);
+                    if (FULL || row < d.rows) {
+                        breg_t v;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            const float g = acc[m][t][r0 + i];
+                            v[t] = msk[bi & 1][i][t] > 0.0f ? g : g * slope;
+                        }
+                        *reinterpret_cast<breg_t*>(tile + (long)row * ld) = FULL ? v : clip(v);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        });
     } else {  // EPI_DGATE: acc = dz ; da = dz*sg*(1-ta^2), dg = dz*ta*sg*(1-sg) with ta = z / sg
         // z/sg come from HBM: issue a whole batch of rows (up to 32 x 16 B per lane in flight) before using any of
-        // them -- row-by-row load->use chains cost 55 us of a 186 us wave (tools/block_stamps.py).
+        // them -- row-by-row load->use chains cost 55 us of a 186 us wave (tools/block_stamps.py).  One batch ahead, not two: with
+        // three buffers the full form's epilogue measured longer (130 300 against 123 400 cycles at MT = 2).
         constexpr int RB = (MT == 4) ? 8 : 4;   // rows per batch: 2 x RB x 16 B per lane in flight, one batch ahead
         constexpr int BPT = 16 / RB;            // batches per 32-row tile
         constexpr int NBATCH = MT * BPT;
-        breg_t vt[2][RB], vs[2][RB];
-        auto fetch = [&](int bi, breg_t (&ft)[RB], breg_t (&fs)[RB]) {
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
+        both_forms(a.gate_rows, [&](auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            breg_t vt[2][RB], vs[2][RB];
+            // (ch, this lane's first column) of utterance b.  The full form holds one 32-bit byte offset per row, shared by the four
+            // tensors, on wave-uniform plane pointers (check_layout keeps the byte offsets within a plane below 2^32) -- with a
+            // 64-bit offset per row and tensor, live from a row's fetch to its stores, the MT = 4 form ran out of registers
+            const long plane = (long)b * a.gate_cp * ld;
+            auto at = [&](auto* base, int ch) {
+                if constexpr (FULL) return (decltype(base))((char*)(base + plane) + 4u * ((unsigned)ch * (unsigned)ld + (unsigned)colbase));
+                else return base + ((long)b * a.gate_cp + ch) * ld + colbase;
+            };
+            auto fetch = [&](int bi, breg_t (&ft)[RB], breg_t (&fs)[RB]) {
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
 #pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                int ch = sl.row0 + 32 * m + rowof(r0 + i, h);
-                ch = ch < a.gate_rows ? ch : a.gate_rows - 1;   // clamp (never stored), no branch
-                const long o = ((long)b * a.gate_cp + ch) * ld + colbase;
-                ft[i] = *reinterpret_cast<const breg_t*>(a.z + o);      // z = tanh(a) sigmoid(g)
-                fs[i] = *reinterpret_cast<const breg_t*>(a.sg + o);
-            }
-        };
-        fetch(0, vt[0], vs[0]);
-#pragma unroll
-        for (int bi = 0; bi < NBATCH; ++bi) {
-            if (bi + 1 < NBATCH) fetch(bi + 1, vt[(bi + 1) & 1], vs[(bi + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const int m = bi / BPT, r0 = (bi % BPT) * RB;
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-                const int r = r0 + i;
-                const int ch = sl.row0 + 32 * m + rowof(r, h);
-                if (ch < a.gate_rows) {
-                    const long o = ((long)b * a.gate_cp + ch) * ld + colbase;
-                    const breg_t z_ = vt[bi & 1][i], sg_ = vs[bi & 1][i];
-                    breg_t va, vg;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        // tanh = z / sigmoid (not stored): da = dz s (1 - t^2) = dz (s - z t), dg = dz t s (1 - s) = dz z (1 - s);
-                        // s = 0 (sigmoid underflow) has z = 0 and both gradients 0
-                        const float dz = acc[m][t][r];
-                        const float tt = sg_[t] > 0.0f ? z_[t] / sg_[t] : 0.0f;
-                        va[t] = dz * (sg_[t] - z_[t] * tt);
-                        vg[t] = dz * z_[t] * (1.0f - sg_[t]);
-                    }
-                    *reinterpret_cast<breg_t*>(a.da + o) = clip(va);
-                    *reinterpret_cast<breg_t*>(a.dg + o) = clip(vg);
+                for (int i = 0; i < RB; ++i) {
+                    int ch = sl.row0 + 32 * m + rowof(r0 + i, h);
+                    if constexpr (!FULL) ch = ch < a.gate_rows ? ch : a.gate_rows - 1;   // clamp (never stored), no branch
+                    ft[i] = *reinterpret_cast<const breg_t*>(at(a.z, ch));      // z = tanh(a) sigmoid(g)
+                    fs[i] = *reinterpret_cast<const breg_t*>(at(a.sg, ch));
                 }
+            };
+            fetch(0, vt[0], vs[0]);
+#pragma unroll
+            for (int bi = 0; bi < NBATCH; ++bi) {
+                if (bi + 1 < NBATCH) fetch(bi + 1, vt[(bi + 1) & 1], vs[(bi + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                const int m = bi / BPT, r0 = (bi % BPT) * RB;
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const int r = r0 + i;
+                    const int ch = sl.row0 + 32 * m + rowof(r, h);
+                    if (FULL || ch < a.gate_rows) {
+                        const breg_t z_ = vt[bi & 1][i], sg_ = vs[bi & 1][i];
+                        breg_t va, vg;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            // tanh = z / sigmoid (not stored): da = dz s (1 - t^2) = dz (s - z t), dg = dz t s (1 - s) = dz z (1 - s);
+                            // s = 0 (sigmoid underflow) has z = 0 and both gradients 0
+                            const float dz = acc[m][t][r];
+                            const float tt = sg_[t] > 0.0f ? z_[t] / sg_[t] : 0.0f;
+                            va[t] = dz * (sg_[t] - z_[t] * tt);
+                            vg[t] = dz * z_[t] * (1.0f - sg_[t]);
+                        }
+                        *reinterpret_cast<breg_t*>(at(a.da, ch)) = FULL ? va : clip(va);
+                        *reinterpret_cast<breg_t*>(at(a.dg, ch)) = FULL ? vg : clip(vg);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        });
     }
 }
 
