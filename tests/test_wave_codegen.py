@@ -1,6 +1,8 @@
 """CPU (hipcc cross-compiles without a GPU): every csrc file that takes its wave and workgroup steps from csrc/wn_wave_dev.h compiles
 for gfx950, still holds the kernels it held before the steps moved there, and no kernel of it uses scratch (register spills, indexed
-local arrays), checked on the metadata of the generated assembly."""
+local arrays), checked on the metadata of the generated assembly.  wn_pileup.hip takes the walk over an op row from
+csrc/wn_opscan.h through lambdas: the same two properties hold it (tests/test_genotype_codegen.py holds wn_genotype.hip, the other
+file on that walk)."""
 import os
 import re
 import subprocess

@@ -1,9 +1,10 @@
-// Genotype likelihoods and diploid calls from mapped reads: the walk of wn_pileup.hip once more, adding
-// quality-weighted evidence instead of counts, and a call per position over the 15 unordered pairs of {A, G, C, T, deletion}.
+// Genotype likelihoods and diploid calls from mapped reads: the walk of wn_opscan.h with pileup_kernel's
+// checks, adding quality-weighted evidence instead of counts, and a call per position over the 15 unordered pairs of {A, G, C, T,
+// deletion}.
 //
-//   pileup_evidence_kernel  grid (batch), 256 threads, ONE WORKGROUP PER READ, two passes over the read's ops in tiles of 256
-//                           columns: pileup_kernel's walk (wn_opscan.h; a reverse-strand read walked back to front), its
-//                           validation and its end columns, without the third ballot -- insertion slots are not needed.  The
+//   pileup_evidence_kernel  grid (batch), 256 threads, ONE WORKGROUP PER READ: validate_ops with pileup_kernel's window and qual
+//                           checks, so that `used` and *bad agree with it, then walk_ops (a reverse-strand read walked back to
+//                           front), without the third ballot -- insertion slots are not needed.  The
 //                           weight table W[3][94] travels BY VALUE in the kernel-argument struct and is copied to LDS once: no
 //                           allocation, no copy call, graph-capturable.  A column that pileup_kernel counts under base k adds
 //                           W[HOM, HET, MIS][min(q, cap[b])] to evidence[lo + i][k][0..2], a deletion column W[.][min(gap_qual,
@@ -18,131 +19,85 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_opscan.h"
-#include <limits.h>
 
 namespace wn {
 
-constexpr int kGMaxIns = 8;
-constexpr int kGMaxReference = 1 << 26;
-constexpr int kGMaxOps = kPaMaxRef + kPaMaxQuery;
 constexpr int kGMaxWeight = 1 << 20;
 constexpr int kGMaxPrior = 1 << 30;
 constexpr int kGWeights = 3 * kPQualRows;     // rows HOM, HET, MIS
 constexpr int kGTile = kPThreads;             // positions per workgroup of the call kernel
 
 struct EvidenceArgs {
-    const unsigned char* ops;           // row b at ops + b * ops_stride
-    const int* ops_len;
-    const int* lo;
-    const int* ref_len;
-    const int* strand;
-    const int* query;
-    const int* query_len;
-    const unsigned char* qual;          // or nullptr
-    const unsigned char* keep;          // or nullptr
+    ReadBatch r;
     const unsigned char* cap;           // or nullptr
-    long long ops_stride, query_stride, qual_stride;
     unsigned long long* evidence;       // [R][5][3]
     signed char* used;
     int* bad;
-    int B, M, max_ops, R, min_qual, flat_qual, gap_qual;
+    int flat_qual, gap_qual;
     int w[kGWeights];                   // by value: 1128 bytes of the kernel-argument segment
 };
 
 __global__ __launch_bounds__(kPThreads) void pileup_evidence_kernel(const EvidenceArgs a) {
     __shared__ int s_slot[2][2][kPWaves];
-    __shared__ int s_w[kGWeights];
     __shared__ int s_lo, s_hi, s_bad;
+    __shared__ int s_w[kGWeights];
     const int b = blockIdx.x, tid = threadIdx.x;
 
-    const int strand = a.strand[b], n_ref = a.ref_len[b];
-    if (strand < 0 || n_ref == 0 || (a.keep && a.keep[b] == 0)) {    // skipped: nothing else of the read is looked at
+    const int strand = a.r.strand[b], n_ref = a.r.ref_len[b];
+    if (read_skipped(strand, n_ref, a.r.keep, b)) {                  // nothing else of the read is looked at
         if (tid == 0) a.used[b] = 0;
         return;
     }
-    const int n_ops = a.ops_len[b], n_query = a.query_len[b], lo = a.lo[b];
-    const bool head_ok = strand <= 1 && n_ref > 0 && lo >= 0 && (long long)lo + n_ref <= a.R && n_query >= 0 && n_query <= a.M &&
-                         n_ops >= 0 && n_ops <= a.max_ops;
-    const int n = head_ok ? n_ops : 0;                               // nothing of a read with a bad header is looked at
-    const bool rev = strand == 1;
-    const unsigned char* ops = a.ops + (long long)b * a.ops_stride;
-    const int* query = a.query + (long long)b * a.query_stride;
-    const unsigned char* qual = a.qual ? a.qual + (long long)b * a.qual_stride : nullptr;
+    const int n_ops = a.r.ops_len[b], n_query = a.r.query_len[b], lo = a.r.lo[b];
+    const bool header_ok = head_ok(strand, n_ref, lo >= 0 && (long long)lo + n_ref <= a.r.R, n_query, a.r.M, n_ops, a.r.max_ops);
+    const OpRow row = op_row(a.r.ops + (long long)b * a.r.ops_stride, header_ok, n_ops, n_ref, n_query, strand == 1);
+    const bool rev = row.rev;
+    const int* query = a.r.query + (long long)b * a.r.query_stride;
+    const unsigned char* qual = a.r.qual ? a.r.qual + (long long)b * a.r.qual_stride : nullptr;
 
     for (int t = tid; t < kGWeights; t += kPThreads) s_w[t] = a.w[t];
-    if (tid == 0) { s_lo = INT_MAX; s_hi = -1; s_bad = head_ok ? 0 : 1; }
+    validate_begin(tid, header_ok, &s_lo, &s_hi, &s_bad);
     __syncthreads();
 
-    // ---- pass 1: validate, first / last aligned walk index, totals (pileup_kernel's, so that `used` and *bad agree with it)
-    bool ok = true;
-    int first = INT_MAX, last = -1, base_ref = 0, base_query = 0, tile = 0;
-    for (int t0 = 0; t0 < n; t0 += kPThreads, ++tile) {
-        const int w = t0 + tid;
-        const bool active = w < n;
-        const int op = active ? (int)ops[rev ? n - 1 - w : w] : 0;
-        const bool is_ref = op >= 1 && op <= 3, is_query = op == 1 || op == 2 || op == 4;
-        int i, j;
-        tile_scan(is_ref, is_query, tid, s_slot[tile & 1], &base_ref, &base_query, &i, &j);
-        if (!active) continue;
-        if (op < 1 || op > 4) { ok = false; continue; }
-        if (is_ref && i >= n_ref) ok = false;
-        if (is_query) {
-            if (j < n_query) {
-                if (qual && qual[rev ? n_query - 1 - j : j] >= kPQualRows) ok = false;
-            } else ok = false;
-        }
-        if (op <= 2) {
-            first = w < first ? w : first;
-            last = w > last ? w : last;
-        }
-    }
-    if (base_ref != n_ref || base_query != n_query) ok = false;      // the ops consume exactly the labels
-    if (!ok) atomicOr(&s_bad, 1);
-    if (last >= 0) { atomicMin(&s_lo, first); atomicMax(&s_hi, last); }
-    __syncthreads();
-    if (s_bad != 0) {
-        if (tid == 0) {
-            a.used[b] = -1;
-            if (a.bad) atomicAdd(a.bad, 1);
-        }
+    // ---- pass 1: pileup_kernel's
+    OpWalk walk{s_slot};
+    const OpSpan span = validate_ops(row, tid, &walk, &s_lo, &s_hi, &s_bad, [&](const OpCol& c, bool, bool in_query) {
+        return !(in_query && qual && qual[rev ? n_query - 1 - c.j : c.j] >= kPQualRows);
+    });
+    if (span.bad) {
+        if (tid == 0) a.used[b] = -1;
+        report_bad(tid, a.bad);
         return;
     }
-    first = s_lo;
-    last = s_hi;
+    const int first = span.first, last = span.last;
     if (tid == 0) a.used[b] = last >= 0 ? 1 : 0;
     if (last < 0) return;                                            // no aligned column: end columns only
 
     // ---- pass 2: the adds.  Every index below was checked in pass 1 on the same words and is checked again before it is used
     const int cap = a.cap ? (int)a.cap[b] : kPQualRows - 1;
     const int q_gap = a.gap_qual < cap ? a.gap_qual : cap;           // gap_qual and flat_qual are at most 93: checked on the host
-    base_ref = base_query = 0;
-    for (int t0 = 0; t0 < n; t0 += kPThreads, ++tile) {
-        const int w = t0 + tid;
-        const bool active = w < n;
-        const int op = active ? (int)ops[rev ? n - 1 - w : w] : 0;
-        const bool is_ref = op >= 1 && op <= 3, is_query = op == 1 || op == 2 || op == 4;
-        int i, j;
-        tile_scan(is_ref, is_query, tid, s_slot[tile & 1], &base_ref, &base_query, &i, &j);       // the barrier is in here
-        if (!active || w < first || w > last || !is_ref || i >= n_ref) continue;                  // end and insertion columns enter nothing
+    walk_ops(row, tid, &walk, [&](const OpCol& c) {
+        const int w = c.w, i = c.i, j = c.j;
+        if (!c.active || w < first || w > last || !c.is_ref || i >= n_ref) return;                // end and insertion columns enter nothing
         int k = 4, q = q_gap;
-        if (op != 3) {
+        if (c.op != 3) {
             k = 5;                                                   // `other`, as in pileup_kernel
             if (j < n_query) {
                 const int jq = rev ? n_query - 1 - j : j;
                 const int v = query[jq];
                 const int qb = qual ? (int)qual[jq] : a.flat_qual;   // min_qual sees the uncapped qual
-                if (v >= 1 && v <= 4 && !(qual && qb < a.min_qual)) {
+                if (v >= 1 && v <= 4 && !(qual && qb < a.r.min_qual)) {
                     k = rev ? 4 - v : v - 1;
                     q = qb < cap ? qb : cap;
                 }
             }
         }
-        if (k > 4 || q < 0 || q >= kPQualRows) continue;
+        if (k > 4 || q < 0 || q >= kPQualRows) return;
         unsigned long long* e = a.evidence + ((size_t)(lo + i) * 5 + k) * 3;
         atomicAdd(e, (unsigned long long)s_w[q]);
         atomicAdd(e + 1, (unsigned long long)s_w[kPQualRows + q]);
         atomicAdd(e + 2, (unsigned long long)s_w[2 * kPQualRows + q]);
-    }
+    });
 }
 
 struct GenotypeArgs {
@@ -288,20 +243,15 @@ int wn_pileup_evidence(const unsigned char* ops, long long ops_stride, const int
                        const unsigned char* qual, long long qual_stride, const unsigned char* keep, int batch, int max_query_len,
                        int max_ops, int reference_len, const unsigned char* cap, const int* weights_host, int flat_qual, int gap_qual,
                        int min_qual, long long* evidence, signed char* used, int* bad, wn_stream_t stream) {
-    if (batch < 1 || max_query_len < 1 || max_ops < 1 || reference_len < 1) return WN_ERR_BAD_SHAPE;
-    if (ops_stride < 0 || query_stride < 0 || qual_stride < 0 || min_qual < 0 || flat_qual < 0 || gap_qual < 0) return WN_ERR_BAD_SHAPE;
-    if (batch > 65535 || max_query_len > kPaMaxQuery || max_ops > kGMaxOps || reference_len > kGMaxReference) return WN_ERR_UNSUPPORTED;
-    if (min_qual >= kPQualRows || flat_qual >= kPQualRows || gap_qual >= kPQualRows) return WN_ERR_UNSUPPORTED;
-    if (!ops || !ops_len || !lo || !ref_lengths || !strand || !query || !query_lengths || !weights_host || !evidence || !used)
-        return WN_ERR_NULL;
-    if (!weights_ok(weights_host)) return WN_ERR_UNSUPPORTED;
     EvidenceArgs a = {};
-    a.ops = ops; a.ops_len = ops_len; a.lo = lo; a.ref_len = ref_lengths; a.strand = strand; a.query = query;
-    a.query_len = query_lengths; a.qual = qual; a.keep = keep; a.cap = cap;
-    a.ops_stride = ops_stride; a.query_stride = query_stride; a.qual_stride = qual_stride;
-    a.evidence = (unsigned long long*)evidence; a.used = used; a.bad = bad;
-    a.B = batch; a.M = max_query_len; a.max_ops = max_ops; a.R = reference_len; a.min_qual = min_qual; a.flat_qual = flat_qual;
-    a.gap_qual = gap_qual;
+    a.r = read_batch(ops, ops_stride, ops_len, lo, ref_lengths, strand, query, query_stride, query_lengths, qual, qual_stride, keep, batch,
+                     max_query_len, max_ops, reference_len, min_qual);
+    if (const int s = check_read_batch(a.r, flat_qual >= 0 && gap_qual >= 0,
+                                       min_qual < kPQualRows && flat_qual < kPQualRows && gap_qual < kPQualRows,
+                                       weights_host && evidence && used))
+        return s;
+    if (!weights_ok(weights_host)) return WN_ERR_UNSUPPORTED;
+    a.cap = cap; a.evidence = (unsigned long long*)evidence; a.used = used; a.bad = bad; a.flat_qual = flat_qual; a.gap_qual = gap_qual;
     for (int t = 0; t < kGWeights; ++t) a.w[t] = weights_host[t];
     hipLaunchKernelGGL(pileup_evidence_kernel, dim3(batch), dim3(kPThreads), 0, (hipStream_t)stream, a);
     WN_HIP(hipGetLastError(), "pileup_evidence");
@@ -313,7 +263,7 @@ int wn_genotype_call(const long long* evidence, const int* counts, const int* in
                      unsigned char* alleles, int* gq, int* qual, unsigned char* flags, unsigned char* ins_copies, unsigned char* ins_len,
                      unsigned char* ins_out, int* ins_gq, int* ins_qual, long long* costs, wn_stream_t stream) {
     if (reference_len < 1 || max_ins < 0 || min_depth < 1 || gap_qual < 0) return WN_ERR_BAD_SHAPE;
-    if (reference_len > kGMaxReference || max_ins > kGMaxIns || gap_qual >= kPQualRows) return WN_ERR_UNSUPPORTED;
+    if (reference_len > kMaxReference || max_ins > kMaxIns || gap_qual >= kPQualRows) return WN_ERR_UNSUPPORTED;
     if (alt_prior < 0 || alt_prior > kGMaxPrior) return WN_ERR_UNSUPPORTED;
     if (!evidence || !counts || !ins_lengths || !reference || !weights_host || !alleles || !gq || !qual || !flags || !ins_copies ||
         !ins_len || !ins_gq || !ins_qual)

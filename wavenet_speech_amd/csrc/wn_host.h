@@ -109,8 +109,43 @@ inline int check_taps(int in_channels, int out_channels, int skip_rows, int kern
     return WN_OK;
 }
 
-// wn_pair_align's limits, which the tools that walk its op strings (quality profile, pileup) share
-constexpr int kPaMaxQuery = 8192, kPaMaxRef = 65535;
+// wn_pair_align's limits, which the tools that walk its op strings (quality profile, pileup, evidence, left-alignment) share, and
+// the limits of the tables over a reference (pileup, consensus and genotype calls)
+constexpr int kPaMaxQuery = 8192, kPaMaxRef = 65535, kPaMaxOps = kPaMaxRef + kPaMaxQuery;
+constexpr int kMaxReference = 1 << 26, kMaxIns = 8;
+
+// The reads of a batch as wn_pileup and wn_pileup_evidence take them: PileupArgs and EvidenceArgs begin with one.
+struct ReadBatch {
+    const unsigned char* ops;           // row b at ops + b * ops_stride
+    const int *ops_len, *lo, *ref_len, *strand, *query, *query_len;
+    const unsigned char *qual, *keep;   // each or nullptr
+    long long ops_stride, query_stride, qual_stride;
+    int B, M, max_ops, R, min_qual;
+};
+// from the arguments of the two entry points, in their order
+inline ReadBatch read_batch(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+                            const int* strand, const int* query, long long query_stride, const int* query_lengths,
+                            const unsigned char* qual, long long qual_stride, const unsigned char* keep, int batch, int max_query_len,
+                            int max_ops, int reference_len, int min_qual) {
+    return {ops, ops_len, lo, ref_lengths, strand, query, query_lengths, qual, keep, ops_stride, query_stride, qual_stride,
+            batch, max_query_len, max_ops, reference_len, min_qual};
+}
+
+// What the entry points over op rows and their queries check (wn_gap_left_align; through check_read_batch wn_pileup and
+// wn_pileup_evidence), one status class after the other; the caller hands in its own verdict for each class.
+inline int check_op_rows(int batch, int max_query_len, int max_ops, long long ops_stride, long long query_stride, bool own_shape_ok,
+                         bool own_supported, bool pointers_ok) {
+    if (batch < 1 || max_query_len < 1 || max_ops < 1 || ops_stride < 0 || query_stride < 0 || !own_shape_ok) return WN_ERR_BAD_SHAPE;
+    if (batch > 65535 || max_query_len > kPaMaxQuery || max_ops > kPaMaxOps || !own_supported) return WN_ERR_UNSUPPORTED;
+    return pointers_ok ? WN_OK : WN_ERR_NULL;
+}
+// the same for a filled-in ReadBatch, with the reference's length, the qual rows and the sign of min_qual (its ceiling, the
+// qual rows of the device tables, is the caller's)
+inline int check_read_batch(const ReadBatch& r, bool own_shape_ok, bool own_supported, bool own_pointers_ok) {
+    return check_op_rows(r.B, r.M, r.max_ops, r.ops_stride, r.query_stride,
+                         r.R >= 1 && r.qual_stride >= 0 && r.min_qual >= 0 && own_shape_ok, r.R <= kMaxReference && own_supported,
+                         r.ops && r.ops_len && r.lo && r.ref_len && r.strand && r.query && r.query_len && own_pointers_ok);
+}
 // the affine costs of wn_pair_align and wn_demux_scores: 0 <= gap_extend <= gap_open <= 1024, |match|, |mismatch| <= 1024
 inline int check_affine_costs(int match, int mismatch, int gap_open, int gap_extend) {
     const auto in = [](int v) { return v >= -1024 && v <= 1024; };       // no abs: INT_MIN is a possible argument

@@ -6,8 +6,8 @@
 //                       reverse-strand read is walked back to front by index arithmetic, as pileup_kernel does: walk index w is
 //                       column n - 1 - w, reference index n_ref - 1 - i, query index n_query - 1 - j.
 //     copy      the whole row goes to ops_out byte by byte, whatever it holds; a skipped or a bad read ends there.
-//     validate  pileup_kernel's pass 1 without the window and the qual: op codes, i / j against the lengths, the totals, and the
-//               first and last aligned walk index.
+//     validate  the validating pass of wn_opscan.h without the window and the qual, KEPT BY HAND here: op
+//               codes, i / j against the lengths, the totals, and the first and last aligned walk index.
 //     passes    every pass is ONE SWEEP OVER THE TILES FROM THE LAST TO THE FIRST, in place on ops_out.  What a column needs lies
 //               at or above it: D, the first column above whose op differs (the end of its stretch); c, the first gap column
 //               above (with v = op[c] and l = D(c) - c: the next run); and NS, the first STOPPER at or above it.  A stopper is a
@@ -36,7 +36,6 @@
 
 namespace wn {
 
-constexpr int kLMaxOps = kPaMaxRef + kPaMaxQuery;
 constexpr int kLMaxPasses = 64;
 constexpr int kLNone = INT_MAX;
 
@@ -224,12 +223,11 @@ int wn_gap_left_align(const unsigned char* ops_in, long long ops_stride, const i
                       long long out_stride, int* passes, signed char* settled, void* workspace, size_t workspace_bytes, int* bad,
                       wn_stream_t stream) {
     (void)workspace, (void)workspace_bytes;                          // the passes run in place on ops_out: none is needed
-    if (batch < 1 || max_ref_len < 1 || max_query_len < 1 || max_ops < 1 || max_passes < 1) return WN_ERR_BAD_SHAPE;
-    if (ops_stride < 0 || ref_stride < 0 || query_stride < 0 || out_stride < 0) return WN_ERR_BAD_SHAPE;
-    if (batch > 65535 || max_query_len > kPaMaxQuery || max_ref_len > kPaMaxRef || max_ops > kLMaxOps || max_passes > kLMaxPasses)
-        return WN_ERR_UNSUPPORTED;
-    if (!ops_in || !ops_len || !ref || !ref_lengths || !query || !query_lengths || !strand || !ops_out || !passes || !settled)
-        return WN_ERR_NULL;
+    if (const int s = check_op_rows(batch, max_query_len, max_ops, ops_stride, query_stride,
+                                    max_ref_len >= 1 && max_passes >= 1 && ref_stride >= 0 && out_stride >= 0,
+                                    max_ref_len <= kPaMaxRef && max_passes <= kLMaxPasses,
+                                    ops_in && ops_len && ref && ref_lengths && query && query_lengths && strand && ops_out && passes && settled))
+        return s;
     if (ops_out == ops_in) return WN_ERR_UNSUPPORTED;                // the input stays as it is: no aliasing
     LeftAlignArgs a = {};
     a.ops_in = ops_in; a.ops_out = ops_out; a.ops_len = ops_len; a.ref = ref; a.ref_len = ref_lengths; a.query = query;

@@ -2,13 +2,11 @@
 // (reference window, read) pair and adds what the read shows at every forward-strand position of the reference into tables over
 // the reference; then calls a consensus base and an insertion per position by integer rules and writes the consensus row.
 //
-//   pileup_kernel          grid (batch), 256 threads, ONE WORKGROUP PER READ, two passes over the read's ops in tiles of 256
-//                          columns, as quality_profile_kernel (wn_opscan.h: one ballot prefix sum per tile for the reference and
-//                          the query index).  A reverse-strand read is WALKED BACK TO FRONT: walk index w is column n - 1 - w,
-//                          query index n_query - 1 - j, label 5 - v.  Every column, and every insertion run with its slot order,
-//                          then arrives in forward orientation, and the forward position of a column is lo + i on both strands.
-//                          Pass 1 validates (op code, i / j against the lengths BEFORE any load, qual <= 93, the totals) and
-//                          finds the first and last aligned (op 1 or 2) walk index.  A bad read stops there.
+//   pileup_kernel          grid (batch), 256 threads, ONE WORKGROUP PER READ: the walk of wn_opscan.h (validate_ops with qual <= 93
+//                          as its own check, then a second pass by hand over the same loader and scan), plus the adds.  A
+//                          reverse-strand read is WALKED BACK TO FRONT: walk index w is column n - 1 - w, query index
+//                          n_query - 1 - j, label 5 - v.  Every column, and every insertion run with its slot order, then arrives
+//                          in forward orientation, and the forward position of a column is lo + i on both strands.
 //                          Pass 2 rescans.  An aligned column or a deletion adds 1 to counts[lo + i][strand][.].  An op-4 column
 //                          is slot w - prev - 1 of the insertion after lo + i - 1, prev the last column before it that is not an
 //                          op 4 (a third ballot: the highest lane below, the waves' last ones through LDS, a running value from
@@ -23,128 +21,88 @@
 #include "../../include/wavenet_amd.h"
 #include "wn_host.h"
 #include "wn_opscan.h"
-#include <limits.h>
 
 namespace wn {
 
-constexpr int kUMaxIns = 8;
-constexpr int kUMaxReference = 1 << 26;
-constexpr int kUMaxOps = kPaMaxRef + kPaMaxQuery;
 constexpr int kUMaxDen = 1 << 15;
 constexpr int kUScanTile = kPThreads;         // positions per workgroup of the call and emit kernels
 
 struct PileupArgs {
-    const unsigned char* ops;           // row b at ops + b * ops_stride
-    const int* ops_len;
-    const int* lo;
-    const int* ref_len;
-    const int* strand;
-    const int* query;
-    const int* query_len;
-    const unsigned char* qual;          // or nullptr
-    const unsigned char* keep;          // or nullptr
-    long long ops_stride, query_stride, qual_stride;
+    ReadBatch r;
     int* counts;                        // [R][2][6]
     int* ins_lengths;                   // [R][max_ins + 1]
     int* ins_bases;                     // [R][max_ins][4], nullptr with max_ins = 0
     signed char* used;
     int* bad;
-    int B, M, max_ops, R, min_qual, max_ins;
+    int max_ins;
 };
 
 __global__ __launch_bounds__(kPThreads) void pileup_kernel(const PileupArgs a) {
     __shared__ int s_slot[2][2][kPWaves];
-    __shared__ int s_last[2][kPWaves];
     __shared__ int s_lo, s_hi, s_bad;
+    __shared__ int s_last[2][kPWaves];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    const int strand = a.strand[b], n_ref = a.ref_len[b];
-    if (strand < 0 || n_ref == 0 || (a.keep && a.keep[b] == 0)) {    // skipped: nothing else of the read is looked at
+    const int strand = a.r.strand[b], n_ref = a.r.ref_len[b];
+    if (read_skipped(strand, n_ref, a.r.keep, b)) {                  // nothing else of the read is looked at
         if (tid == 0) a.used[b] = 0;
         return;
     }
-    const int n_ops = a.ops_len[b], n_query = a.query_len[b], lo = a.lo[b];
-    const bool head_ok = strand <= 1 && n_ref > 0 && lo >= 0 && (long long)lo + n_ref <= a.R && n_query >= 0 && n_query <= a.M &&
-                         n_ops >= 0 && n_ops <= a.max_ops;
-    const int n = head_ok ? n_ops : 0;                               // nothing of a read with a bad header is looked at
-    const bool rev = strand == 1;
-    const unsigned char* ops = a.ops + (long long)b * a.ops_stride;
-    const int* query = a.query + (long long)b * a.query_stride;
-    const unsigned char* qual = a.qual ? a.qual + (long long)b * a.qual_stride : nullptr;
+    const int n_ops = a.r.ops_len[b], n_query = a.r.query_len[b], lo = a.r.lo[b];
+    const bool header_ok = head_ok(strand, n_ref, lo >= 0 && (long long)lo + n_ref <= a.r.R, n_query, a.r.M, n_ops, a.r.max_ops);
+    const OpRow row = op_row(a.r.ops + (long long)b * a.r.ops_stride, header_ok, n_ops, n_ref, n_query, strand == 1);
+    const int n = row.n;
+    const bool rev = row.rev;
+    const int* query = a.r.query + (long long)b * a.r.query_stride;
+    const unsigned char* qual = a.r.qual ? a.r.qual + (long long)b * a.r.qual_stride : nullptr;
 
-    if (tid == 0) { s_lo = INT_MAX; s_hi = -1; s_bad = head_ok ? 0 : 1; }
+    validate_begin(tid, header_ok, &s_lo, &s_hi, &s_bad);
     __syncthreads();
 
     // ---- pass 1: validate, first / last aligned walk index, totals
-    bool ok = true;
-    int first = INT_MAX, last = -1, base_ref = 0, base_query = 0, tile = 0;
-    for (int t0 = 0; t0 < n; t0 += kPThreads, ++tile) {
-        const int w = t0 + tid;
-        const bool active = w < n;
-        const int op = active ? (int)ops[rev ? n - 1 - w : w] : 0;
-        const bool is_ref = op >= 1 && op <= 3, is_query = op == 1 || op == 2 || op == 4;
-        int i, j;
-        tile_scan(is_ref, is_query, tid, s_slot[tile & 1], &base_ref, &base_query, &i, &j);
-        if (!active) continue;
-        if (op < 1 || op > 4) { ok = false; continue; }
-        if (is_ref && i >= n_ref) ok = false;
-        if (is_query) {
-            if (j < n_query) {
-                if (qual && qual[rev ? n_query - 1 - j : j] >= kPQualRows) ok = false;
-            } else ok = false;
-        }
-        if (op <= 2) {
-            first = w < first ? w : first;
-            last = w > last ? w : last;
-        }
-    }
-    if (base_ref != n_ref || base_query != n_query) ok = false;      // the ops consume exactly the labels
-    if (!ok) atomicOr(&s_bad, 1);
-    if (last >= 0) { atomicMin(&s_lo, first); atomicMax(&s_hi, last); }
-    __syncthreads();
-    if (s_bad != 0) {
-        if (tid == 0) {
-            a.used[b] = -1;
-            if (a.bad) atomicAdd(a.bad, 1);
-        }
+    OpWalk walk{s_slot};
+    const OpSpan span = validate_ops(row, tid, &walk, &s_lo, &s_hi, &s_bad, [&](const OpCol& c, bool, bool in_query) {
+        return !(in_query && qual && qual[rev ? n_query - 1 - c.j : c.j] >= kPQualRows);
+    });
+    if (span.bad) {
+        if (tid == 0) a.used[b] = -1;
+        report_bad(tid, a.bad);
         return;
     }
-    first = s_lo;
-    last = s_hi;
+    const int first = span.first, last = span.last;
     if (tid == 0) a.used[b] = last >= 0 ? 1 : 0;
     if (last < 0) return;                                            // no aligned column: end columns only
 
     // ---- pass 2: the adds.  Ops, labels and quals are loaded again; every index below was checked in pass 1 on the same words (the
-    // inputs must not change while the launch runs: stream order gives that) and is checked again before it is used
+    // inputs must not change while the launch runs: stream order gives that) and is checked again before it is used.  The loop is
+    // this kernel's own: the third ballot's wave values go to LDS before the barrier inside the scan
     const unsigned long long below = (1ull << lane) - 1ull;
     const int ins_cols = a.max_ins + 1;
     int last_non4 = -1;
-    base_ref = base_query = 0;
-    for (int t0 = 0; t0 < n; t0 += kPThreads, ++tile) {
-        const int w = t0 + tid;
-        const bool active = w < n;
-        const int op = active ? (int)ops[rev ? n - 1 - w : w] : 0;
-        const bool is_ref = op >= 1 && op <= 3, is_query = op == 1 || op == 2 || op == 4;
-        const unsigned long long m_non4 = __ballot(active && op != 4);
-        if (lane == 0) s_last[tile & 1][wave] = m_non4 ? t0 + wave * 64 + 63 - __clzll((long long)m_non4) : -1;
-        int i, j;
-        tile_scan(is_ref, is_query, tid, s_slot[tile & 1], &base_ref, &base_query, &i, &j);       // the barrier is in here
+    walk.base_ref = walk.base_query = 0;
+    for (int t0 = 0; t0 < n; t0 += kPThreads) {
+        OpCol c = row.load(t0 + tid);
+        const int w = c.w, op = c.op, slot = walk.tile & 1;
+        const unsigned long long m_non4 = __ballot(c.active && op != 4);
+        if (lane == 0) s_last[slot][wave] = m_non4 ? t0 + wave * 64 + 63 - __clzll((long long)m_non4) : -1;
+        walk.scan(&c, tid);                                          // the barrier is in here
+        const int i = c.i, j = c.j;
         int prev = last_non4;                                        // the last walk index before w whose op is not 4
 #pragma unroll
         for (int v = 0; v < kPWaves; ++v) {
-            const int l = s_last[tile & 1][v];
+            const int l = s_last[slot][v];
             if (l >= 0) {
                 last_non4 = l;
                 if (v < wave) prev = l;
             }
         }
         if (m_non4 & below) prev = t0 + wave * 64 + 63 - __clzll((long long)(m_non4 & below));
-        if (!active || w < first || w > last) continue;              // end columns enter nothing
+        if (!c.active || w < first || w > last) continue;            // end columns enter nothing
         int col = 5;                                                 // of the query label: 0..3 a base on the forward strand, 5 other
-        if (is_query && j < n_query) {
+        if (c.is_query && j < n_query) {
             const int jq = rev ? n_query - 1 - j : j;
             const int v = query[jq];
-            if (v >= 1 && v <= 4 && !(qual && (int)qual[jq] < a.min_qual)) col = rev ? 4 - v : v - 1;
+            if (v >= 1 && v <= 4 && !(qual && (int)qual[jq] < a.r.min_qual)) col = rev ? 4 - v : v - 1;
         }
         if (op != 4) {
             if (i < n_ref) atomicAdd(a.counts + ((size_t)(lo + i) * 2 + strand) * 6 + (op == 3 ? 4 : col), 1);
@@ -321,19 +279,13 @@ int wn_pileup(const unsigned char* ops, long long ops_stride, const int* ops_len
               long long qual_stride, const unsigned char* keep, int batch, int max_query_len, int max_ops, int reference_len,
               int min_qual, int max_ins, int* counts, int* ins_lengths, int* ins_bases, signed char* used, int* bad,
               wn_stream_t stream) {
-    if (batch < 1 || max_query_len < 1 || max_ops < 1 || reference_len < 1) return WN_ERR_BAD_SHAPE;
-    if (ops_stride < 0 || query_stride < 0 || qual_stride < 0 || min_qual < 0 || max_ins < 0) return WN_ERR_BAD_SHAPE;
-    if (batch > 65535 || max_query_len > kPaMaxQuery || max_ops > kUMaxOps || reference_len > kUMaxReference) return WN_ERR_UNSUPPORTED;
-    if (min_qual >= kPQualRows || max_ins > kUMaxIns) return WN_ERR_UNSUPPORTED;
-    if (!ops || !ops_len || !lo || !ref_lengths || !strand || !query || !query_lengths || !counts || !ins_lengths || !used)
-        return WN_ERR_NULL;
-    if (max_ins > 0 && !ins_bases) return WN_ERR_NULL;
     PileupArgs a = {};
-    a.ops = ops; a.ops_len = ops_len; a.lo = lo; a.ref_len = ref_lengths; a.strand = strand; a.query = query;
-    a.query_len = query_lengths; a.qual = qual; a.keep = keep;
-    a.ops_stride = ops_stride; a.query_stride = query_stride; a.qual_stride = qual_stride;
-    a.counts = counts; a.ins_lengths = ins_lengths; a.ins_bases = ins_bases; a.used = used; a.bad = bad;
-    a.B = batch; a.M = max_query_len; a.max_ops = max_ops; a.R = reference_len; a.min_qual = min_qual; a.max_ins = max_ins;
+    a.r = read_batch(ops, ops_stride, ops_len, lo, ref_lengths, strand, query, query_stride, query_lengths, qual, qual_stride, keep, batch,
+                     max_query_len, max_ops, reference_len, min_qual);
+    if (const int s = check_read_batch(a.r, max_ins >= 0, min_qual < kPQualRows && max_ins <= kMaxIns,
+                                       counts && ins_lengths && used && (max_ins <= 0 || ins_bases)))
+        return s;
+    a.counts = counts; a.ins_lengths = ins_lengths; a.ins_bases = ins_bases; a.used = used; a.bad = bad; a.max_ins = max_ins;
     hipLaunchKernelGGL(pileup_kernel, dim3(batch), dim3(kPThreads), 0, (hipStream_t)stream, a);
     WN_HIP(hipGetLastError(), "pileup");
     return WN_OK;
@@ -341,7 +293,7 @@ int wn_pileup(const unsigned char* ops, long long ops_stride, const int* ops_len
 
 static int consensus_shape(int reference_len, int max_ins) {
     if (reference_len < 1 || max_ins < 0) return WN_ERR_BAD_SHAPE;
-    if (reference_len > kUMaxReference || max_ins > kUMaxIns) return WN_ERR_UNSUPPORTED;
+    if (reference_len > kMaxReference || max_ins > kMaxIns) return WN_ERR_UNSUPPORTED;
     return WN_OK;
 }
 

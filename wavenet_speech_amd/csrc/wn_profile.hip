@@ -8,7 +8,7 @@
 //                            is the number of earlier columns that consume a reference / query label: per tile one wave ballot
 //                            each, the popcount of the lanes below, the four wave totals through LDS (two slots, by tile
 //                            parity: one barrier per tile), and a running base carried from tile to tile (tile_scan in
-//                            wn_opscan.h, shared with wn_pileup.hip).
+//                            wn_opscan.h, whose header says what a valid op row is; pass 1 below is KEPT BY HAND: section 7u).
 //                            Pass 1 validates every column (op code, i_c / j_c against the lengths BEFORE the loads, the labels
 //                            against [0, classes), op 1 / 2 against the labels, qual <= 93, dwell >= 0), finds the first and
 //                            last match-or-mismatch column and the two totals.  A bad read stops there: its rows are cleared,

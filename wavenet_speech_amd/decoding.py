@@ -184,6 +184,8 @@ def ctc_forced_align(x, targets, target_lengths, input_lengths=None, blank=0, in
 
 MAX_PAIR_QUERY = 8192
 MAX_PAIR_REF = 65535
+MAX_OPS = MAX_PAIR_REF + MAX_PAIR_QUERY       # op columns of a row: what pileup, pileup_evidence and left_align take
+TILE = 256                                    # op columns per tile of the kernels that walk an op row (kPThreads in csrc/wn_opscan.h)
 OP_PAD, OP_MATCH, OP_MISMATCH, OP_REF_GAP, OP_QUERY_GAP = 0, 1, 2, 3, 4
 
 
@@ -403,6 +405,31 @@ def _profile_rows(rows, B, M, dtype, what, name):
     return _args.int_rows(rows, what, name, B=B, shape="(%d, >= %d)" % (B, M), min_width=M, dtypes=(dtype,), pad_empty=True)
 
 
+def _alignment_ops(alignment, what):
+    """(ops, ops_len) of a PairwiseAlignment with ops, GPU tensors: the first step of every walker of an op row"""
+    if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
+        raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
+    return _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
+
+
+def _op_rows(ops, ops_len, B, dev, what, on=None, cap=MAX_OPS, pad_empty=True):
+    """the second step, with B and the device known -> (ops, ops_len, max_ops) as the C ABI takes them.  on: the noun the message
+    names the device by (None: the caller has compared the devices); cap: the most columns (None: none); pad_empty: rows without
+    columns become one unused column"""
+    if ops.device != dev or ops_len.device != dev or ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] != B or \
+            ops_len.dtype != torch.int32 or ops_len.shape != (B,):
+        raise ValueError("wavenet_speech_amd.%s: alignment.ops must be uint8 of shape (%d, n) and ops_len int32 of shape (%d,)%s"
+                         % (what, B, B, ", on the device of the %s" % on if on else ""))
+    max_ops = int(ops.shape[1])
+    if cap is not None and max_ops > cap:
+        raise ValueError("wavenet_speech_amd.%s: at most %d op columns per read, got %d" % (what, cap, max_ops))
+    if pad_empty and max_ops < 1:                                    # no columns: one unused column
+        ops, max_ops = torch.zeros(B, 1, dtype=torch.uint8, device=dev), 1
+    if ops.shape[1] > 1 and ops.stride(1) != 1 or ops.stride(0) < 0:
+        ops = ops.contiguous()
+    return ops, ops_len.contiguous(), max_ops
+
+
 def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None, dwell=None, classes=5, count_ends=False,
                     into=None):
     """Walks each alignment of `pairwise_align(ref, ref_lengths, query, query_lengths)` and tabulates, for every query base,
@@ -419,9 +446,7 @@ def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None
     a qual above 93, a negative dwell, ...) has outcome 0, ref_index -1, read_counts -1, adds nothing to the tables and is
     reported through check_device_flags()."""
     what = "quality_profile"
-    if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
-        raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
-    ops, ops_len = _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
+    ops, ops_len = _alignment_ops(alignment, what)
     width = int(query.shape[1]) if isinstance(query, torch.Tensor) and query.dim() == 2 else 0
     ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
     query, query_lengths = _pair_rows(query, query_lengths, what, "query")
@@ -435,14 +460,8 @@ def quality_profile(alignment, ref, ref_lengths, query, query_lengths, qual=None
     if N > MAX_PAIR_REF or M > MAX_PAIR_QUERY:
         raise ValueError("wavenet_speech_amd.%s: at most %d reference and %d query labels per pair, got %d and %d"
                          % (what, MAX_PAIR_REF, MAX_PAIR_QUERY, N, M))
-    if ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] != B or ops_len.dtype != torch.int32 or ops_len.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: alignment.ops must be uint8 of shape (%d, n) and ops_len int32 of shape (%d,)" % (what, B, B))
-    max_ops = min(int(ops.shape[1]), N + M)
-    if max_ops < 1:                                                  # both sides without columns: one unused column
-        ops, max_ops = torch.zeros(B, 1, dtype=torch.uint8, device=dev), 1
-    if ops.shape[1] > 1 and ops.stride(1) != 1 or ops.stride(0) < 0:
-        ops = ops.contiguous()
-    ops_len = ops_len.contiguous()
+    ops, ops_len, max_ops = _op_rows(ops, ops_len, B, dev, what, cap=None)
+    max_ops = min(max_ops, N + M)
     qual = _profile_rows(qual, B, width, torch.uint8, what, "qual")
     dwell = _profile_rows(dwell, B, width, torch.int32, what, "dwell")
     if (qual is not None and qual.device != dev) or (dwell is not None and dwell.device != dev):

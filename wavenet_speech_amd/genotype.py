@@ -29,7 +29,7 @@ import torch
 from . import _args, _lib
 from ._args import _p, _stream
 from .decoding import DEFAULT_ALPHABET, MAX_QUAL
-from .pileup import DELETION, INSERTION, LOW_DEPTH, MAX_INS, SUBSTITUTION, Pileup, _read_args, _reference_labels
+from .pileup import DELETION, INSERTION, LOW_DEPTH, MAX_INS, SUBSTITUTION, Pileup, _note_bad_reads, _read_args, _reference_labels
 from .readmap import MAX_REFERENCE, _int_in
 
 HOM, HET, MIS = range(3)
@@ -37,7 +37,6 @@ QUAL_COLUMNS = MAX_QUAL + 1
 MAX_WEIGHT = 1 << 20
 MAX_ALT_PRIOR = 1 << 30
 GT_HET, INS_HET = 32, 64
-TILE = 256                                    # positions per tile of the call kernel
 GENOTYPES = tuple((a, b) for a in range(5) for b in range(a, 5))     # the 15 unordered pairs, in the order of `costs`
 
 
@@ -134,9 +133,7 @@ def pileup_evidence(alignment, lo, ref_lengths, strand, query, query_lengths, R,
                                           query.stride(0), _p(query_lengths), _p(qual), qual.stride(0) if qual is not None else 0, _p(keep),
                                           B, M, max_ops, R, _p(cap), ctypes.cast(table, ctypes.c_void_p), flat_qual, gap_qual, min_qual,
                                           _p(evidence), _p(used), _p(bad), _stream()), "wn_pileup_evidence")
-        _args.note_bad(bad, lambda n, R=R: "wavenet_speech_amd.pileup_evidence: %d pair(s) whose ops do not fit: an op outside 1..4, a "
-                       "length out of range, labels not consumed exactly, a strand above 1, a window outside [0, %d] or a qual above %d"
-                       % (n, R, MAX_QUAL))
+        _note_bad_reads(bad, what, R)
     return Evidence(evidence, used)
 
 

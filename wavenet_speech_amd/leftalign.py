@@ -18,10 +18,9 @@ import torch
 
 from . import _args, _lib
 from ._args import _p, _stream
-from .decoding import MAX_PAIR_QUERY, MAX_PAIR_REF, PairwiseAlignment, _pair_rows
+from .decoding import MAX_OPS, MAX_PAIR_QUERY, MAX_PAIR_REF, _alignment_ops, _op_rows, _pair_rows
 from .readmap import _int_in
 
-MAX_OPS = MAX_PAIR_REF + MAX_PAIR_QUERY
 MAX_PASSES = 64
 
 LeftAligned = namedtuple("LeftAligned", "alignment passes settled")
@@ -47,10 +46,8 @@ def left_align(alignment, ref, ref_lengths, query, query_lengths, strand, max_pa
     not fit (an op outside 1..4, a length outside its row, labels not consumed exactly, strand > 1; a poisoned pair of
     pairwise_align) is copied unchanged with settled -1 and reported through check_device_flags()."""
     what = "left_align"
-    if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
-        raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
     max_passes = _int_in(what, "max_passes", max_passes, 1, MAX_PASSES)
-    ops, ops_len = _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
+    ops, ops_len = _alignment_ops(alignment, what)
     ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
     query, query_lengths = _pair_rows(query, query_lengths, what, "query")
     B, N, M = int(ref.shape[0]), int(ref.shape[1]), int(query.shape[1])
@@ -60,13 +57,7 @@ def left_align(alignment, ref, ref_lengths, query, query_lengths, strand, max_pa
     if B < 1 or B > 65535 or N > MAX_PAIR_REF or M > MAX_PAIR_QUERY:
         raise ValueError("wavenet_speech_amd.%s: need 1 to 65535 pairs of at most %d reference and %d query labels, got %d of %d and %d"
                          % (what, MAX_PAIR_REF, MAX_PAIR_QUERY, B, N, M))
-    if ops.device != dev or ops_len.device != dev or ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] != B or \
-            ops_len.dtype != torch.int32 or ops_len.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: alignment.ops must be uint8 of shape (%d, n) and ops_len int32 of shape (%d,), on the "
-                         "device of the labels" % (what, B, B))
-    max_ops = int(ops.shape[1])
-    if max_ops > MAX_OPS:
-        raise ValueError("wavenet_speech_amd.%s: at most %d op columns per read, got %d" % (what, MAX_OPS, max_ops))
+    ops, ops_len, max_ops = _op_rows(ops, ops_len, B, dev, what, on="labels", pad_empty=False)
     strand = _args.lengths(strand, B, dev, what, "strand")
     passes = torch.empty(B, dtype=torch.int32, device=dev)
     settled = torch.empty(B, dtype=torch.int8, device=dev)
@@ -74,9 +65,6 @@ def left_align(alignment, ref, ref_lengths, query, query_lengths, strand, max_pa
         passes.zero_()
         settled.fill_(1)
         return LeftAligned(alignment._replace(ops=ops.clone()), passes, settled)
-    if ops.shape[1] > 1 and ops.stride(1) != 1 or ops.stride(0) < 0:
-        ops = ops.contiguous()
-    ops_len = ops_len.contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
         out = torch.empty(B, max_ops, dtype=torch.uint8, device=dev)

@@ -31,14 +31,12 @@ import torch
 
 from . import _args, _lib
 from ._args import _p, _stream
-from .decoding import DEFAULT_ALPHABET, MAX_PAIR_QUERY, MAX_PAIR_REF, MAX_QUAL, PairwiseAlignment, _pair_rows, _profile_rows
+from .decoding import DEFAULT_ALPHABET, MAX_OPS, MAX_PAIR_QUERY, MAX_QUAL, TILE, _alignment_ops, _op_rows, _pair_rows, _profile_rows
 from .readmap import MAX_REFERENCE, ReadIndex, _int_in
 
 MAX_INS = 8
-MAX_OPS = MAX_PAIR_REF + MAX_PAIR_QUERY
 MAX_DEN = 1 << 15
-TILE = 256                                    # op columns per tile of the pileup kernel
-SCAN_TILE = 256                               # positions per tile of the call and emit kernels
+SCAN_TILE = TILE                              # positions per tile of the call and emit kernels
 COL_A, COL_G, COL_C, COL_T, COL_DELETION, COL_OTHER = range(6)
 LOW_DEPTH, AMBIGUOUS, SUBSTITUTION, DELETION, INSERTION = 1, 2, 4, 8, 16
 
@@ -83,29 +81,16 @@ def _read_args(what, alignment, lo, ref_lengths, strand, query, query_lengths, R
     """the checks and preparations of the reads of a batch that pileup and pileup_evidence (genotype.py) share: the two walk the same
     columns of the same reads, so they refuse the same inputs in the same words -> (R, min_qual, ops, ops_len, lo, ref_lengths,
     strand, query, query_lengths, qual, keep) as the C ABI takes them"""
-    if not isinstance(alignment, PairwiseAlignment) or alignment.ops is None or alignment.ops_len is None:
-        raise ValueError("wavenet_speech_amd.%s: alignment must be a PairwiseAlignment with ops (return_ops=True)" % what)
     R = _int_in(what, "R", R, 1, MAX_REFERENCE)
     min_qual = _int_in(what, "min_qual", min_qual, 0, MAX_QUAL)
-    ops, ops_len = _args.gpu_tensor(alignment.ops, what, "alignment.ops"), _args.gpu_tensor(alignment.ops_len, what, "alignment.ops_len")
+    ops, ops_len = _alignment_ops(alignment, what)
     width = int(query.shape[1]) if isinstance(query, torch.Tensor) and query.dim() == 2 else 0
     query, query_lengths = _pair_rows(query, query_lengths, what, "query")
     B, M = int(query.shape[0]), int(query.shape[1])
     dev = query.device
     if B < 1 or B > 65535 or M > MAX_PAIR_QUERY:
         raise ValueError("wavenet_speech_amd.%s: need 1 to 65535 reads of at most %d labels, got %d of %d" % (what, MAX_PAIR_QUERY, B, M))
-    if ops.device != dev or ops_len.device != dev or ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] != B or \
-            ops_len.dtype != torch.int32 or ops_len.shape != (B,):
-        raise ValueError("wavenet_speech_amd.%s: alignment.ops must be uint8 of shape (%d, n) and ops_len int32 of shape (%d,), on the "
-                         "device of the query" % (what, B, B))
-    max_ops = int(ops.shape[1])
-    if max_ops > MAX_OPS:
-        raise ValueError("wavenet_speech_amd.%s: at most %d op columns per read, got %d" % (what, MAX_OPS, max_ops))
-    if max_ops < 1:                                                  # no columns: one unused column
-        ops, max_ops = torch.zeros(B, 1, dtype=torch.uint8, device=dev), 1
-    if ops.shape[1] > 1 and ops.stride(1) != 1 or ops.stride(0) < 0:
-        ops = ops.contiguous()
-    ops_len = ops_len.contiguous()
+    ops, ops_len, _ = _op_rows(ops, ops_len, B, dev, what, on="query")
     lo, ref_lengths, strand = (_args.lengths(x, B, dev, what, name) for x, name in ((lo, "lo"), (ref_lengths, "ref_lengths"), (strand, "strand")))
     qual = _profile_rows(qual, B, width, torch.uint8, what, "qual")
     if qual is not None and qual.device != dev:
@@ -116,6 +101,12 @@ def _read_args(what, alignment, lo, ref_lengths, strand, query, query_lengths, R
             raise ValueError("wavenet_speech_amd.%s: keep must be bool of shape (%d,), got %s %s" % (what, B, keep.dtype, tuple(keep.shape)))
         keep = keep.to(device=dev, dtype=torch.uint8).contiguous()
     return R, min_qual, ops, ops_len, lo, ref_lengths, strand, query, query_lengths, qual, keep
+
+
+def _note_bad_reads(bad, what, R):
+    """the report of the reads pileup and pileup_evidence refuse on the device: one text, the same reads"""
+    _args.note_bad(bad, lambda n: "wavenet_speech_amd.%s: %d pair(s) whose ops do not fit: an op outside 1..4, a length out of range, "
+                   "labels not consumed exactly, a strand above 1, a window outside [0, %d] or a qual above %d" % (what, n, R, MAX_QUAL))
 
 
 def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=None, min_qual=0, max_ins=4, keep=None, into=None):
@@ -150,9 +141,7 @@ def pileup(alignment, lo, ref_lengths, strand, query, query_lengths, R, qual=Non
                                  _p(query_lengths), _p(qual), qual.stride(0) if qual is not None else 0, _p(keep), B, M, max_ops, R,
                                  min_qual, max_ins, _p(counts), _p(ins_lengths), _p(ins_bases) if max_ins else None, _p(used), _p(bad),
                                  _stream()), "wn_pileup")
-        _args.note_bad(bad, lambda n, R=R: "wavenet_speech_amd.pileup: %d pair(s) whose ops do not fit: an op outside 1..4, a length "
-                       "out of range, labels not consumed exactly, a strand above 1, a window outside [0, %d] or a qual above %d"
-                       % (n, R, MAX_QUAL))
+        _note_bad_reads(bad, what, R)
     return Pileup(counts, ins_lengths, ins_bases, used)
 
 
