@@ -8,10 +8,9 @@ import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "wavenet_speech_amd", "csrc")
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+from tools.listing import HIPCC, NO_HIPCC, ROOT, listing
+
+pytestmark = pytest.mark.skipif(NO_HIPCC, reason="hipcc not installed")
 
 
 def test_cursor_matches_closed_form():
@@ -31,11 +30,7 @@ def test_cursor_matches_closed_form():
 def test_band_kernels_use_no_scratch():
     found = {}
     for src in ("wn_sigalign.hip", "wn_eventalign.hip"):
-        out = os.path.join(tempfile.mkdtemp(prefix="wn_asm_"), src.replace(".hip", ".s"))
-        r = subprocess.run([HIPCC, "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        text = open(out).read()
+        text = open(listing(src)).read()
         names = re.findall(r"\.name:\s+(_Z\S*(?:signal|event)_align_kernel\S*)", text)
         sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)
         assert len(names) == len(sizes), (names, sizes)

@@ -9,15 +9,14 @@ acknowledgement on every batch's critical path).  With a branch around each row'
 skipped path and waits for too much; the full-tile form is straight-line code, and its counts are exact.
 
 The test reads only waits, loads, stores and branches."""
-import os
 import re
 import subprocess
 
 import pytest
 
-from tests.test_kernel_codegen import HIPCC, _asm
+from tools.listing import NO_HIPCC, listing
 
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = pytest.mark.skipif(NO_HIPCC, reason="hipcc not installed")
 
 EPI_DGATE = 2
 LOAD = re.compile(r"(global|buffer|flat)_load_")
@@ -130,8 +129,8 @@ def failures(text):
     return out, seen
 
 
-def test_full_tile_dgate_epilogue_waits_for_exactly_its_rows(tmp_path):
-    text = open(_asm("wn_gemm.hip", tmp_path)).read()
+def test_full_tile_dgate_epilogue_waits_for_exactly_its_rows():
+    text = open(listing("wn_gemm.hip")).read()
     bad, seen = failures(text)
     assert seen == 4, seen                        # MT = 1 and 2 at two waves per SIMD, MT = 4 at prefetch depths 1 and 3
     assert not bad, "\n".join(bad)

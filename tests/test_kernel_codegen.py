@@ -6,41 +6,18 @@ the LDS-DMA rings, their design rest on -- checked on the assembly, because hipc
   the barrier and no compiler-inserted `vmcnt(0)` (hipcc did insert one in hwgrad_kernel)."""
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "wavenet_speech_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+from tools.listing import NO_HIPCC, ROOT, listing
+
+pytestmark = pytest.mark.skipif(NO_HIPCC, reason="hipcc not installed")
 
 
-# per-file flags of csrc/Makefile (FLAGS_<file>): the assembly checked here must be the product's
-EXTRA_FLAGS = {"wn_half.hip": ["-fno-slp-vectorize"], "wn_fused.hip": ["-fno-slp-vectorize"], "wn_col.hip": ["-fno-slp-vectorize"],
-               "wn_col_conv.hip": ["-fno-slp-vectorize"], "wn_col2.hip": ["-fno-slp-vectorize"], "wn_col_skip.hip": ["-fno-slp-vectorize"]}
-
-
-_ASM = {}
-
-
-def _asm(src, tmp_path):
-    """assembly listing of one kernel file, compiled once per test session (several tests read the same listing)"""
-    if src in _ASM and os.path.exists(_ASM[src]):
-        return _ASM[src]
-    import tempfile
-    out = os.path.join(tempfile.mkdtemp(prefix="wn_asm_"), src + ".s")
-    _ASM[src] = out
-    r = subprocess.run([HIPCC, "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only"] + EXTRA_FLAGS.get(src, []) +
-                       ["-S", os.path.join(CSRC, src), "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out
-
-
-def test_ring_kernels_keep_their_prefetch_in_flight(tmp_path):
-    files = [_asm("wn_half.hip", tmp_path), _asm("wn_half_wgrad.hip", tmp_path), _asm("wn_fused.hip", tmp_path)]
+def test_ring_kernels_keep_their_prefetch_in_flight():
+    files = [listing("wn_half.hip"), listing("wn_half_wgrad.hip"), listing("wn_fused.hip")]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_rings.py")] + files, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
     # 15 hgemm (12 at 128 rows, 3 at 256) + 24 hgemm8 + 3 hwgrad + 24 fused-forward instantiations
@@ -49,15 +26,15 @@ def test_ring_kernels_keep_their_prefetch_in_flight(tmp_path):
 
 @pytest.mark.parametrize("src", ["wn_gemm.hip", "wn_wgrad.hip", "wn_half.hip", "wn_half_wgrad.hip", "wn_fused.hip", "wn_col.hip", "wn_col_conv.hip", "wn_col_skip.hip", "wn_col2.hip", "wn_embed.hip",
                                  "wn_nll.hip", "wn_pack.hip"])
-def test_no_kernel_uses_scratch(src, tmp_path):
-    text = open(_asm(src, tmp_path)).read()
+def test_no_kernel_uses_scratch(src):
+    text = open(listing(src)).read()
     sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)
     assert sizes, "no kernel metadata found"
     assert all(int(x) == 0 for x in sizes), "scratch in use: %s" % sizes
     assert "scratch_store" not in text and "scratch_load" not in text
 
 
-def test_column_owner_kernels_wait_for_exactly_their_stage(tmp_path):
+def test_column_owner_kernels_wait_for_exactly_their_stage():
     """hcol_kernel (wn_col.hip) counts, per ring stage, everything that is younger than the stage's LDS-DMA pieces in the in-order
     vmcnt queue: the pieces of the stages after it and the compiler-visible loads its schedule has issued since.  The counts
     are template arithmetic; here the schedule is restated independently and compared with the `s_waitcnt vmcnt(N)` in front of
@@ -89,7 +66,7 @@ def test_column_owner_kernels_wait_for_exactly_their_stage(tmp_path):
 
     seen = 0
     for src in ("wn_col.hip", "wn_col_conv.hip", "wn_col_skip.hip"):
-        text = open(_asm(src, tmp_path)).read()
+        text = open(listing(src)).read()
         for m in re.finditer(r"^(_ZN2wn11hcol_kernel\w+):[^\n]*\n(.*?)\n\.Lfunc_end", text, re.S | re.M):
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             bf, nt, nks, epi = re.search(r"hcol_kernel<(\w+), (\d+), (\d+), (\d+)>", name).groups()
@@ -107,7 +84,7 @@ def test_column_owner_kernels_wait_for_exactly_their_stage(tmp_path):
     assert seen == 48 + 64 + 64, seen
 
 
-def test_paired_dx_dz_kernel_waits_for_exactly_its_stage(tmp_path):
+def test_paired_dx_dz_kernel_waits_for_exactly_its_stage():
     """hcol2_kernel (wn_col2.hip: dx of a block and dz of the block below it in one launch): the same exact-count discipline, with
     two products on one stage stream, a fragment stream that continues from dx's operands into dz's dS segment, the dgate inputs
     scheduled as dS dies, and the dx STORES between the two products counted for the stages whose pieces were issued before them."""
@@ -132,7 +109,7 @@ def test_paired_dx_dz_kernel_waits_for_exactly_its_stage(tmp_path):
             out.append(y)
         return out
 
-    text = open(_asm("wn_col2.hip", tmp_path)).read()
+    text = open(listing("wn_col2.hip")).read()
     seen = 0
     for m in re.finditer(r"^(_ZN2wn12hcol2_kernel\w+):[^\n]*\n(.*?)\n\.Lfunc_end", text, re.S | re.M):
         name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()

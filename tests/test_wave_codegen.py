@@ -3,16 +3,13 @@ for gfx950, still holds the kernels it held before the steps moved there, and no
 local arrays), checked on the metadata of the generated assembly.  wn_pileup.hip takes the walk over an op row from
 csrc/wn_opscan.h through lambdas: the same two properties hold it (tests/test_genotype_codegen.py holds wn_genotype.hip, the other
 file on that walk)."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+from tools.listing import NO_HIPCC, listing
+
+pytestmark = pytest.mark.skipif(NO_HIPCC, reason="hipcc not installed")
 
 # kernels per file, counted in the assembly of the commit before the shared header
 KERNELS = {"wn_reads.hip": 2, "wn_readmap.hip": 3, "wn_select.hip": 8, "wn_pileup.hip": 4, "wn_profile.hip": 1, "wn_eventdetect.hip": 5,
@@ -21,11 +18,7 @@ KERNELS = {"wn_reads.hip": 2, "wn_readmap.hip": 3, "wn_select.hip": 8, "wn_pileu
 
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_kernels_are_all_there_and_use_no_scratch(name):
-    out = os.path.join(tempfile.mkdtemp(prefix="wn_asm_"), name[:-4] + ".s")
-    r = subprocess.run([HIPCC, "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                        os.path.join(ROOT, "wavenet_speech_amd", "csrc", name), "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
+    text = open(listing(name)).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
     assert len(kernels) == KERNELS[name], kernels
     sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)

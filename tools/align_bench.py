@@ -18,18 +18,11 @@ from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import decoding as D  # noqa: E402
 from wavenet_speech_amd.functional import _p, _stream  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(reps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / reps
+    return timed(fn, calls=reps, warmup=warmup).median
 
 
 def loss_only(lib, x, labels, lens):
@@ -60,12 +53,13 @@ def main():
     lib = _lib.load()
     C = 5
     Bs, Ts = ([8], [1024]) if a.quick else ([8, 32], [1024, 4096])
+    rep = Report()
     lines = ["# CTC forced alignment next to the loss-only wn_ctc_loss call, C=%d, fp32 logits [B][C][T], %s; reps=%d warmup=%d"
              % (C, torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%4s %5s %5s %13s %13s %12s %11s %10s %10s %15s" % ("B", "T", "L", "align ms/batch", "loss ms/batch", "align us/step",
                                                                  "align/loss", "align ws MB", "loss ws MB", "cpu-ref ms/utt")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for B in Bs:
         for T in Ts:
             for L in (max(T // 10, 1), 2047):
@@ -88,16 +82,12 @@ def main():
                     t = time.perf_counter()
                     R.viterbi_align(lp, lh[0].tolist())
                     cpu = "%.0f %s" % ((time.perf_counter() - t) * 1e3, cpu)
-                s = "%4d %5d %5d %13.3f %13.3f %12.3f %11.2f %10.1f %10.1f %15s" % (
+                rep.emit("%4d %5d %5d %13.3f %13.3f %12.3f %11.2f %10.1f %10.1f %15s" % (
                     B, T, L, ms_align, ms_loss, ms_align * 1e3 / T, ms_align / ms_loss,
-                    lib.wn_ctc_align_workspace_bytes(B, C, T, L) / 2**20, loss_ws / 2**20, cpu)
-                print(s, flush=True)
-                lines.append(s)
+                    lib.wn_ctc_align_workspace_bytes(B, C, T, L) / 2**20, loss_ws / 2**20, cpu))
     torch.cuda.synchronize()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

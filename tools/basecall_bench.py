@@ -17,18 +17,11 @@ import torch  # noqa: E402
 import wavenet_speech_amd as W  # noqa: E402
 from wavenet_speech_amd import basecalling as BC  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(reps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / reps
+    return timed(fn, calls=reps, warmup=warmup).median
 
 
 def wall_ms(fn, reps, warmup):
@@ -70,12 +63,8 @@ def main():
     scale = torch.full((a.reads,), 1.0 / 60.0, device=dev)
     shift = torch.full((a.reads,), -500.0, device=dev)
     samples = int(lengths.sum())
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    rep = Report()
+    emit = rep.emit
     eager = W.Basecaller(net, chunk=a.chunk, batch=a.batch)
     left, right = eager.left, eager.right
     plan = BC.chunk_plan(lengths, a.chunk, left, right, 3)
@@ -115,9 +104,7 @@ def main():
                                                                  (ms_gather + ms_stitch) / ms_fwd))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

@@ -15,18 +15,11 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from wavenet_speech_amd import decoding as D  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(reps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / reps
+    return timed(fn, calls=reps, warmup=warmup).median
 
 
 def main():
@@ -42,13 +35,10 @@ def main():
     Bs, Ts, Ws = ([8], [1024], [1, 8, 32, 64]) if a.quick else ([8, 32], [1024, 4096], [1, 8, 32, 64])
     lines = ["# CTC decoding, C=%d, fp32 logits [B][C][T], %s; reps=%d warmup=%d" % (C, torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%-7s %4s %5s %3s %12s %14s %16s" % ("decoder", "B", "T", "W", "gpu ms/batch", "gpu us/step", "cpu-ref ms/batch")]
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    rep = Report()
+    emit = rep.emit
     for line in lines:
-        print(line, flush=True)
+        emit(line)
     ref_cache = {}
     for B in Bs:
         for T in Ts:
@@ -76,9 +66,7 @@ def main():
                 emit("%-7s %4d %5d %3d %12.3f %14.3f %16s" % ("beam", B, T, W, ms, ms * 1e3 / T, cpu))
     torch.cuda.synchronize()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

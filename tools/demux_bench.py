@@ -25,25 +25,15 @@ import wavenet_speech_amd as W  # noqa: E402
 from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd._args import _p, _stream  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 DEV = "cuda:0"
 SHIFT, MASK, NEG = 10, 1023, -(3 << 29)
 
 
 def gpu_ms(fn, reps, warmup, min_seconds):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    while True:
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(reps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms = t0.elapsed_time(t1)
-        if ms >= 1e3 * min_seconds or reps >= 4096:
-            return ms / reps, reps
-        reps *= 4
+    t = timed(fn, calls=reps, warmup=warmup, min_seconds=min_seconds)
+    return t.median, t.calls
 
 
 def torch_dp(window_rows, pat, costs, chunk=1024):
@@ -127,12 +117,13 @@ def main():
         host[b, :n[b]] = rng.integers(1, 5, n[b])
     labels, lengths = torch.from_numpy(host).to(DEV), torch.from_numpy(n.astype(np.int32)).to(DEV)
     codes = rng.integers(1, 5, (a.barcodes, 24))
+    rep = Report()
     lines = ["# demultiplexing: %d reads of %d..1200 labels x %d barcodes x both ends x window %d, costs 3/-6/5/2, %s"
              % (B, max(400, window), a.barcodes, window, torch.cuda.get_device_name(0)),
              "%4s %5s %16s %6s %14s %18s %20s %16s %8s" % ("P", "form", "scores ms/call", "reps", "cell updates/s", "demultiplex ms/call",
                                                           "torch DP ms/call", "torch updates/s", "ratio")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for flank, form in ((0, "reg32"), (8, "reg64"), (32, "reg96"), (52, "reg128")):
         ff, rf = rng.integers(1, 5, flank).tolist(), rng.integers(1, 5, flank).tolist()
         kit = W.BarcodeSet([c.tolist() for c in codes], front_flank=ff, rear_flank=rf)
@@ -157,14 +148,10 @@ def main():
                 assert torch.equal(got, ref), "the comparator's %s differs from the kernel's" % name
             tm, _ = gpu_ms(lambda: torch_tables(labels, lengths, kit, window, costs), 1, 1, 0.0)
             t_ms, t_rate, ratio = "%.1f" % tm, "%.3g" % (cells / (tm * 1e-3)), "%.0fx" % (tm / ms)
-        s = "%4d %5s %16.3f %6d %14.3g %18.3f %20s %16s %8s" % (P, form, ms, reps, cells / (ms * 1e-3), ms_all, t_ms, t_rate, ratio)
-        print(s, flush=True)
-        lines.append(s)
+        rep.emit("%4d %5s %16.3f %6d %14.3g %18.3f %20s %16s %8s" % (P, form, ms, reps, cells / (ms * 1e-3), ms_all, t_ms, t_rate, ratio))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

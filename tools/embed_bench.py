@@ -2,19 +2,13 @@
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wavenet_speech_amd import functional as HF
+from gputime import timed
 dev = "cuda:0"
 B, C, L = 16, 256, 16000
 w = torch.randn(C, 256, 2, device=dev, requires_grad=True); b = torch.randn(C, device=dev, requires_grad=True)
 q = torch.randint(0, 256, (B, L), device=dev); cot = torch.randn(B, C, L, device=dev)
 
-def t(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); e1.synchronize()
-    return e0.elapsed_time(e1) / n
+def t(fn, n=10): return timed(fn, calls=n, warmup=3).median
 
 y = HF.embed_conv(q, w, b)
 print("embed forward  %.3f ms" % t(lambda: HF.embed_conv(q, w, b)))

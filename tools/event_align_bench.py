@@ -22,7 +22,6 @@ Writes its table to --out, by default profiles/rNN/event_align_bench.txt in the 
 Usage: event_align_bench.py [--blocks N] [--calls N] [--out FILE] [--quick]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,31 +32,16 @@ from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
 from wavenet_speech_amd._args import _p, _stream  # noqa: E402
 
+from gputime import Report, next_profile_dir, timed  # noqa: E402
+
 FIRST, K = 2, 5
 DWELL = ("gamma", 4.0, 2000.0, 4000.0)          # mean 8 samples, shape 4
 
 
 def block_ms(fn, blocks, calls):
     """median, min, max over `blocks` of the ms per call of a block of `calls` calls, each block after one warm-up call"""
-    out = []
-    for _ in range(blocks):
-        fn()
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / calls)
-    out.sort()
-    return out[len(out) // 2], out[0], out[-1]
-
-
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
+    t = timed(fn, calls=calls, windows=blocks, warm_each=1)
+    return t.median, t.least, t.greatest
 
 
 def make_reads(B, bases, seed, dev):
@@ -172,6 +156,7 @@ def main():
     assert torch.cuda.is_available(), "event_align_bench.py measures the GPU; there is no CPU path"
     dev = torch.device("cuda:0")
     lib = _lib.load()
+    rep = Report()
     lines = ["# event_align against signal_align: k=%d, dwell %s, %s; device events around the C call, buffers allocated beforehand; "
              "median (min .. max) ms per call over %d blocks of %d calls (signal_align on the long reads: fewer, see the tool)"
              % (K, DWELL, torch.cuda.get_device_name(0), a.blocks, a.calls),
@@ -181,21 +166,17 @@ def main():
                  "reads", "bases", "band", "samples", "events", "longest", "event_align ms", "us/step", "signal_align (clean) ms", "us/step",
                  "true1.5", "hit", "none", "true3.0", "hit", "none", "sa true")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for bases in (2000,) if a.quick else (2000, 16000):
         for B in (32, 256):
             for band in (128, 512):
                 line = time_shape(lib, B, bases, band, a.blocks, a.calls, dev)
-                print(line, flush=True)
-                lines.append(line)
+                rep.emit(line)
     for line in move_rounds(dev):
-        print(line, flush=True)
-        lines.append(line)
+        rep.emit(line)
     W.check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "event_align_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

@@ -15,7 +15,6 @@ free rNN.
 Usage: events_bench.py [--reps N] [--warmup N] [--reads B] [--bases N] [--out FILE]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,24 +25,14 @@ from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
 from wavenet_speech_amd.functional import _p, _stream  # noqa: E402
 
+from gputime import Report, next_profile_dir, timed  # noqa: E402
+
 K, FIRST, FRAC_BITS, MAX_DWELL = 5, 2, 12, 255
 
 
 def gpu_ms(fn, reps, warmup):
     """(min, median, max) ms of one call"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
-    times.sort()
-    return times[0], times[len(times) // 2], times[-1]
+    return timed(fn, windows=reps, warmup=warmup)[:3]
 
 
 def torch_tables(signal, signal_lengths, starts, kmers, live):
@@ -66,12 +55,6 @@ def torch_tables(signal, signal_lengths, starts, kmers, live):
     hist = torch.zeros(4 ** K * (MAX_DWELL + 1), dtype=torch.int64, device=signal.device)
     hist.index_add_(0, ev_code * (MAX_DWELL + 1) + length, torch.ones_like(length))
     return stats, hist.view(4 ** K, MAX_DWELL + 1)
-
-
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
 
 
 def main():
@@ -126,23 +109,21 @@ def main():
     assert torch.equal(t_stats, ev.kmer_stats) and torch.equal(rows[3], ev.sum) and int(bad) == 0
     work = [("wn_kmer_events (C ABI)", abi), ("wn_kmer_events, tables only", lambda: abi([None] * 5)), ("kmer_events (Python)", user),
             ("torch ops", lambda: torch_tables(signal, reads.signal_lengths, reads.starts, kmers, live))]
+    rep = Report()
     lines = ["# event tables: %d reads, %d samples (%.1f MB of float32 signal), %d events, k=%d, frac_bits=%d, max_dwell=%d, %s; "
              "reps=%d warmup=%d; ms per call: min / median / max" % (B, samples, samples * 4 / 1e6, events, K, FRAC_BITS, MAX_DWELL,
                                                                     torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%-30s %28s %14s %10s" % ("form", "ms", "signal GB/s", "vs torch")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     results = [(name, gpu_ms(fn, a.reps, a.warmup)) for name, fn in work]
     base = results[-1][1][1]
     for name, t in results:
         line = "%-30s %28s %14.1f %10.2f" % (name, "%.3f / %.3f / %.3f" % t, samples * 4 / (t[1] * 1e-3) / 1e9, base / t[1])
-        print(line, flush=True)
-        lines.append(line)
+        rep.emit(line)
     W.check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "events_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

@@ -13,6 +13,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import wavenet_speech_amd as W  # noqa: E402
 
+import gputime  # noqa: E402
+
 RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 BLOCKS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 dev = torch.device("cuda:0")
@@ -27,19 +29,8 @@ def reads(B, L, gen):
 
 def timed(fn):
     """(median, min, max) in ms per call over BLOCKS blocks of RUNS calls"""
-    out = []
-    for _ in range(BLOCKS):
-        fn()
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(RUNS):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        out.append(t0.elapsed_time(t1) / RUNS)
-    out.sort()
-    return out[len(out) // 2], out[0], out[-1]
+    t = gputime.timed(fn, calls=RUNS, windows=BLOCKS, warm_each=1)
+    return t.median, t.least, t.greatest
 
 
 gen = torch.Generator(device=dev).manual_seed(0)

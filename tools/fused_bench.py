@@ -7,6 +7,7 @@ import torch
 from wavenet_speech_amd import _lib
 from wavenet_speech_amd import functional as HF
 from wavenet_speech_amd import functional_half as FH
+from gputime import timed
 
 C = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 L = int(sys.argv[2]) if len(sys.argv) > 2 else 4098
@@ -35,17 +36,7 @@ r, sg, z = (FH._hlease(mode, B, C, layout, dev) for _ in range(3))
 def run():
     _lib.check(lib.wn_hblock_forward(ctypes.byref(shape), mode.code, HF._p(packed), HF._p(x), HF._p(r), None, 0, HF._p(sg), HF._p(z),
                                      None, HF._stream()), "fwd")
-for _ in range(20):
-    run()
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-N = 200
-e0.record()
-for _ in range(N):
-    run()
-e1.record()
-e1.synchronize()
-us = e0.elapsed_time(e1) / N * 1e3
+us = timed(run, calls=200, warmup=20).median * 1e3
 mb = B * L * C * 2 * 4 / 1e6
 print("C %d L %d B %d d %d %s fused=%s dbg=%s: %.1f us per block forward  (%.0f MB algorithmic -> %.2f TB/s)" % (
     C, L, B, d, prec, os.environ.get("WN_FUSED_FWD", "1"), os.environ.get("WN_FUSED_DBG", "0"), us, mb, mb / us * 1e-6 * 1e6 / 1e6))

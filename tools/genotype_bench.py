@@ -21,7 +21,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pileup_bench import gpu_ms, make_reads  # noqa: E402
+from gputime import Report, timed  # noqa: E402
+from pileup_bench import make_reads  # noqa: E402
 
 
 def main():
@@ -81,6 +82,7 @@ def main():
     ev = W.pileup_evidence(aln, lo, ref_len, strand, query, query_len, R, weights, qual=qual, min_qual=7)
     calls = W.call_genotypes(pile, ev, reference, weights)
     columns = int(ops_len.sum())
+    rep = Report()
     lines = ["# genotype: %d reads of %d..%d op columns (rows of %d; queries of at most %d) on a reference of %d, both strands, quals 0..40, %s"
              % (B, int(ops_len.min()), int(ops_len.max()), width, M, R, torch.cuda.get_device_name(0)),
              "# %d op columns, %d evidence cells added into (3 atomics each); mean depth %.2f; %d positions with a variant flag, %d heterozygous"
@@ -88,7 +90,7 @@ def main():
                 int((calls.flags & 32 != 0).sum())),
              "%-44s %10s %10s %10s %6s" % ("stage", "median ms", "least", "greatest", "reps")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     times = {}
     for name, fn in (("pileup (wn_pileup, no qual)", pile_kernel),
                      ("evidence (wn_pileup_evidence, no qual)", evidence_kernel),
@@ -101,24 +103,18 @@ def main():
                      ("call_consensus (python, 3 launches)", lambda: W.call_consensus(pile, reference)),
                      ("call_genotypes (python, 1 launch)", lambda: W.call_genotypes(pile, ev, reference, weights)),
                      ("call_genotypes (python, with costs)", lambda: W.call_genotypes(pile, ev, reference, weights, return_costs=True))):
-        (med, least, most), reps = gpu_ms(fn, a.reps, a.warmup, a.min_seconds, a.repeats)
-        times[name] = med
-        s = "%-44s %10.4f %10.4f %10.4f %6d" % (name, med, least, most, reps)
-        print(s, flush=True)
-        lines.append(s)
-    s = "evidence / pileup: %.2fx without qual, %.2fx with; evidence: %.3g op columns/s; call_genotypes / call_consensus: %.2fx, %.3g positions/s" % (
+        t = timed(fn, calls=a.reps, windows=a.repeats, warmup=a.warmup, min_seconds=a.min_seconds)
+        times[name] = t.median
+        rep.emit("%-44s %10.4f %10.4f %10.4f %6d" % (name, t.median, t.least, t.greatest, t.calls))
+    rep.emit("evidence / pileup: %.2fx without qual, %.2fx with; evidence: %.3g op columns/s; call_genotypes / call_consensus: %.2fx, %.3g positions/s" % (
         times["evidence (wn_pileup_evidence, no qual)"] / times["pileup (wn_pileup, no qual)"],
         times["evidence (wn_pileup_evidence, qual)"] / times["pileup (wn_pileup, qual)"],
         columns / (1e-3 * times["evidence (wn_pileup_evidence, qual)"]),
         times["call_genotypes (python, 1 launch)"] / times["call_consensus (python, 3 launches)"],
-        R / (1e-3 * times["call_genotypes (python, 1 launch)"]))
-    print(s, flush=True)
-    lines.append(s)
+        R / (1e-3 * times["call_genotypes (python, 1 launch)"])))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

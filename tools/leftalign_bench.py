@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pileup_bench import gpu_ms, make_reads  # noqa: E402
+from gputime import Report, timed  # noqa: E402
+from pileup_bench import make_reads  # noqa: E402
 
 
 def make_labels(rng, ops, share):
@@ -111,6 +112,7 @@ def main():
     assert torch.equal(la.alignment.ops, out) and torch.equal(la.passes, passes)
     interior = (ops >= 3)
     runs = int((interior & ~torch.cat([torch.zeros(B, 1, dtype=torch.bool, device=dev), ops[:, 1:] == ops[:, :-1]], 1)).sum())
+    rep = Report()
     lines = ["# left_align: %d reads of %d..%d op columns (rows of %d), windows of at most %d and reads of at most %d labels, both strands, "
              "max_passes %d, %s" % (B, int(ops_len.min()), int(ops_len.max()), width, N, M, a.max_passes, torch.cuda.get_device_name(0)),
              "# %d op columns, %d gap runs, a homopolymer asked for around %.0f %% of them; %d rows changed, passes per row mean %.2f "
@@ -119,26 +121,20 @@ def main():
                                                                 int((out != ops).sum())),
              "%-34s %10s %10s %10s %6s" % ("stage", "median ms", "least", "greatest", "reps")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     times = {}
     for name, fn in (("left_align (wn_gap_left_align)", kernel),
                      ("left_align (python)", lambda: W.left_align(aln, ref, ref_len, query, query_len, strand, max_passes=a.max_passes)),
                      ("pileup (wn_pileup)", pileup_kernel)):
-        (med, least, most), reps = gpu_ms(fn, a.reps, a.warmup, a.min_seconds, a.repeats)
-        times[name] = med
-        s = "%-34s %10.4f %10.4f %10.4f %6d" % (name, med, least, most, reps)
-        print(s, flush=True)
-        lines.append(s)
+        t = timed(fn, calls=a.reps, windows=a.repeats, warmup=a.warmup, min_seconds=a.min_seconds)
+        times[name] = t.median
+        rep.emit("%-34s %10.4f %10.4f %10.4f %6d" % (name, t.median, t.least, t.greatest, t.calls))
     t = times["left_align (wn_gap_left_align)"] * 1e-3
-    s = "left_align: %.3g op columns/s, %.3g reads/s; %.2fx the time of wn_pileup on the same strings" % (
-        int(ops_len.sum()) / t, B / t, times["left_align (wn_gap_left_align)"] / times["pileup (wn_pileup)"])
-    print(s, flush=True)
-    lines.append(s)
+    rep.emit("left_align: %.3g op columns/s, %.3g reads/s; %.2fx the time of wn_pileup on the same strings" % (
+        int(ops_len.sum()) / t, B / t, times["left_align (wn_gap_left_align)"] / times["pileup (wn_pileup)"]))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

@@ -4,14 +4,11 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn.functional as F
 from wavenet_speech_amd import functional as HF
+from gputime import timed
 B, C, L = 16, 256, 16000
 dev = "cuda:0"
 pred = torch.randn(B, C, L, device=dev, requires_grad=True); tg = torch.randint(0, C, (B, L), device=dev)
-def timeit(fn, n=20):
-    for _ in range(3): fn()
-    torch.cuda.synchronize(); e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True); e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize(); return e0.elapsed_time(e1) / n
+def timeit(fn, n=20): return timed(fn, calls=n, warmup=3).median
 def hip_f(): return HF.sequence_nll(pred, tg)
 def hip_fb(): pred.grad = None; HF.sequence_nll(pred, tg).backward()
 def th_f(): return F.cross_entropy(pred, tg, reduction="sum") / B

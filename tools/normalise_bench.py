@@ -20,21 +20,12 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from wavenet_speech_amd import normalise as N  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def event_ms(fn, reps, warmup):
     """device time of every one of `reps` calls"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
-    return min(times), sorted(times)[len(times) // 2], max(times)
+    return timed(fn, windows=reps, warmup=warmup)[:3]
 
 
 def sort_med_mad(signal, lengths):
@@ -61,12 +52,8 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "normalise_bench.py measures the GPU; there is no CPU path"
     dev = torch.device("cuda:0")
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    rep = Report()
+    emit = rep.emit
     g = torch.Generator().manual_seed(1)                              # the reads of tools/basecall_bench.py
     lengths48 = torch.randint(20000, 120001, (48,), generator=g)
     concentrated = torch.randint(300, 700, (48, int(lengths48.max())), generator=g).to(torch.int16)
@@ -99,9 +86,7 @@ def main():
         emit("  torch.sort based ms min / median / max = %.3f / %.3f / %.3f; %.1f x read_med_mad (median); results equal: %s"
              % (base + (base[1] / ours[1], same)))
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

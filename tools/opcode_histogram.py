@@ -1,23 +1,24 @@
 #!/usr/bin/env python3
-"""Per-kernel, per-opcode instruction counts of csrc files (hipcc --cuda-device-only -S for gfx950): the mnemonic alone, no
+"""Per-kernel, per-opcode instruction counts of csrc files (the device listing of tools/listing.py): the mnemonic alone, no
 registers, no order.  Two trees compare with `diff` of the two outputs; a refactor that leaves the code alone leaves them equal.
+The listing is made with the flags of this tree's csrc/Makefile, the per-file ones included, so the counts are of the product's
+code.  Before the flags moved there this tool left the per-file flags out: its counts of wn_half.hip, wn_fused.hip and the four
+wn_col*.hip files differ from those of earlier versions; every other file's are the same.
 
     tools/opcode_histogram.py [--csrc DIR] wn_pileup.hip ...      one line per kernel and opcode: file kernel opcode count
     tools/opcode_histogram.py --totals ...                        one line per kernel: file kernel instructions"""
-import argparse, collections, os, re, subprocess, sys, tempfile
+import argparse, collections, re, subprocess
 
-root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import listing
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--csrc", default=os.path.join(root, "wavenet_speech_amd", "csrc"))
+ap.add_argument("--csrc", default=listing.CSRC)
 ap.add_argument("--totals", action="store_true")
 ap.add_argument("files", nargs="+")
 args = ap.parse_args()
-tmp = tempfile.mkdtemp(prefix="wn_ops_")
 for f in args.files:
-    out = os.path.join(tmp, f + ".s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                    os.path.join(args.csrc, f), "-o", out], check=True)
-    kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(out).read(), re.M))
+    out = listing.listing(f, args.csrc)
+    kernels = {k for k, _ in listing.kernels(open(out).read())}
     cur, hist = None, collections.defaultdict(collections.Counter)
     for line in open(out):
         m = re.match(r"^(\w+):", line)

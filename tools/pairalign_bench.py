@@ -20,18 +20,11 @@ import torch  # noqa: E402
 from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import decoding as D  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(reps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / reps
+    return timed(fn, calls=reps, warmup=warmup).median
 
 
 def mutate(rng, ref, rate):
@@ -73,12 +66,13 @@ def main():
     assert torch.cuda.is_available(), "pairalign_bench.py measures the GPU; there is no CPU path"
     lib = _lib.load()
     shapes = [(8, 400)] if a.quick else [(8, 400), (32, 400), (1, 8192)]
+    rep = Report()
     lines = ["# pairwise alignment, needle's costs, free end gaps, int32 labels, %s; reps=%d warmup=%d"
              % (torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%4s %6s %6s %14s %18s %13s %12s %8s %15s" % ("B", "N", "M", "align ms/batch", "score-only ms/batch", "cells/us full",
                                                          "mean identity", "ws MB", "cpu-ref ms/pair")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for B, n in shapes:
         ref, rl, query, ql, refs, queries = make_pairs(B, n, 1000 * B + n)
         ms_full = gpu_ms(lambda: D.pairwise_align(ref, rl, query, ql), a.reps, a.warmup)
@@ -93,11 +87,9 @@ def main():
             want = R.align(refs[0], queries[0])
             cpu = "%.0f" % ((time.perf_counter() - t) * 1e3)
             assert want.score == int(float(out.score[0]) * 2) and want.length == int(out.length[0])
-        s = "%4d %6d %6d %14.3f %18.3f %13.1f %12.3f %8.1f %15s" % (
+        rep.emit("%4d %6d %6d %14.3f %18.3f %13.1f %12.3f %8.1f %15s" % (
             B, n, n, ms_full, ms_score, cells / (ms_full * 1e3), float(out.identity.mean()),
-            lib.wn_pair_align_workspace_bytes(B, n, n) / 2**20, cpu)
-        print(s, flush=True)
-        lines.append(s)
+            lib.wn_pair_align_workspace_bytes(B, n, n) / 2**20, cpu))
     if not a.quick:
         B, C, T, W = 32, 5, 4096, 8
         g = torch.Generator().manual_seed(7)
@@ -106,15 +98,12 @@ def main():
         labels, lengths, _, _ = D.ctc_beam_decode(x, W)
         best, n_best = labels[:, 0], lengths[:, 0]                   # the decoder's output, aligned in place against another beam
         ms_reads = gpu_ms(lambda: D.pairwise_align(labels[:, 1], lengths[:, 1], best, n_best), a.reps, a.warmup)
-        s = ("# beam decode W=%d of B=%d, T=%d random logits: %.3f ms/batch; aligning its best beam (mean %.0f labels, rows of %d) "
-             "against its second: %.3f ms/batch" % (W, B, T, ms_beam, float(n_best.float().mean()), T, ms_reads))
-        print(s, flush=True)
-        lines.append(s)
-    D._flags.check_device_flags()
+        rep.emit("# beam decode W=%d of B=%d, T=%d random logits: %.3f ms/batch; aligning its best beam (mean %.0f labels, rows of %d) "
+                 "against its second: %.3f ms/batch" % (W, B, T, ms_beam, float(n_best.float().mean()), T, ms_reads))
+    from wavenet_speech_amd import check_device_flags
+    check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

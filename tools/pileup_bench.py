@@ -23,6 +23,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 
 def make_reads(rng, count, reference, lo=1600, hi=2400):
     """(ops [count, width] uint8, ops_len, window lo, ref_lengths, strand, query [count, M] int32, query_lengths)"""
@@ -86,28 +88,6 @@ def torch_pileup(ops, ops_len, lo, ref_len, strand, query, query_len, R, max_ins
     return counts.view(R, 2, 6), ins_lengths.view(R, max_ins + 1), ins_bases.view(R, max_ins, 4)
 
 
-def gpu_ms(fn, reps, warmup, min_seconds, repeats):
-    """(median, least, greatest) ms per call over `repeats` windows, and the reps of a window"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    windows = []
-    while len(windows) < repeats:
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(reps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms = t0.elapsed_time(t1)
-        if ms < 1e3 * min_seconds and reps < 4096 and not windows:
-            reps *= 4
-            continue
-        windows.append(ms / reps)
-    windows.sort()
-    return (windows[len(windows) // 2], windows[0], windows[-1]), reps
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=4096)
@@ -150,44 +130,37 @@ def main():
     assert torch.equal(pile.counts, counts) and torch.equal(pile.ins_lengths, ins_lengths) and torch.equal(pile.ins_bases, ins_bases)
     columns, adds = int(ops_len.sum()), int(counts.sum()) + int(ins_lengths.sum()) + int(ins_bases.sum())
     calls = W.call_consensus(pile, reference)
+    rep = Report()
     lines = ["# pileup: %d reads of %d..%d op columns (rows of %d; queries of at most %d) on a reference of %d, max_ins %d, both strands, %s"
              % (B, int(ops_len.min()), int(ops_len.max()), width, M, R, max_ins, torch.cuda.get_device_name(0)),
              "# %d op columns, %d atomic adds; mean depth over the reference %.2f; consensus of %d labels, %d positions called"
              % (columns, adds, float(pile.depth.double().mean()), int(calls.consensus.shape[0]), int((calls.flags & 28 != 0).sum())),
              "%-34s %10s %10s %10s %6s" % ("stage", "median ms", "least", "greatest", "reps")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     times = {}
     for name, fn in (("pileup (wn_pileup)", kernel),
                      ("pileup (python, fresh tables)", lambda: W.pileup(aln, lo, ref_len, strand, query, query_len, R, max_ins=max_ins)),
                      ("pileup (python, into=)", lambda: W.pileup(aln, lo, ref_len, strand, query, query_len, R, max_ins=max_ins, into=pile)),
                      ("call_consensus (python, 3 launches)", lambda: W.call_consensus(pile, reference))):
-        (med, least, most), reps = gpu_ms(fn, a.reps, a.warmup, a.min_seconds, a.repeats)
-        times[name] = med
-        s = "%-34s %10.4f %10.4f %10.4f %6d" % (name, med, least, most, reps)
-        print(s, flush=True)
-        lines.append(s)
+        t = timed(fn, calls=a.reps, windows=a.repeats, warmup=a.warmup, min_seconds=a.min_seconds)
+        times[name] = t.median
+        rep.emit("%-34s %10.4f %10.4f %10.4f %6d" % (name, t.median, t.least, t.greatest, t.calls))
     t = times["pileup (wn_pileup)"] * 1e-3
-    s = "pileup: %.3g op columns/s, %.3g reads/s; call_consensus: %.3g positions/s" % (
-        columns / t, B / t, R / (1e-3 * times["call_consensus (python, 3 launches)"]))
-    print(s, flush=True)
-    lines.append(s)
+    rep.emit("pileup: %.3g op columns/s, %.3g reads/s; call_consensus: %.3g positions/s" % (
+        columns / t, B / t, R / (1e-3 * times["call_consensus (python, 3 launches)"])))
     if not a.no_torch:
         fresh = W.pileup(aln, lo, ref_len, strand, query, query_len, R, max_ins=max_ins)
         tc, tl, tb = torch_pileup(ops, ops_len, lo, ref_len, strand, query, query_len, R, max_ins)
         assert torch.equal(tc, fresh.counts) and torch.equal(tl, fresh.ins_lengths) and torch.equal(tb, fresh.ins_bases), \
             "the comparator's tables differ from the kernel's"
-        (med, least, most), reps = gpu_ms(lambda: torch_pileup(ops, ops_len, lo, ref_len, strand, query, query_len, R, max_ins), 2, 1, 0.0,
-                                          min(a.repeats, 3))
-        s = "%-34s %10.4f %10.4f %10.4f %6d   (%.1fx pileup (python, fresh tables))" % ("torch-op pileup (fresh tables)", med, least, most, reps,
-                                                                                        med / times["pileup (python, fresh tables)"])
-        print(s, flush=True)
-        lines.append(s)
+        t = timed(lambda: torch_pileup(ops, ops_len, lo, ref_len, strand, query, query_len, R, max_ins), calls=2, windows=min(a.repeats, 3),
+                  warmup=1)
+        rep.emit("%-34s %10.4f %10.4f %10.4f %6d   (%.1fx pileup (python, fresh tables))" % (
+            "torch-op pileup (fresh tables)", t.median, t.least, t.greatest, t.calls, t.median / times["pileup (python, fresh tables)"]))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

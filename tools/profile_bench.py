@@ -10,7 +10,6 @@ Writes its table to --out, by default profiles/rNN/profile_bench.txt in the next
 Usage: profile_bench.py [--reps N] [--warmup N] [--quick] [--out FILE]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,22 +18,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from wavenet_speech_amd import decoding as D  # noqa: E402
 
+from gputime import Report, next_profile_dir, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
     """(min, median, max) ms of one call"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
-    times.sort()
-    return times[0], times[len(times) // 2], times[-1]
+    return timed(fn, windows=reps, warmup=warmup)[:3]
 
 
 def pairs(seed, B, n_lo, n_hi, width, rate=0.06, unrelated=False):
@@ -62,12 +51,6 @@ def pairs(seed, B, n_lo, n_hi, width, rate=0.06, unrelated=False):
     return truth, tn, calls, cn
 
 
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -81,11 +64,12 @@ def main():
             ("1 x 8192 mutated", 1, 7600, 7600, 8192, False, False), ("1 x 8192 16384 col", 1, 8192, 8192, 8192, True, True)]
     if a.quick:
         work = work[:1]
+    rep = Report()
     lines = ["# quality profile next to the pairwise alignment that made its ops, classes=5, qual and dwell given, %s; reps=%d "
              "warmup=%d; ms per call: min / median / max" % (torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%-19s %8s %26s %26s %7s" % ("pairs", "columns", "pairwise_align ms", "quality_profile ms", "ratio")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for n, (name, B, lo, hi, width, unrelated, count_ends) in enumerate(work):
         truth, tn, calls, cn = (torch.from_numpy(v).to(dev) for v in pairs(1000 + n, B, lo, hi, width, unrelated=unrelated))
         g = torch.Generator().manual_seed(n)
@@ -98,15 +82,12 @@ def main():
         t_pr = gpu_ms(lambda: D.quality_profile(al, truth, tn, calls, cn, qual=qual, dwell=dwell, count_ends=count_ends), a.reps, a.warmup)
         line = "%-19s %8d %26s %26s %7.3f" % (name, int(al.ops_len.sum()), "%.3f / %.3f / %.3f" % t_al, "%.3f / %.3f / %.3f" % t_pr,
                                               t_pr[1] / t_al[1])
-        print(line, flush=True)
-        lines.append(line)
+        rep.emit(line)
     torch.cuda.synchronize()
     from wavenet_speech_amd import check_device_flags
     check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "profile_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

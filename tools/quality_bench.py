@@ -8,7 +8,6 @@ Writes its table to --out, by default profiles/rNN/quality_bench.txt in the next
 Usage: quality_bench.py [--reps N] [--warmup N] [--quick] [--out FILE]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,22 +16,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from wavenet_speech_amd import decoding as D  # noqa: E402
 
+from gputime import Report, next_profile_dir, timed  # noqa: E402
+
 
 def gpu_ms(fn, reps, warmup):
     """(min, median, max) ms of one call"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
-    times.sort()
-    return times[0], times[len(times) // 2], times[-1]
+    return timed(fn, windows=reps, warmup=warmup)[:3]
 
 
 def peaked_logits(seed, B, C, T, margin=6.0):
@@ -47,12 +36,6 @@ def peaked_logits(seed, B, C, T, margin=6.0):
     return torch.from_numpy(x)
 
 
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -63,11 +46,12 @@ def main():
     assert torch.cuda.is_available(), "quality_bench.py measures the GPU; there is no CPU path"
     C = 5
     Bs, Ts = ([8], [4096]) if a.quick else ([8, 32], [4096, 100000])
+    rep = Report()
     lines = ["# per-base qualities next to the greedy decode of the same logits, C=%d, fp32 [B][C][T], %s; reps=%d warmup=%d; "
              "ms per call: min / median / max" % (C, torch.cuda.get_device_name(0), a.reps, a.warmup),
              "%4s %7s %9s %26s %26s %7s" % ("B", "T", "bases", "greedy decode ms", "base qualities ms", "ratio")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for B in Bs:
         for T in Ts:
             x = peaked_logits(B * 1000003 + T, B, C, T).to("cuda:0")
@@ -76,15 +60,12 @@ def main():
             q = gpu_ms(lambda: D.ctc_base_qualities(x, labels, lengths, frames), a.reps, a.warmup)
             line = "%4d %7d %9d %26s %26s %7.2f" % (B, T, int(lengths.sum()), "%.3f / %.3f / %.3f" % g, "%.3f / %.3f / %.3f" % q,
                                                     q[1] / g[1])
-            print(line, flush=True)
-            lines.append(line)
+            rep.emit(line)
     torch.cuda.synchronize()
     from wavenet_speech_amd import check_device_flags
     check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "quality_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

@@ -25,6 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from gputime import Report, timed  # noqa: E402
+
 DEFAULTS = dict(h=64, max_dist=5000, bandwidth=500, gap_base=2, gap_log=8)
 
 
@@ -91,28 +93,6 @@ def pairs_evaluated(keys, n_anchors, h):
     return total
 
 
-def gpu_ms(fn, reps, warmup, min_seconds, repeats):
-    """(median, least, greatest) ms per call over `repeats` windows, and the reps of a window"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    windows = []
-    while len(windows) < repeats:
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(reps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms = t0.elapsed_time(t1)
-        if ms < 1e3 * min_seconds and reps < 4096 and not windows:
-            reps *= 4
-            continue
-        windows.append(ms / reps)
-    windows.sort()
-    return (windows[len(windows) // 2], windows[0], windows[-1]), reps
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=4096)
@@ -177,6 +157,7 @@ def main():
     assert torch.equal(torch.stack(list(whole[:8]), 1), result) and torch.equal(whole.f, f) and torch.equal(whole.pred, pred)
     assert torch.equal(whole.anchors.keys, keys) and torch.equal(torch.sort(keys, dim=1).values, keys)          # the rows come sorted
     mapped = int(whole.mapped.sum())
+    rep = Report()
     lines = ["# read mapping: %d reads of 400..1200 labels (8 %% errors, both strands; rows of %d) against %d bases, k %d w %d max_occ %d h %d, "
              "%d anchors per read at most, %s" % (B, L, a.reference, k, w, max_occ, c["h"], cap, torch.cuda.get_device_name(0)),
              "# index: %d entries, built in %.1f ms (first call %.1f ms); reads: %d minimizers, %d anchors (%.1f per read, %d reads truncated), "
@@ -184,33 +165,25 @@ def main():
                                                         int(truncated.sum()), pairs, mapped),
              "%-28s %10s %10s %10s %6s" % ("stage", "median ms", "least", "greatest", "reps")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     times = {}
     for name, fn in (("sketch (wn_minimizers)", sketch), ("seeds, sorted (wn_read_seeds)", seeds), ("chain (wn_chain)", chain),
                      ("chain with f and pred", lambda: chain(True)), ("map_reads (python, all three)", lambda: W.map_reads(labels, lengths, index))):
-        (med, lo, hi), reps = gpu_ms(fn, a.reps, a.warmup, a.min_seconds, a.repeats)
-        times[name] = med
-        s = "%-28s %10.4f %10.4f %10.4f %6d" % (name, med, lo, hi, reps)
-        print(s, flush=True)
-        lines.append(s)
+        t = timed(fn, calls=a.reps, windows=a.repeats, warmup=a.warmup, min_seconds=a.min_seconds)
+        times[name] = t.median
+        rep.emit("%-28s %10.4f %10.4f %10.4f %6d" % (name, t.median, t.least, t.greatest, t.calls))
     t = times["chain (wn_chain)"] * 1e-3
-    s = "chain: %.3g anchors/s, %.3g predecessor pairs/s; all three stages: %.3g reads/s" % (
-        anchors / t, pairs / t, B / (1e-3 * sum(times[n] for n in list(times)[:3])))
-    print(s, flush=True)
-    lines.append(s)
+    rep.emit("chain: %.3g anchors/s, %.3g predecessor pairs/s; all three stages: %.3g reads/s" % (
+        anchors / t, pairs / t, B / (1e-3 * sum(times[n] for n in list(times)[:3]))))
     if not a.no_torch:
         tf, tp = torch_chain(keys, n_anchors, k, **c)
         assert torch.equal(tf, f) and torch.equal(tp, pred), "the comparator's chain table differs from the kernel's"
-        (med, lo, hi), reps = gpu_ms(lambda: torch_chain(keys, n_anchors, k, **c), 1, 1, 0.0, min(a.repeats, 3))
-        s = "%-28s %10.4f %10.4f %10.4f %6d   (%.0fx the kernel with the table)" % ("torch-op chain DP", med, lo, hi, reps,
-                                                                                   med / times["chain with f and pred"])
-        print(s, flush=True)
-        lines.append(s)
+        t = timed(lambda: torch_chain(keys, n_anchors, k, **c), windows=min(a.repeats, 3), warmup=1)
+        rep.emit("%-28s %10.4f %10.4f %10.4f %6d   (%.0fx the kernel with the table)" % ("torch-op chain DP", t.median, t.least, t.greatest,
+                                                                                        t.calls, t.median / times["chain with f and pred"]))
     W.check_device_flags()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        rep.save(a.out)
 
 
 if __name__ == "__main__":

@@ -15,7 +15,6 @@ Writes its table to --out, by default profiles/rNN/signal_align_bench.txt in the
 Usage: signal_align_bench.py [--reps N] [--warmup N] [--out FILE] [--quick]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,31 +25,15 @@ from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
 from wavenet_speech_amd.functional import _p, _stream  # noqa: E402
 
+from gputime import Report, next_profile_dir, timed  # noqa: E402
+
 FIRST = 2
 DWELL = ("gamma", 4.0, 2000.0, 4000.0)          # mean 8 samples, shape 4
 
 
 def gpu_ms(fn, reps, warmup):
     """(min, median, max) ms of one call"""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
-    times.sort()
-    return times[0], times[len(times) // 2], times[-1]
-
-
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
+    return timed(fn, windows=reps, warmup=warmup)[:3]
 
 
 def time_shape(lib, model, B, bases, band, reps, warmup, dev):
@@ -117,6 +100,7 @@ def main():
     dev = torch.device("cuda:0")
     lib = _lib.load()
     model = W.signal_model(*S.standin_kmer_table())
+    rep = Report()
     lines = ["# signal_align: k=%d, frac_bits=%d, weight_shift=%d, dwell %s, %s; device events around wn_signal_align; reps=%d warmup=%d "
              "(long reads: %d and %d); ms per call: min / median / max" % (model.k, model.frac_bits, model.weight_shift, DWELL,
                                                                           torch.cuda.get_device_name(0), a.reps, a.warmup,
@@ -124,23 +108,19 @@ def main():
              "%5s %8s %6s %10s %10s %8s %30s %10s %8s %10s" % ("reads", "bases", "band", "samples", "k-mers", "ws MiB", "ms", "Msample/s",
                                                              "hit", "true kmer")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     for bases in (2000,) if a.quick else (2000, 16000):
         for B in (32, 256):
             for band in (128, 512):
                 long_read = bases > 4000
                 line = time_shape(lib, model, B, bases, band, max(a.reps // 10, 2) if long_read else a.reps,
                                   max(a.warmup // 3, 1) if long_read else a.warmup, dev)
-                print(line, flush=True)
-                lines.append(line)
+                rep.emit(line)
     for line in training(dev):
-        print(line, flush=True)
-        lines.append(line)
+        rep.emit(line)
     W.check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "signal_align_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

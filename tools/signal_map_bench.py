@@ -14,7 +14,6 @@ Writes its table to --out, by default profiles/rNN/signal_map_bench.txt in the n
 Usage: signal_map_bench.py [--out FILE] [--quick] [--seconds S]"""
 import argparse
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +23,8 @@ import wavenet_speech_amd as W  # noqa: E402
 from wavenet_speech_amd import _lib  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
 from wavenet_speech_amd._args import _p, _stream  # noqa: E402
+
+from gputime import Report, next_profile_dir, timed  # noqa: E402
 
 DWELL = ("gamma", 4.0, 2000.0, 4000.0)          # mean 8 samples, shape 4
 TILE, FULL_CHIP = 1024, 512                     # csrc/wn_sigmap.hip: kSmTile, kSmFullChip
@@ -49,12 +50,6 @@ def halo_share(lengths, M, strip):
             first = max(own0 - up64(T - 1), 0)
             computed += -(-(min(own0 + strip, M) - first) // TILE) * TILE
     return 1.0 - M * len(lengths) / computed
-
-
-def next_profile_dir():
-    base = os.path.join(ROOT, "profiles")
-    taken = [int(m.group(1)) for m in (re.match(r"r(\d+)$", n) for n in (os.listdir(base) if os.path.isdir(base) else [])) if m]
-    return os.path.join(base, "r%02d" % (max(taken, default=0) + 1))
 
 
 def make_reads(reference, B, T, seed, dev):
@@ -86,17 +81,9 @@ def time_shape(lib, reference, B, T, strip, seconds, dev):
                                      model.frac_bits, model.weight_shift, 2 ** 31 - 1, strip, _p(score), _p(end), _p(start), _p(runner),
                                      _p(block_cost), _p(block_end), None, _p(ws), ws_bytes, _p(bad), _stream()), "wn_signal_map")
 
-    def one():
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        abi()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1)
-
-    warm = one()                                                     # the warm-up call
+    warm = timed(abi).median                                         # the warm-up call
     reps = max(2, min(20, int(seconds * 1e3 / max(warm, 1e-3))))
-    times = sorted(one() for _ in range(reps))
+    times = timed(abi, windows=reps).ms
     assert int(bad) == 0
     cells = M * int(lengths.sum())
     used = strip or auto_strip(B, T, M)
@@ -119,25 +106,23 @@ def main():
     lib = _lib.load()
     model = W.signal_model(*S.standin_kmer_table())
     g = torch.Generator().manual_seed(7)
+    rep = Report()
     lines = ["# signal_map: k=%d, frac_bits=%d, weight_shift=%d, dwell %s, both strands, %s; device events around wn_signal_map (both "
              "launches); one warm-up call, then `n` timed calls (about %.1f s per shape); ms per call: min / median / max; Gcell/s = M * "
              "sum T_b / median, halo excluded" % (model.k, model.frac_bits, model.weight_shift, DWELL, torch.cuda.get_device_name(0), a.seconds),
              "%5s %6s %9s %8s %4s %30s %10s %7s %7s %9s" % ("reads", "T", "states", "strip", "n", "ms", "Gcell/s", "halo", "found", "2nd/best")]
     for line in lines:
-        print(line, flush=True)
+        rep.emit(line)
     small = W.map_reference(torch.randint(1, 5, (48502,), generator=g), model, device=dev)
     shapes = [(small, B, T, strip) for B in ((32,) if a.quick else (1, 32, 256)) for T in (512, 2048, 4096) for strip in (0, 2048, 16384)]
     if not a.quick:
         shapes.append((W.map_reference(torch.randint(1, 5, (4600000,), generator=g), model, device=dev), 4, 2048, 0))
     for reference, B, T, strip in shapes:
         line = time_shape(lib, reference, B, T, strip, a.seconds, dev)
-        print(line, flush=True)
-        lines.append(line)
+        rep.emit(line)
     W.check_device_flags()
     out = a.out or os.path.join(next_profile_dir(), "signal_map_bench.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    rep.save(out)
     print("wrote", out)
 
 

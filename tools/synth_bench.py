@@ -12,23 +12,17 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from wavenet_speech_amd import synthetic as S  # noqa: E402
 
+import gputime  # noqa: E402
 
 
 def ragged(out_path):
     """device events; B = 32 reads of about 700 bases, uniform (6, 2) (about cfg2's 4096 samples), and B = 16 at about 16 000"""
-    def timed_ev(fn, n=50, warm=5):
-        for _ in range(warm):
-            fn()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(n):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / n
+    def timed_ev(fn, n=50):
+        return gputime.timed(fn, calls=n, warmup=5).median
 
     dev = "cuda:0"
-    lines = ["ragged generator, uniform dwell (6, 2), loader window; ms per call by device events, host launch overhead included"]
+    rep = gputime.Report()
+    rep.emit("ragged generator, uniform dwell (6, 2), loader window; ms per call by device events, host launch overhead included")
     table = S.standin_kmer_table(device=dev)
     gen = torch.Generator(device=dev).manual_seed(1)
     host_gen = torch.Generator().manual_seed(1)                        # the seed is drawn on the host: no device read
@@ -49,18 +43,16 @@ def ragged(out_path):
         t_fixed = timed_ev(fixed)
         t_torch = timed_ev(lambda: S._torch_reads(B, lo, hi, 2, ("uniform", 6, 2), 7, table, gen, torch.device(dev), pad, None, None, None,
                                                   None), n=20)
-        lines += ["B = %d, %d..%d bases, longest read %d samples, rows of %d" % (B, lo, hi - 1, samples, pad),
-                  "  wn_reads_plan                          : %.3f ms" % t_plan,
-                  "  wn_reads_signal                        : %.3f ms" % t_sig,
-                  "  ragged_reads, pad_to (two launches)    : %.3f ms" % t_both,
-                  "  ragged_reads, one host read of the max : %.3f ms" % t_sync,
-                  "  fixed generator, %d samples, 3 launches (bases, signal, quantize; no one-hot): %.3f ms" % (samples, t_fixed),
-                  "  torch ops on the GPU (randint, cumsum, searchsorted, gather, randn)         : %.3f ms" % t_torch,
-                  "  expectation (plan + signal <= fixed three-launch generator): %s" % ("holds" if t_plan + t_sig <= t_fixed else "DOES NOT HOLD")]
-    text = "\n".join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(out_path), exist_ok=True)
-    open(out_path, "w").write(text + "\n")
+        for line in ("B = %d, %d..%d bases, longest read %d samples, rows of %d" % (B, lo, hi - 1, samples, pad),
+                     "  wn_reads_plan                          : %.3f ms" % t_plan,
+                     "  wn_reads_signal                        : %.3f ms" % t_sig,
+                     "  ragged_reads, pad_to (two launches)    : %.3f ms" % t_both,
+                     "  ragged_reads, one host read of the max : %.3f ms" % t_sync,
+                     "  fixed generator, %d samples, 3 launches (bases, signal, quantize; no one-hot): %.3f ms" % (samples, t_fixed),
+                     "  torch ops on the GPU (randint, cumsum, searchsorted, gather, randn)         : %.3f ms" % t_torch,
+                     "  expectation (plan + signal <= fixed three-launch generator): %s" % ("holds" if t_plan + t_sig <= t_fixed else "DOES NOT HOLD")):
+            rep.emit(line)
+    rep.save(out_path)
 
 
 if "--ragged" in sys.argv:
