@@ -1035,6 +1035,51 @@ int wn_genotype_call(const long long* evidence, const int* counts, const int* in
                      unsigned char* ins_len, unsigned char* ins_out /* with max_ins > 0 */, int* ins_gq, int* ins_qual,
                      long long* costs /* may be NULL */, wn_stream_t stream);
 
+/* ---- Read-backed phasing and haplotags (wavenet_speech_amd/phase.py): what WhatsHap, longshot or HapCUT2 do
+ * after the calls -- the alleles of neighbouring heterozygous sites linked through the reads that span them, and a haplotype tag
+ * per read.  Integer arithmetic only; all pointers are DEVICE pointers.  tests/phase_ref.py holds the same definitions as plain
+ * loops.
+ *   A site s (0 <= s < n_sites) is a heterozygous position: site_of [R] int32 holds the site of a position or -1, alleles
+ *   [n_sites][2] bytes its two called labels (0: deleted), pos [n_sites] int32 its position, ascending.
+ *   An OBSERVATION of a read: a column that wn_pileup_evidence adds for (the same reads, arguments, ops, end columns, orientation,
+ *   complement, min_qual rule, skipped and bad reads as wn_pileup) at a position with site_of >= 0.  It shows the label k (1..4, or 0
+ *   for a deletion column) with the weight q' = min(q, cap[b]), q the base's qual, flat_qual without qual, gap_qual for a deletion;
+ *   x = 0 if k == alleles[s][0], else 1 if k == alleles[s][1], else NEITHER.
+ *   wn_phase_links: observed [n_sites][3] int32 += 1 at [s][x] (column 2: neither); links [n_sites][reach][2] int64: for every pair
+ *   of observations of one read at sites s - d and s, 1 <= d <= reach, neither of them NEITHER, += min(q'(s - d), q'(s)) at
+ *   [s][d - 1][x(s - d) xor x(s)] (0 cis, 1 trans).  Both tables are ADDED INTO (integer atomics), never cleared; two runs are
+ *   bitwise identical.  used [B] and *bad as wn_pileup writes them.  One workgroup per read, two passes over its ops.
+ *   wn_phase_chain: per site, margin_d = |cis - trans| of links[s][d - 1] for d in 1..min(reach, s), d* the greatest (ties to the
+ *   least d).  s == 0 or margin_d* < min_margin: a root, parent[s] = s, flip[s] = 0, margin[s] = 0; else parent[s] = s - d*, flip[s]
+ *   = (trans > cis), margin[s] = min(margin_d*, 2^31 - 1).  root[s]: the root of s's tree; parity[s]: the xor of the flips on the way
+ *   there; ps[s] = pos[root[s]]; set_size[s]: the sites of that tree.  work: 2 * n_sites int32.  3 + ceil(log2 n_sites) launches
+ *   (pointer doubling), nothing is read back.
+ *   wn_haplotag: per read, over its observations with x in {0, 1} at sites with set_size > 1: its set is root[s] of the one with
+ *   the greatest q' (ties to the least s); weight [B][2] int32: the sum of q' of those in that set at [x xor parity[s]]; n_observed
+ *   [B][2] int32: how many lie in that set, and in others; hp [B] bytes: 1 if weight[0] > weight[1], 2 if less, else 0; ps [B] int32:
+ *   pos[root] or -1 without such an observation.  A skipped or bad read: hp 0, ps -1, zeros; bad ones are counted in *bad.
+ * Checked before any launch, in this order.  WN_ERR_BAD_SHAPE: batch, max_query_len, max_ops, reference_len, n_sites or reach < 1, a
+ * negative stride, min_qual, flat_qual, gap_qual or min_margin.  WN_ERR_UNSUPPORTED: batch > 65535, max_query_len > 8192, max_ops >
+ * 65535 + 8192, reference_len > 2^26, min_qual, flat_qual or gap_qual > 93, reach > 8, n_sites > reference_len (wn_phase_chain:
+ * > 2^26).  WN_ERR_NULL: any pointer but qual, keep, cap and bad. */
+int wn_phase_links(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+                   const int* strand, const int* query, long long query_stride, const int* query_lengths,
+                   const unsigned char* qual /* may be NULL */, long long qual_stride,
+                   const unsigned char* keep /* may be NULL */, int batch, int max_query_len, int max_ops, int reference_len,
+                   const unsigned char* cap /* may be NULL */, int flat_qual, int gap_qual, int min_qual, const int* site_of,
+                   const unsigned char* alleles, int n_sites, int reach, long long* links, int* observed, signed char* used,
+                   int* bad /* may be NULL */, wn_stream_t stream);
+int wn_phase_chain(const long long* links, const int* pos, int n_sites, int reach, int min_margin, int* parent,
+                   unsigned char* flip, int* margin, int* root, unsigned char* parity, int* ps, int* set_size, int* work,
+                   wn_stream_t stream);
+int wn_haplotag(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+                const int* strand, const int* query, long long query_stride, const int* query_lengths,
+                const unsigned char* qual /* may be NULL */, long long qual_stride, const unsigned char* keep /* may be NULL */,
+                int batch, int max_query_len, int max_ops, int reference_len, const unsigned char* cap /* may be NULL */,
+                int flat_qual, int gap_qual, int min_qual, const int* site_of, const unsigned char* alleles, int n_sites,
+                const int* pos, const int* root, const unsigned char* parity, const int* set_size, unsigned char* hp, int* ps,
+                int* weight, int* n_observed, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

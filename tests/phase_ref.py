@@ -1,0 +1,173 @@
+"""CPU reference of the phasing sites, observations, links, the chain, the haplotags and the phased records (csrc/wn_phase.hip,
+wavenet_speech_amd/phase.py), as plain loops over Python integers, written from the definitions and not from
+the kernel: every read is walked in READ orientation and its columns are mapped to the forward strand one by one, as
+tests/genotype_ref.py add_read does; which reads are skipped or bad is tests/pileup_ref.py read_state; the forest is resolved by
+following parents, one step at a time.
+
+Labels 1..4 = A, G, C, T, the complement of v is 5 - v; the label of a deletion column and of a deleted allele is 0.  An observation
+is (site, x, weight) with x 0, 1 or NEITHER.  tests/test_phase_ref.py holds this file to hand-worked rows and to the planted run."""
+from collections import namedtuple
+
+import numpy as np
+
+from tests import genotype_ref as G
+from tests import pileup_ref as P
+
+NEITHER = 2
+I32_MAX = 2 ** 31 - 1
+
+Sites = namedtuple("Sites", "pos alleles site_of")
+Links = namedtuple("Links", "links observed used bad")
+Chain = namedtuple("Chain", "parent flip margin root parity ps set_size")
+Tags = namedtuple("Tags", "hp ps weight n_sites used bad")
+
+
+def sites_ref(flags, alleles):
+    """the positions with HET set -> Sites(pos list, alleles list of pairs, site_of list over the reference)"""
+    pos = [p for p in range(len(flags)) if int(flags[p]) & G.HET_FLAG]
+    site_of = [-1] * len(flags)
+    for s, p in enumerate(pos):
+        site_of[p] = s
+    return Sites(pos, [(int(alleles[p][0]), int(alleles[p][1])) for p in pos], site_of)
+
+
+def observations(sites, ops, lo, n_ref, strand, query, qual, min_qual, flat_qual, gap_qual, cap):
+    """the observations of one valid read, sorted by site; None if it has no aligned column"""
+    row = [int(v) for v in ops]
+    aligned = [c for c, v in enumerate(row) if v <= 2]
+    if not aligned:
+        return None
+    first, last = aligned[0], aligned[-1]
+    i = sum(v != 4 for v in row[:first])
+    j = sum(v != 3 for v in row[:first])
+    shown = []                                                       # (forward position, label, weight)
+    for c in range(first, last + 1):
+        op = row[c]
+        pos = lo + n_ref - 1 - i if strand else lo + i
+        if op <= 2:
+            v = int(query[j])
+            q = flat_qual if qual is None else int(qual[j])
+            if 1 <= v <= 4 and not (qual is not None and q < min_qual):
+                shown.append((pos, 5 - v if strand else v, min(q, cap)))
+            i, j = i + 1, j + 1
+        elif op == 3:
+            shown.append((pos, 0, min(gap_qual, cap)))
+            i += 1
+        else:
+            j += 1
+    out = []
+    for pos, label, q in shown:
+        s = sites.site_of[pos]
+        if s >= 0:
+            a0, a1 = sites.alleles[s]
+            out.append((s, 0 if label == a0 else 1 if label == a1 else NEITHER, q))
+    return sorted(out)
+
+
+def read_observations(sites, ops, ops_len, lo, ref_lengths, strand, query, query_lengths, qual=None, flat_qual=20, gap_qual=20, cap=None,
+                      min_qual=0, keep=None):
+    """-> ([the observations of read b, or None if it is skipped, bad or without an aligned column], used [B], bad: the count)"""
+    B = len(ops_len)
+    max_ops = len(ops[0]) if B else 0
+    M = len(query[0]) if B else 0
+    R = len(sites.site_of)
+    out, used, bad = [], [], 0
+    for b in range(B):
+        q = None if qual is None else qual[b]
+        state = P.read_state(ops[b], int(ops_len[b]), max_ops, int(lo[b]), int(ref_lengths[b]), int(strand[b]), int(query_lengths[b]), M, R, q,
+                             True if keep is None else bool(keep[b]))
+        obs = None
+        if state == 1:
+            obs = observations(sites, ops[b][:int(ops_len[b])], int(lo[b]), int(ref_lengths[b]), int(strand[b]), query[b], q, min_qual, flat_qual,
+                               gap_qual, 93 if cap is None else int(cap[b]))
+            state = 0 if obs is None else 1
+        bad += state == -1
+        out.append(obs)
+        used.append(state)
+    return out, np.array(used, dtype=np.int8), bad
+
+
+def links_ref(sites, *reads, reach=4, into=None, **kw):
+    """reads and kw: read_observations' -> Links(links [S][reach][2] and observed [S][3] as nested lists of Python integers, used, bad)"""
+    S = len(sites.pos)
+    links = [[[0, 0] for _ in range(reach)] for _ in range(S)] if into is None else [[list(c) for c in s] for s in into.links]
+    observed = [[0, 0, 0] for _ in range(S)] if into is None else [list(s) for s in into.observed]
+    per_read, used, bad = read_observations(sites, *reads, **kw)
+    for obs in per_read:
+        for n, (s, x, q) in enumerate(obs or []):
+            observed[s][x] += 1
+            for s2, x2, q2 in obs[:n]:
+                if 1 <= s - s2 <= reach and x != NEITHER and x2 != NEITHER:
+                    links[s][s - s2 - 1][x ^ x2] += min(q, q2)
+    return Links(links, observed, used, bad)
+
+
+def chain_ref(links, pos, min_margin=1):
+    """links [S][reach][2] -> Chain of lists; the forest is resolved by walking from every site to its root"""
+    S = len(pos)
+    parent, flip, margin = [], [], []
+    for s in range(S):
+        best = None                                                  # (margin, d)
+        for d in range(1, min(len(links[s]), s) + 1):
+            m = abs(int(links[s][d - 1][0]) - int(links[s][d - 1][1]))
+            if best is None or m > best[0]:
+                best = (m, d)
+        if best is None or best[0] < min_margin:
+            parent.append(s), flip.append(0), margin.append(0)
+        else:
+            parent.append(s - best[1]), flip.append(int(int(links[s][best[1] - 1][1]) > int(links[s][best[1] - 1][0]))), margin.append(min(best[0], I32_MAX))
+    root, parity = [], []
+    for s in range(S):
+        at, x = s, 0
+        while parent[at] != at:
+            x ^= flip[at]
+            at = parent[at]
+        root.append(at), parity.append(x)
+    size = [root.count(r) if r == s else 0 for s, r in enumerate(root)]
+    return Chain(parent, flip, margin, root, parity, [pos[r] for r in root], [size[r] for r in root])
+
+
+def haplotag_ref(sites, chain, *reads, **kw):
+    """-> Tags(hp [B], ps [B], weight [B][2], n_sites [B][2], used, bad)"""
+    per_read, used, bad = read_observations(sites, *reads, **kw)
+    hp, ps, weight, n_sites = [], [], [], []
+    for obs in per_read:
+        counted = [(s, x, q) for s, x, q in obs or [] if x != NEITHER and chain.set_size[s] > 1]
+        if not counted:
+            hp.append(0), ps.append(-1), weight.append([0, 0]), n_sites.append([0, 0])
+            continue
+        best = max(counted, key=lambda o: (o[2], -o[0]))             # the greatest weight, ties to the least site
+        r = chain.root[best[0]]
+        w, n = [0, 0], [0, 0]
+        for s, x, q in counted:
+            if chain.root[s] == r:
+                w[x ^ chain.parity[s]] += q
+                n[0] += 1
+            else:
+                n[1] += 1
+        hp.append(1 if w[0] > w[1] else 2 if w[0] < w[1] else 0), ps.append(sites.pos[r]), weight.append(w), n_sites.append(n)
+    return Tags(hp, ps, weight, n_sites, used, bad)
+
+
+def phased_records_ref(reference, calls, pile, sites, chain):
+    """genotype_ref.records_ref's tuples with a phased gt and a ninth field ps (None: unphased)"""
+    R = len(reference)
+    deleted = lambda p: 0 <= p < R and bool(int(calls.flags[p]) & G.DELETION)                        # noqa: E731
+    hom = lambda p: int(calls.alleles[p][0]) == 0                                                    # noqa: E731
+    run_starts = iter([p for p in range(R) if deleted(p) and not (deleted(p - 1) and hom(p - 1) == hom(p))])
+    out = []
+    for rec in G.records_ref(reference, calls, pile):                # deletion records come in the order of their runs
+        pos, kind, ref, alts, gt = rec[:5]
+        at = pos if kind == "sub" else next(run_starts) if kind == "del" else None
+        s = -1 if at is None else sites.site_of[at]
+        if s < 0 or chain.set_size[s] <= 1:
+            out.append(rec + (None,))
+            continue
+        labels = [sites.alleles[s][chain.parity[s]], sites.alleles[s][1 - chain.parity[s]]]        # on haplotype 1, on haplotype 2
+        if kind == "del":
+            index = [1 if v == 0 else 0 for v in labels]
+        else:
+            listed = [ref] + list(alts)
+            index = [listed.index((v,) if v else ()) for v in labels]
+        out.append(rec[:4] + ("%d|%d" % tuple(index),) + rec[5:] + (chain.ps[s],))
+    return out

@@ -33,6 +33,8 @@ from .pileup import ConsensusCalls, Pileup, Variant, call_consensus, pileup, var
 from .leftalign import LeftAligned, left_align  # noqa: F401
 from .genotype import (Evidence, GenotypeRecord, Genotypes, GenotypeWeights, call_genotypes, genotype_records, genotype_weights,  # noqa: F401
                        pileup_evidence, vcf_genotype_records)
+from .phase import (Haplotags, PhasedRecord, PhaseLinks, PhaseSites, Phasing, haplotag, phase_chain, phase_links, phase_sites,  # noqa: F401
+                    phased_records, vcf_phased_records)
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

@@ -17,7 +17,8 @@ from the one, the weights from the other, and nothing can check that they belong
 Everything the kernels add or compare is an integer, so results equal the host reference of tests/genotype_ref.py exactly and two
 runs are bitwise identical.  Neither function synchronises with the host.  There is no CPU fallback: CPU tensors raise (the host
 helpers genotype_records / vcf_genotype_records take tensors on any device).
-Not built: phasing, realignment against candidate haplotypes, more than one insertion allele per site, strand bias, a gap_qual
+Read-backed phasing of the heterozygous calls and a haplotype tag per read are phase.py's.
+Not built: realignment against candidate haplotypes, more than one insertion allele per site, strand bias, a gap_qual
 derived from quality_profile.
 """
 import ctypes
@@ -198,7 +199,12 @@ def genotype_records(reference, genotypes, pileup):
     alleles deleted, or one) is one record -- a change of zygosity starts another -- anchored as variant_records anchors it, gt 1/1
     or 0/1, with the qual, gq and depth of its first position; a position whose other allele is a substituted base is heterozygous
     in the deletion record too.  An insertion after p is anchored on ref[p]: gt 0/1 or 1/1, qual and gq the insertion's."""
-    what = "genotype_records"
+    return [v for v, _ in _records_with_sites("genotype_records", reference, genotypes, pileup)]
+
+
+def _records_with_sites(what, reference, genotypes, pileup):
+    """genotype_records' list as pairs (record, the position whose call it reports: a substitution's own, the first deleted one of a
+    deletion, an insertion's anchor); phased_records (phase.py) looks the phase up there"""
     if not isinstance(genotypes, Genotypes) or not isinstance(pileup, Pileup):
         raise ValueError("wavenet_speech_amd.%s: genotypes must be Genotypes and pileup a Pileup" % what)
     flags = genotypes.flags
@@ -226,7 +232,7 @@ def genotype_records(reference, genotypes, pileup):
                 alts, gt = alts + ((),), "1/2"
             else:
                 gt = "1/2" if len(alts) == 2 else "1/1" if len(bases) == 2 else "0/1"
-            out.append(GenotypeRecord(p, "sub", (r,), alts, gt, qual, gq, depth))
+            out.append((GenotypeRecord(p, "sub", (r,), alts, gt, qual, gq, depth), p))
         if f & DELETION and starts(q):                               # a run starts here; alleles (0, 0) are the homozygous ones
             e = q
             while e + 1 < len(rows) and rows[e + 1][1] & DELETION and not starts(e + 1):
@@ -234,16 +240,16 @@ def genotype_records(reference, genotypes, pileup):
             gone = tuple(rows[t][2] for t in range(q, e + 1))
             gt = "1/1" if a0 == 0 else "0/1"
             if p > 0:
-                out.append(GenotypeRecord(p - 1, "del", (before,) + gone, ((before,),), gt, qual, gq, depth))
+                out.append((GenotypeRecord(p - 1, "del", (before,) + gone, ((before,),), gt, qual, gq, depth), p))
             elif rows[e][0] + 1 < R:
-                out.append(GenotypeRecord(0, "del", gone + (rows[e][4],), ((rows[e][4],),), gt, qual, gq, depth))
+                out.append((GenotypeRecord(0, "del", gone + (rows[e][4],), ((rows[e][4],),), gt, qual, gq, depth), p))
             else:
-                out.append(GenotypeRecord(0, "del", gone, ((),), gt, qual, gq, depth))
+                out.append((GenotypeRecord(0, "del", gone, ((),), gt, qual, gq, depth), p))
         if f & INSERTION:
-            out.append(GenotypeRecord(p, "ins", (r,), ((r,) + tuple(inserted[q][:n_ins]),), "1/1" if copies == 2 else "0/1", ins_qual, ins_gq,
-                                      depth))
+            out.append((GenotypeRecord(p, "ins", (r,), ((r,) + tuple(inserted[q][:n_ins]),), "1/1" if copies == 2 else "0/1", ins_qual, ins_gq,
+                                       depth), p))
         q += 1
-    out.sort(key=lambda v: (v.pos, ("sub", "del", "ins").index(v.kind)))
+    out.sort(key=lambda v: (v[0].pos, ("sub", "del", "ins").index(v[0].kind)))
     return out
 
 
