@@ -102,6 +102,25 @@ def links_ref(sites, *reads, reach=4, into=None, **kw):
     return Links(links, observed, used, bad)
 
 
+def links_near_ref(sites, *reads, reach=4, into=None, **kw):
+    """links_ref in linear time, for reads too long for its quadratic loop: an observation is compared with the `reach`
+    observations of its read before it only.  From the definition alone: read_observations returns a read's observations sorted by
+    site and a read meets a site at most once, so the sites of the list ascend strictly and the observation `e` entries back lies
+    at least `e` sites back -- a partner 1 <= d <= reach sites back is at most d <= reach entries back.  links_ref stays the
+    definition; tests/test_call_limits_ref.py holds the two equal wherever the quadratic form is affordable."""
+    S = len(sites.pos)
+    links = [[[0, 0] for _ in range(reach)] for _ in range(S)] if into is None else [[list(c) for c in s] for s in into.links]
+    observed = [[0, 0, 0] for _ in range(S)] if into is None else [list(s) for s in into.observed]
+    per_read, used, bad = read_observations(sites, *reads, **kw)
+    for obs in per_read:
+        for n, (s, x, q) in enumerate(obs or []):
+            observed[s][x] += 1
+            for s2, x2, q2 in obs[max(0, n - reach):n]:
+                if 1 <= s - s2 <= reach and x != NEITHER and x2 != NEITHER:
+                    links[s][s - s2 - 1][x ^ x2] += min(q, q2)
+    return Links(links, observed, used, bad)
+
+
 def chain_ref(links, pos, min_margin=1):
     """links [S][reach][2] -> Chain of lists; the forest is resolved by walking from every site to its root"""
     S = len(pos)
