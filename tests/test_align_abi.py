@@ -1,25 +1,21 @@
-"""CPU: the C ABI of CTC forced alignment (csrc/wn_align.hip): exported symbols, workspace sizes, and the shape / limit /
-pointer checks, which run on the host before any HIP call -- none of the calls below touches a device."""
+"""CPU: the C ABI of CTC forced alignment (csrc/wn_align.hip): exported symbols, the ctypes rows against the header, workspace
+sizes, and the shape / limit / pointer checks, which run on the host before any HIP call -- none of the calls below touches a
+device."""
 import ctypes
 
-import pytest
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE
-
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+ALIGN = Entry("wn_ctc_align", dict(x=FAKE, sb=lambda a: a["classes"] * a["length"], sc=lambda a: a["length"], st=1, input_kind=0, labels=FAKE,
+                                   label_lengths=FAKE, input_lengths=None, batch=2, classes=5, length=10, max_label_len=4, blank=0, states=FAKE,
+                                   frame_labels=None, spans=None, score=FAKE, workspace=FAKE, workspace_bytes=1 << 30, bad=None, stream=None))
+SIZE = Entry("wn_ctc_align_workspace_bytes", dict(batch=2, classes=5, length=10, max_label_len=4))
 
 
 def test_align_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_ctc_align_workspace_bytes", "wn_ctc_align"):
-        assert name in _lib.SIGNATURES
-        assert hasattr(lib, name)
-    assert lib.wn_version() == 300
+    for entry in (ALIGN, SIZE):                                      # 21 and 4 arguments
+        entry.check_exported(lib)
+        entry.check_declared()
 
 
 def test_workspace_bytes(lib):
@@ -36,33 +32,18 @@ def test_workspace_bytes(lib):
         assert lib.wn_ctc_align_workspace_bytes(B, C, T, L) == 0, (B, C, T, L)
 
 
-def _align(lib, B=2, C=5, T=10, L=4, kind=0, blank=0, x=FAKE, labels=FAKE, label_len=FAKE, states=FAKE, score=FAKE, ws=FAKE,
-           ws_bytes=1 << 30):
-    return lib.wn_ctc_align(x, C * T, T, 1, kind, labels, label_len, None, B, C, T, L, blank, states, None, None, score, ws,
-                            ws_bytes, None, None)
-
-
 def test_align_rejects_on_the_host(lib):
-    assert _align(lib, C=65) == WN_ERR_UNSUPPORTED
-    assert _align(lib, L=2048) == WN_ERR_UNSUPPORTED
-    assert _align(lib, T=(1 << 24) + 1) == WN_ERR_UNSUPPORTED
-    assert _align(lib, B=65536) == WN_ERR_UNSUPPORTED
-    assert _align(lib, B=0) == WN_ERR_BAD_SHAPE
-    assert _align(lib, C=1) == WN_ERR_BAD_SHAPE
-    assert _align(lib, T=0) == WN_ERR_BAD_SHAPE
-    assert _align(lib, L=0) == WN_ERR_BAD_SHAPE
-    assert _align(lib, kind=3) == WN_ERR_BAD_SHAPE
-    assert _align(lib, kind=-1) == WN_ERR_BAD_SHAPE
-    assert _align(lib, blank=5) == WN_ERR_BAD_SHAPE
-    assert _align(lib, blank=-1) == WN_ERR_BAD_SHAPE
-    for name in ("x", "labels", "label_len", "states", "score", "ws"):
-        assert _align(lib, **{name: None}) == WN_ERR_NULL, name
-    need = lib.wn_ctc_align_workspace_bytes(2, 5, 10, 4)
+    ALIGN.rejects(lib, "x",
+                  shape=(dict(batch=0), dict(classes=1), dict(length=0), dict(max_label_len=0), dict(input_kind=3), dict(input_kind=-1),
+                         dict(blank=5), dict(blank=-1)),
+                  unsupported=(dict(classes=65), dict(max_label_len=2048), dict(length=(1 << 24) + 1), dict(batch=65536)),
+                  required=("x", "labels", "label_lengths", "states", "score", "workspace"))
+    need = SIZE(lib)
     assert need > 0
-    assert _align(lib, ws_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _align(lib, ws_bytes=0) == WN_ERR_WORKSPACE
-    assert _align(lib, ws=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE      # not 16-byte aligned
+    assert ALIGN(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, workspace=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE      # not 16-byte aligned
     # the order of the checks: shape, then unsupported, then NULL, then workspace
-    assert _align(lib, B=0, C=65, x=None) == WN_ERR_BAD_SHAPE
-    assert _align(lib, C=65, x=None, ws_bytes=0) == WN_ERR_UNSUPPORTED
-    assert _align(lib, x=None, ws_bytes=0) == WN_ERR_NULL
+    assert ALIGN(lib, batch=0, classes=65, x=None) == WN_ERR_BAD_SHAPE
+    assert ALIGN(lib, classes=65, x=None, workspace_bytes=0) == WN_ERR_UNSUPPORTED
+    assert ALIGN(lib, x=None, workspace_bytes=0) == WN_ERR_NULL

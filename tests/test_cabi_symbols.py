@@ -1,24 +1,14 @@
 """CPU: libwavenet_amd.so loads without a GPU and exports every symbol include/wavenet_amd.h declares
 (no compute calls here -- those need a GPU)."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "wavenet_amd.h")
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    names = re.findall(r"\b(wn_[a-z0-9_]+)\s*\(", src)
-    return sorted(set(n for n in names))
+from tests.abi_util import check_row, declared_functions
 
 
 def test_header_declares_the_expected_surface():
-    names = _declared_functions()
+    names = declared_functions()
     for must in ("wn_block_pack", "wn_block_forward", "wn_block_backward_data", "wn_block_backward_weights",
                  "wn_conv_forward", "wn_series_layout", "wn_strerror", "wn_version"):
         assert must in names
@@ -27,15 +17,14 @@ def test_header_declares_the_expected_surface():
 def test_library_exports_every_declared_symbol():
     from wavenet_speech_amd import _lib
     lib = _lib.load()
-    for name in _declared_functions():
+    for name in declared_functions():
         assert hasattr(lib, name), "libwavenet_amd.so does not export %s" % name
     # and the ctypes table covers the header one-to-one
-    assert sorted(_lib.SIGNATURES) == _declared_functions()
+    assert sorted(_lib.SIGNATURES) == declared_functions()
 
 
 def test_every_signature_row_matches_the_header():
     """result type, argument count and every argument type of all of _lib.SIGNATURES, by the rule of tests/abi_util.py"""
-    from tests.abi_util import check_row
     from wavenet_speech_amd import _lib
     assert len(_lib.SIGNATURES) >= 106
     for name in _lib.SIGNATURES:

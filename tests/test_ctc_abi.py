@@ -1,28 +1,23 @@
-"""CPU: the C ABI of the CTC loss (csrc/wn_ctc.hip): exported symbols, the workspace size, and the shape / limit / pointer /
-workspace checks, which run on the host before any HIP call -- none of the calls below touches a device."""
+"""CPU: the C ABI of the CTC loss (csrc/wn_ctc.hip): exported symbols, the ctypes rows against the header, the workspace size, and
+the shape / limit / pointer / workspace checks, which run on the host before any HIP call -- none of the calls below touches a
+device."""
 import ctypes
 import os
 import re
 
-import pytest
-
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE
+from tests.abi_util import FAKE, ROOT, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
 MAX_CLASSES, MAX_LABELS, MAX_BATCH = 64, 2047, 65535
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+LOSS = Entry("wn_ctc_loss", dict(logits=FAKE, labels=FAKE, label_lengths=FAKE, input_lengths=None, batch=2, classes=5, length=10, max_label_len=4,
+                                 blank=0, nll=FAKE, dlogits=FAKE, workspace=FAKE, workspace_bytes=1 << 40, bad_labels=None, stream=None))
+SIZE = Entry("wn_ctc_workspace_bytes", dict(batch=2, classes=5, length=10, max_label_len=4))
 
 
 def test_ctc_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_ctc_workspace_bytes", "wn_ctc_loss"):
-        assert name in _lib.SIGNATURES
-        assert hasattr(lib, name)
-    assert len(_lib.SIGNATURES["wn_ctc_loss"][1]) == 15 and len(_lib.SIGNATURES["wn_ctc_workspace_bytes"][1]) == 4
+    for entry in (LOSS, SIZE):                                       # 15 and 4 arguments
+        entry.check_exported(lib)
+        entry.check_declared()
 
 
 def _bytes(B, T, L):
@@ -41,51 +36,43 @@ def test_workspace_bytes(lib):
         assert lib.wn_ctc_workspace_bytes(B, C, T, L) == 0, (B, C, T, L)
 
 
-def _loss(lib, B=2, C=5, T=10, L=4, blank=0, x=FAKE, labels=FAKE, label_len=FAKE, in_len=None, nll=FAKE, dx=FAKE, ws=FAKE,
-          ws_bytes=1 << 40, bad=None):
-    return lib.wn_ctc_loss(x, labels, label_len, in_len, B, C, T, L, blank, nll, dx, ws, ws_bytes, bad, None)
-
-
 def test_loss_rejects_on_the_host(lib):
-    for kw in (dict(B=0), dict(B=-2), dict(C=1), dict(C=0), dict(T=0), dict(T=-1), dict(L=0), dict(L=-1), dict(blank=5), dict(blank=-1),
-               dict(C=64, blank=64)):
-        assert _loss(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(C=MAX_CLASSES + 1), dict(L=MAX_LABELS + 1), dict(B=MAX_BATCH + 1), dict(B=MAX_BATCH, T=32769), dict(B=2, T=2 ** 30)):
-        assert _loss(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for name in ("x", "labels", "label_len", "nll", "ws"):
-        assert _loss(lib, **{name: None}) == WN_ERR_NULL, name
-    need = lib.wn_ctc_workspace_bytes(2, 5, 10, 4)
+    LOSS.rejects(lib, "logits",
+                 shape=(dict(batch=0), dict(batch=-2), dict(classes=1), dict(classes=0), dict(length=0), dict(length=-1), dict(max_label_len=0),
+                        dict(max_label_len=-1), dict(blank=5), dict(blank=-1), dict(classes=64, blank=64)),
+                 unsupported=(dict(classes=MAX_CLASSES + 1), dict(max_label_len=MAX_LABELS + 1), dict(batch=MAX_BATCH + 1),
+                              dict(batch=MAX_BATCH, length=32769), dict(batch=2, length=2 ** 30)),
+                 required=("logits", "labels", "label_lengths", "nll", "workspace"))
+    need = SIZE(lib)
     assert need == _bytes(2, 10, 4)
-    assert _loss(lib, ws_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _loss(lib, ws_bytes=0) == WN_ERR_WORKSPACE
+    assert LOSS(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert LOSS(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
     for off in (1, 2, 4, 7):
-        assert _loss(lib, ws=ctypes.c_void_p((1 << 20) + off)) == WN_ERR_WORKSPACE, off      # not 8-byte aligned
+        assert LOSS(lib, workspace=ctypes.c_void_p((1 << 20) + off)) == WN_ERR_WORKSPACE, off      # not 8-byte aligned
 
 
 def test_the_order_of_the_checks(lib):
     """shape, then unsupported, then NULL, then workspace"""
-    assert _loss(lib, B=0, C=65, x=None, ws_bytes=0) == WN_ERR_BAD_SHAPE
-    assert _loss(lib, blank=7, L=2048, x=None, ws_bytes=0) == WN_ERR_BAD_SHAPE
-    assert _loss(lib, C=65, x=None, ws_bytes=0) == WN_ERR_UNSUPPORTED
-    assert _loss(lib, x=None, ws_bytes=0) == WN_ERR_NULL
-    assert _loss(lib, ws=None, ws_bytes=0) == WN_ERR_NULL
-    assert _loss(lib, ws=ctypes.c_void_p((1 << 20) + 4), ws_bytes=0) == WN_ERR_WORKSPACE
+    assert LOSS(lib, batch=0, classes=65, logits=None, workspace_bytes=0) == WN_ERR_BAD_SHAPE
+    assert LOSS(lib, blank=7, max_label_len=2048, logits=None, workspace_bytes=0) == WN_ERR_BAD_SHAPE
+    assert LOSS(lib, classes=65, logits=None, workspace_bytes=0) == WN_ERR_UNSUPPORTED
+    assert LOSS(lib, logits=None, workspace_bytes=0) == WN_ERR_NULL
+    assert LOSS(lib, workspace=None, workspace_bytes=0) == WN_ERR_NULL
+    assert LOSS(lib, workspace=ctypes.c_void_p((1 << 20) + 4), workspace_bytes=0) == WN_ERR_WORKSPACE
 
 
 def test_the_limits_themselves_are_accepted(lib):
     """at C = 64, L = 2047, B = 65535 every check up to the workspace's passes: one byte short is the first complaint"""
-    for kw in (dict(C=MAX_CLASSES, blank=63), dict(L=MAX_LABELS), dict(B=MAX_BATCH), dict(B=MAX_BATCH, T=32768, L=1),
-               dict(B=1, C=MAX_CLASSES, T=2304, L=MAX_LABELS)):
-        shape = dict(B=2, C=5, T=10, L=4)
-        shape.update({k: v for k, v in kw.items() if k in shape})
-        need = lib.wn_ctc_workspace_bytes(shape["B"], shape["C"], shape["T"], shape["L"])
-        assert need == _bytes(shape["B"], shape["T"], shape["L"]) > 0, kw
-        assert _loss(lib, ws_bytes=need - 1, **kw) == WN_ERR_WORKSPACE, kw
+    for kw in (dict(classes=MAX_CLASSES, blank=63), dict(max_label_len=MAX_LABELS), dict(batch=MAX_BATCH),
+               dict(batch=MAX_BATCH, length=32768, max_label_len=1), dict(batch=1, classes=MAX_CLASSES, length=2304, max_label_len=MAX_LABELS)):
+        shape = dict(SIZE.defaults, **{k: v for k, v in kw.items() if k in SIZE.defaults})
+        need = SIZE(lib, **shape)
+        assert need == _bytes(shape["batch"], shape["length"], shape["max_label_len"]) > 0, kw
+        assert LOSS(lib, workspace_bytes=need - 1, **kw) == WN_ERR_WORKSPACE, kw
 
 
 def test_the_documented_limits_match():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "INTEGRATION.md")) as f:
+    with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
         text = f.read()
     line = next(l for l in text.splitlines() if "limits (checked, WN_ERR_UNSUPPORTED otherwise)" in l)
     m = re.search(r"C <= (\d+) classes, Lmax <= (\d+) labels per utterance, B <= (\d+), B\*T < 2\^(\d+)", line)

@@ -1,24 +1,22 @@
-"""CPU: the C ABI of the CTC decoders (csrc/wn_decode.hip): exported symbols, workspace sizes, and the shape / limit / pointer
-checks, which run on the host before any HIP call -- none of the calls below touches a device."""
+"""CPU: the C ABI of the CTC decoders (csrc/wn_decode.hip): exported symbols, the ctypes rows against the header, workspace sizes,
+and the shape / limit / pointer checks, which run on the host before any HIP call -- none of the calls below touches a device."""
 import ctypes
 
-import pytest
+from tests.abi_util import FAKE, WN_ERR_NULL, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE
-
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+X = dict(x=FAKE, sb=lambda a: a["classes"] * a["length"], sc=lambda a: a["length"], st=1)           # [B][C][T], dense
+GREEDY = Entry("wn_ctc_greedy_decode", dict(X, input_lengths=None, batch=2, classes=5, length=10, blank=0, labels=FAKE, frames=None, lengths=FAKE,
+                                            bad=None, stream=None))
+BEAM = Entry("wn_ctc_beam_decode", dict(X, input_kind=0, input_lengths=None, batch=2, classes=5, length=10, blank=0, beam_width=4, labels=FAKE,
+                                        frames=None, lengths=FAKE, scores=FAKE, workspace=FAKE, workspace_bytes=1 << 30, bad=None, stream=None))
+SIZE = Entry("wn_ctc_decode_workspace_bytes", dict(batch=2, classes=5, length=10, beam_width=4))
 
 
 def test_decode_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_ctc_decode_workspace_bytes", "wn_ctc_greedy_decode", "wn_ctc_beam_decode"):
-        assert name in _lib.SIGNATURES
-        assert hasattr(lib, name)
+    for entry in (SIZE, GREEDY, BEAM):                               # 4, 14 and 19 arguments
+        entry.check_exported(lib)
+        entry.check_declared()
 
 
 def test_workspace_bytes(lib):
@@ -33,29 +31,14 @@ def test_workspace_bytes(lib):
     assert lib.wn_ctc_decode_workspace_bytes(8, 5, 0, 8) == 0
 
 
-def _beam(lib, B=2, C=5, T=10, W=4, kind=0, ptr=FAKE, ws=FAKE, ws_bytes=1 << 30):
-    return lib.wn_ctc_beam_decode(ptr, C * T, T, 1, kind, None, B, C, T, 0, W, ptr, None, ptr, ptr, ws, ws_bytes, None, None)
-
-
 def test_beam_decode_rejects_on_the_host(lib):
-    assert _beam(lib, C=65) == WN_ERR_UNSUPPORTED
-    assert _beam(lib, W=65) == WN_ERR_UNSUPPORTED
-    assert _beam(lib, W=0) == WN_ERR_BAD_SHAPE
-    assert _beam(lib, B=0) == WN_ERR_BAD_SHAPE
-    assert _beam(lib, C=1) == WN_ERR_BAD_SHAPE
-    assert _beam(lib, T=0) == WN_ERR_BAD_SHAPE
-    assert _beam(lib, kind=3) == WN_ERR_BAD_SHAPE
-    assert _beam(lib, ptr=None) == WN_ERR_NULL
-    assert _beam(lib, ws=None) == WN_ERR_NULL
-    assert _beam(lib, ws_bytes=16) == WN_ERR_WORKSPACE
-    assert _beam(lib, ws=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE      # not 16-byte aligned
+    BEAM.rejects(lib, "x", shape=(dict(beam_width=0), dict(batch=0), dict(classes=1), dict(length=0), dict(input_kind=3)),
+                 unsupported=(dict(classes=65), dict(beam_width=65)), required=("workspace",))
+    assert BEAM(lib, x=None, labels=None, lengths=None, scores=None) == WN_ERR_NULL
+    assert BEAM(lib, workspace_bytes=16) == WN_ERR_WORKSPACE
+    assert BEAM(lib, workspace=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE       # not 16-byte aligned
 
 
 def test_greedy_decode_rejects_on_the_host(lib):
-    def greedy(B=2, C=5, T=10, ptr=FAKE):
-        return lib.wn_ctc_greedy_decode(ptr, C * T, T, 1, None, B, C, T, 0, ptr, None, ptr, None, None)
-    assert greedy(C=65) == WN_ERR_UNSUPPORTED
-    assert greedy(C=1) == WN_ERR_BAD_SHAPE
-    assert greedy(B=0) == WN_ERR_BAD_SHAPE
-    assert greedy(T=0) == WN_ERR_BAD_SHAPE
-    assert greedy(ptr=None) == WN_ERR_NULL
+    GREEDY.rejects(lib, "x", shape=(dict(classes=1), dict(batch=0), dict(length=0)), unsupported=(dict(classes=65),))
+    assert GREEDY(lib, x=None, labels=None, lengths=None) == WN_ERR_NULL

@@ -6,87 +6,57 @@ import numpy as np
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, Entry
+from tests.abi_util import lib  # noqa: F401
 
-SCORES = ["labels", "labels_stride", "lengths", "patterns", "pattern_stride", "pattern_lengths", "batch", "max_len", "n_patterns", "n_front",
-          "max_pattern_len", "window", "match", "mismatch", "gap_open", "gap_extend", "score", "start", "end", "bad", "stream"]
-PICK = ["score", "start", "end", "lengths", "pattern_group", "min_score", "batch", "n_patterns", "n_front", "min_margin", "require_both",
-        "barcode", "trim", "hits", "runner_up", "stream"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+SCORES = Entry("wn_demux_scores", dict(labels=FAKE, labels_stride=400, lengths=FAKE, patterns=FAKE, pattern_stride=40, pattern_lengths=FAKE, batch=2,
+                                       max_len=400, n_patterns=24, n_front=12, max_pattern_len=40, window=150, match=6, mismatch=-12, gap_open=10,
+                                       gap_extend=4, score=FAKE, start=FAKE, end=FAKE, bad=None, stream=None))
+PICK = Entry("wn_demux_pick", dict(score=FAKE, start=FAKE, end=FAKE, lengths=FAKE, pattern_group=FAKE, min_score=FAKE, batch=2, n_patterns=24,
+                                   n_front=12, min_margin=12, require_both=0, barcode=FAKE, trim=FAKE, hits=FAKE, runner_up=FAKE, stream=None))
 
 
 def test_symbols_are_exported(lib):
     from wavenet_speech_amd import _lib
-    for name in ("wn_demux_scores", "wn_demux_pick"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    SCORES.check_exported(lib)
+    PICK.check_exported(lib)
     assert "wn_demux_workspace_bytes" not in _lib.SIGNATURES         # no workspace is needed
-    assert lib.wn_version() == 300                                   # additive entry points
 
 
 def test_signature_rows_match_the_header():
-    check_row("wn_demux_scores", count=21, opaque=True)
-    check_row("wn_demux_pick", count=16, opaque=True)
-    assert header_names("wn_demux_scores") == SCORES and header_names("wn_demux_pick") == PICK
-
-
-def _scores(lib, **kw):
-    a = dict(labels=FAKE, labels_stride=400, lengths=FAKE, patterns=FAKE, pattern_stride=40, pattern_lengths=FAKE, batch=2, max_len=400,
-             n_patterns=24, n_front=12, max_pattern_len=40, window=150, match=6, mismatch=-12, gap_open=10, gap_extend=4, score=FAKE,
-             start=FAKE, end=FAKE, bad=None, stream=None)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_demux_scores(*[a[n] for n in SCORES])
-
-
-def _pick(lib, **kw):
-    a = dict(score=FAKE, start=FAKE, end=FAKE, lengths=FAKE, pattern_group=FAKE, min_score=FAKE, batch=2, n_patterns=24, n_front=12,
-             min_margin=12, require_both=0, barcode=FAKE, trim=FAKE, hits=FAKE, runner_up=FAKE, stream=None)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_demux_pick(*[a[n] for n in PICK])
+    SCORES.check_declared()                                          # 21 arguments
+    PICK.check_declared()                                            # 16
 
 
 def test_scores_rejects_on_the_host_in_order(lib):
-    """every accepted call here goes on to the NULL check (labels=None): nothing is ever launched"""
-    for kw in (dict(batch=0), dict(batch=-1), dict(n_patterns=0), dict(n_front=-1), dict(n_front=25), dict(max_len=0), dict(max_pattern_len=0),
-               dict(window=0), dict(window=-3), dict(labels_stride=-1), dict(pattern_stride=-1)):
-        assert _scores(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(batch=65536), dict(max_len=2 ** 24 + 1), dict(n_patterns=1025), dict(max_pattern_len=129), dict(window=513),
-               dict(gap_extend=-1), dict(gap_extend=11), dict(gap_open=1025, gap_extend=0), dict(match=1025), dict(match=-1025),
-               dict(mismatch=1025), dict(mismatch=-1025)):
-        assert _scores(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in (dict(batch=1), dict(batch=65535), dict(max_len=2 ** 24), dict(max_len=1), dict(n_patterns=1024), dict(n_patterns=12),
-               dict(n_front=0), dict(n_front=24), dict(max_pattern_len=128), dict(max_pattern_len=1), dict(window=512), dict(window=1),
-               dict(gap_extend=0), dict(gap_extend=10), dict(gap_open=1024, gap_extend=1024), dict(gap_open=0, gap_extend=0), dict(match=1024),
-               dict(match=-1024), dict(mismatch=1024), dict(mismatch=-1024), dict(labels_stride=0), dict(pattern_stride=0)):
-        assert _scores(lib, labels=None, **kw) == WN_ERR_NULL, kw
-    for name in ("labels", "lengths", "patterns", "pattern_lengths", "score", "start", "end"):
-        assert _scores(lib, **{name: None}) == WN_ERR_NULL, name
+    SCORES.rejects(lib, "labels",
+                   shape=(dict(batch=0), dict(batch=-1), dict(n_patterns=0), dict(n_front=-1), dict(n_front=25), dict(max_len=0),
+                          dict(max_pattern_len=0), dict(window=0), dict(window=-3), dict(labels_stride=-1), dict(pattern_stride=-1)),
+                   unsupported=(dict(batch=65536), dict(max_len=2 ** 24 + 1), dict(n_patterns=1025), dict(max_pattern_len=129), dict(window=513),
+                                dict(gap_extend=-1), dict(gap_extend=11), dict(gap_open=1025, gap_extend=0), dict(match=1025), dict(match=-1025),
+                                dict(mismatch=1025), dict(mismatch=-1025)),
+                   accepted=(dict(batch=1), dict(batch=65535), dict(max_len=2 ** 24), dict(max_len=1), dict(n_patterns=1024), dict(n_patterns=12),
+                             dict(n_front=0), dict(n_front=24), dict(max_pattern_len=128), dict(max_pattern_len=1), dict(window=512), dict(window=1),
+                             dict(gap_extend=0), dict(gap_extend=10), dict(gap_open=1024, gap_extend=1024), dict(gap_open=0, gap_extend=0),
+                             dict(match=1024), dict(match=-1024), dict(mismatch=1024), dict(mismatch=-1024), dict(labels_stride=0),
+                             dict(pattern_stride=0)),
+                   required=("labels", "lengths", "patterns", "pattern_lengths", "score", "start", "end"))
     # the order: shape, then unsupported, then NULL
-    assert _scores(lib, batch=0, window=513, labels=None) == WN_ERR_BAD_SHAPE
-    assert _scores(lib, n_front=1026, n_patterns=1025, score=None) == WN_ERR_BAD_SHAPE
-    assert _scores(lib, labels_stride=-1, match=2000, lengths=None) == WN_ERR_BAD_SHAPE
-    assert _scores(lib, window=513, labels=None) == WN_ERR_UNSUPPORTED
-    assert _scores(lib, gap_extend=11, end=None) == WN_ERR_UNSUPPORTED
+    assert SCORES(lib, batch=0, window=513, labels=None) == WN_ERR_BAD_SHAPE
+    assert SCORES(lib, n_front=1026, n_patterns=1025, score=None) == WN_ERR_BAD_SHAPE
+    assert SCORES(lib, labels_stride=-1, match=2000, lengths=None) == WN_ERR_BAD_SHAPE
+    assert SCORES(lib, window=513, labels=None) == WN_ERR_UNSUPPORTED
+    assert SCORES(lib, gap_extend=11, end=None) == WN_ERR_UNSUPPORTED
 
 
 def test_pick_rejects_on_the_host_in_order(lib):
-    for kw in (dict(batch=0), dict(batch=-1), dict(n_patterns=0), dict(n_front=-1), dict(n_front=25)):
-        assert _pick(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(batch=65536), dict(n_patterns=1025), dict(min_margin=-1)):
-        assert _pick(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in (dict(batch=1), dict(batch=65535), dict(n_patterns=1024), dict(n_front=0), dict(n_front=24), dict(min_margin=0),
-               dict(min_margin=2 ** 31 - 1), dict(require_both=1)):
-        assert _pick(lib, score=None, **kw) == WN_ERR_NULL, kw
-    for name in ("score", "start", "end", "lengths", "pattern_group", "min_score", "barcode", "trim", "hits", "runner_up"):
-        assert _pick(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _pick(lib, batch=0, min_margin=-1, score=None) == WN_ERR_BAD_SHAPE
-    assert _pick(lib, min_margin=-1, score=None) == WN_ERR_UNSUPPORTED
+    PICK.rejects(lib, "score", shape=(dict(batch=0), dict(batch=-1), dict(n_patterns=0), dict(n_front=-1), dict(n_front=25)),
+                 unsupported=(dict(batch=65536), dict(n_patterns=1025), dict(min_margin=-1)),
+                 accepted=(dict(batch=1), dict(batch=65535), dict(n_patterns=1024), dict(n_front=0), dict(n_front=24), dict(min_margin=0),
+                           dict(min_margin=2 ** 31 - 1), dict(require_both=1)),
+                 required=("score", "start", "end", "lengths", "pattern_group", "min_score", "barcode", "trim", "hits", "runner_up"))
+    assert PICK(lib, batch=0, min_margin=-1, score=None) == WN_ERR_BAD_SHAPE
+    assert PICK(lib, min_margin=-1, score=None) == WN_ERR_UNSUPPORTED
 
 
 def test_barcode_set_builds_the_table():

@@ -7,32 +7,25 @@ import ctypes
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row, header_names
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
-NAME = "wn_event_detect"
-ARGS = ["signal", "signal_kind", "signal_stride", "signal_lengths", "scale_shift", "batch", "max_signal", "frac_bits", "window_short",
-        "window_long", "radius_short", "radius_long", "threshold_short", "threshold_long", "min_var_short", "min_var_long", "max_event_len",
-        "max_events", "chunk_samples", "n_events", "starts", "ev_sum", "ev_sumsq", "ev_kind", "workspace", "workspace_bytes", "bad", "stream"]
-REQUIRED = ("signal", "signal_lengths", "n_events", "starts", "ev_sum", "ev_sumsq", "workspace")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+DETECT = Entry("wn_event_detect", dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, batch=2, max_signal=1000,
+                                       frac_bits=12, window_short=3, window_long=6, radius_short=3, radius_long=6, threshold_short=4096,
+                                       threshold_long=9216, min_var_short=100, min_var_long=400, max_event_len=65536, max_events=1000,
+                                       chunk_samples=0, n_events=FAKE, starts=FAKE, ev_sum=FAKE, ev_sumsq=FAKE, ev_kind=FAKE, workspace=FAKE,
+                                       workspace_bytes=0, bad=None, stream=None))    # workspace_bytes 0: never launches
+SIZE = Entry("wn_event_detect_workspace_bytes", dict(batch=2, max_signal=1000))
 
 
 def test_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in (NAME, NAME + "_workspace_bytes"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # additive entry points
+    DETECT.check_exported(lib)
+    SIZE.check_exported(lib)
 
 
 def test_signature_rows_match_the_header():
-    check_row(NAME, count=28, opaque=True)
-    check_row(NAME + "_workspace_bytes", count=2, opaque=True)
-    assert header_names(NAME) == ARGS and header_names(NAME + "_workspace_bytes") == ["batch", "max_signal"]
+    DETECT.check_declared()                                          # 28 arguments
+    SIZE.check_declared()                                            # 2
 
 
 def test_size_function(lib):
@@ -44,56 +37,42 @@ def test_size_function(lib):
         assert need <= size(B, L) < need + 3 * 256 and size(B, L) % 16 == 0, (B, L)
 
 
-def _call(lib, **kw):
-    a = dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, batch=2, max_signal=1000, frac_bits=12,
-             window_short=3, window_long=6, radius_short=3, radius_long=6, threshold_short=4096, threshold_long=9216, min_var_short=100,
-             min_var_long=400, max_event_len=65536, max_events=1000, chunk_samples=0, n_events=FAKE, starts=FAKE, ev_sum=FAKE,
-             ev_sumsq=FAKE, ev_kind=FAKE, workspace=FAKE, workspace_bytes=0, bad=None, stream=None)    # workspace_bytes 0: never launches
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_event_detect(*[a[n] for n in ARGS])
-
-
 def test_rejects_on_the_host_in_order(lib):
-    assert _call(lib) == WN_ERR_WORKSPACE                            # everything else about the default call is accepted
-    for kw in (dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(max_events=0), dict(max_events=-1),
-               dict(signal_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)):
-        assert _call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(frac_bits=-1), dict(frac_bits=21), dict(batch=65536), dict(max_signal=2 ** 24 + 1), dict(max_events=2 ** 24 + 1),
-               dict(window_short=0), dict(window_short=17), dict(window_long=-1), dict(window_long=17), dict(radius_short=0),
-               dict(radius_short=65), dict(radius_long=0), dict(radius_long=65), dict(threshold_short=0), dict(threshold_long=0),
-               dict(threshold_long=-7), dict(min_var_short=0), dict(min_var_short=2 ** 55 + 1), dict(min_var_long=0),
-               dict(min_var_long=2 ** 55 + 1), dict(max_event_len=0), dict(max_event_len=65537), dict(chunk_samples=128),
-               dict(chunk_samples=-256), dict(chunk_samples=384), dict(chunk_samples=16384 + 256), dict(chunk_samples=1)):
-        assert _call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    # the accepted side of each limit goes on to the pointer checks
-    for kw in (dict(frac_bits=0), dict(frac_bits=20), dict(batch=65535), dict(batch=1), dict(max_signal=2 ** 24), dict(max_signal=1),
-               dict(max_events=2 ** 24), dict(max_events=1), dict(window_short=1), dict(window_short=16), dict(window_long=0),
-               dict(window_long=16), dict(radius_short=1), dict(radius_short=64), dict(radius_long=1), dict(radius_long=64),
-               dict(threshold_short=1), dict(threshold_long=2 ** 31 - 1), dict(min_var_short=1), dict(min_var_short=2 ** 55),
-               dict(min_var_long=1), dict(min_var_long=2 ** 55), dict(max_event_len=1), dict(max_event_len=65536), dict(chunk_samples=256),
-               dict(chunk_samples=768), dict(chunk_samples=16384), dict(signal_kind=1), dict(signal_stride=0),
-               dict(window_long=0, radius_long=0, threshold_long=0, min_var_long=0)):         # the long detector off: its three are ignored
-        assert _call(lib, signal=None, **kw) == WN_ERR_NULL, kw
-    for name in REQUIRED:
-        assert _call(lib, **{name: None}) == WN_ERR_NULL, name
+    assert DETECT(lib) == WN_ERR_WORKSPACE                           # everything else about the default call is accepted
+    DETECT.rejects(lib, "signal",
+                   shape=(dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(max_events=0), dict(max_events=-1),
+                          dict(signal_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)),
+                   unsupported=(dict(frac_bits=-1), dict(frac_bits=21), dict(batch=65536), dict(max_signal=2 ** 24 + 1), dict(max_events=2 ** 24 + 1),
+                                dict(window_short=0), dict(window_short=17), dict(window_long=-1), dict(window_long=17), dict(radius_short=0),
+                                dict(radius_short=65), dict(radius_long=0), dict(radius_long=65), dict(threshold_short=0), dict(threshold_long=0),
+                                dict(threshold_long=-7), dict(min_var_short=0), dict(min_var_short=2 ** 55 + 1), dict(min_var_long=0),
+                                dict(min_var_long=2 ** 55 + 1), dict(max_event_len=0), dict(max_event_len=65537), dict(chunk_samples=128),
+                                dict(chunk_samples=-256), dict(chunk_samples=384), dict(chunk_samples=16384 + 256), dict(chunk_samples=1)),
+                   accepted=(dict(frac_bits=0), dict(frac_bits=20), dict(batch=65535), dict(batch=1), dict(max_signal=2 ** 24), dict(max_signal=1),
+                             dict(max_events=2 ** 24), dict(max_events=1), dict(window_short=1), dict(window_short=16), dict(window_long=0),
+                             dict(window_long=16), dict(radius_short=1), dict(radius_short=64), dict(radius_long=1), dict(radius_long=64),
+                             dict(threshold_short=1), dict(threshold_long=2 ** 31 - 1), dict(min_var_short=1), dict(min_var_short=2 ** 55),
+                             dict(min_var_long=1), dict(min_var_long=2 ** 55), dict(max_event_len=1), dict(max_event_len=65536),
+                             dict(chunk_samples=256), dict(chunk_samples=768), dict(chunk_samples=16384), dict(signal_kind=1), dict(signal_stride=0),
+                             dict(window_long=0, radius_long=0, threshold_long=0, min_var_long=0)),   # the long detector off: its three are ignored
+                   required=("signal", "signal_lengths", "n_events", "starts", "ev_sum", "ev_sumsq", "workspace"))
     for name in ("scale_shift", "ev_kind", "bad"):                   # optional
-        assert _call(lib, **{name: None}) == WN_ERR_WORKSPACE, name
+        assert DETECT(lib, **{name: None}) == WN_ERR_WORKSPACE, name
     # the workspace: too small by one byte, misaligned, and a signal off its element size
-    need = lib.wn_event_detect_workspace_bytes(2, 1000)
-    assert _call(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _call(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, batch=300, workspace_bytes=need) == WN_ERR_WORKSPACE           # the size follows the batch
+    need = SIZE(lib)
+    assert DETECT(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert DETECT(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert DETECT(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert DETECT(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert DETECT(lib, batch=300, workspace_bytes=need) == WN_ERR_WORKSPACE          # the size follows the batch
     # the order: shape, then unsupported, then NULL, then workspace
-    assert _call(lib, batch=0, frac_bits=21, signal=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, signal_kind=2, chunk_samples=100, starts=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, max_events=0, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, window_short=17, signal=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, max_event_len=0, n_events=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, chunk_samples=100, workspace=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, ev_sum=None, workspace_bytes=0) == WN_ERR_NULL
+    assert DETECT(lib, batch=0, frac_bits=21, signal=None) == WN_ERR_BAD_SHAPE
+    assert DETECT(lib, signal_kind=2, chunk_samples=100, starts=None) == WN_ERR_BAD_SHAPE
+    assert DETECT(lib, max_events=0, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
+    assert DETECT(lib, window_short=17, signal=None) == WN_ERR_UNSUPPORTED
+    assert DETECT(lib, max_event_len=0, n_events=None) == WN_ERR_UNSUPPORTED
+    assert DETECT(lib, chunk_samples=100, workspace=None) == WN_ERR_UNSUPPORTED
+    assert DETECT(lib, ev_sum=None, workspace_bytes=0) == WN_ERR_NULL
 
 
 def test_python_surface_refusals():

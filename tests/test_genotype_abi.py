@@ -8,13 +8,9 @@ import ctypes
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
-
-EVIDENCE = ["ops", "ops_stride", "ops_len", "lo", "ref_lengths", "strand", "query", "query_stride", "query_lengths", "qual", "qual_stride", "keep",
-            "batch", "max_query_len", "max_ops", "reference_len", "cap", "weights_host", "flat_qual", "gap_qual", "min_qual", "evidence", "used",
-            "bad", "stream"]
-CALL = ["evidence", "counts", "ins_lengths", "ins_bases", "reference", "reference_len", "max_ins", "min_depth", "alt_prior", "weights_host",
-        "gap_qual", "alleles", "gq", "qual", "flags", "ins_copies", "ins_len", "ins_out", "ins_gq", "ins_qual", "costs", "stream"]
+from tests.abi_util import FAKE, READ_ACCEPTED, READ_BATCH, READ_REQUIRED, READ_SHAPE, READ_UNSUPPORTED, WN_ERR_BAD_SHAPE, WN_ERR_NULL, \
+    WN_ERR_UNSUPPORTED, Entry, header_names, host_alignment
+from tests.abi_util import lib  # noqa: F401
 
 
 def _table(fill=1, **at):
@@ -25,103 +21,57 @@ def _table(fill=1, **at):
 
 
 GOOD = _table()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+EVIDENCE = Entry("wn_pileup_evidence", dict(READ_BATCH, cap=None, weights_host=GOOD, flat_qual=20, gap_qual=20, min_qual=0, evidence=FAKE, used=FAKE,
+                                            bad=None, stream=None))
+CALL = Entry("wn_genotype_call", dict(evidence=FAKE, counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE, reference=FAKE, reference_len=5000, max_ins=4,
+                                      min_depth=3, alt_prior=3000, weights_host=GOOD, gap_qual=20, alleles=FAKE, gq=FAKE, qual=FAKE, flags=FAKE,
+                                      ins_copies=FAKE, ins_len=FAKE, ins_out=FAKE, ins_gq=FAKE, ins_qual=FAKE, costs=None, stream=None))
 
 
 def test_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_pileup_evidence", "wn_genotype_call"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # additive entry points
+    EVIDENCE.check_exported(lib)
+    CALL.check_exported(lib)
 
 
 def test_signature_rows_match_the_header():
-    check_row("wn_pileup_evidence", count=25, opaque=True)
-    check_row("wn_genotype_call", count=22, opaque=True)
-    assert header_names("wn_pileup_evidence") == EVIDENCE and header_names("wn_genotype_call") == CALL
-    assert header_names("wn_pileup_evidence")[:16] == header_names("wn_pileup")[:16]          # the same read arguments
-
-
-def _call(fn, names, defaults, kw):
-    assert set(kw) <= set(defaults), kw
-    a = dict(defaults, **kw)
-    return fn(*[ctypes.cast(a[n], ctypes.c_void_p) if isinstance(a[n], ctypes.Array) else a[n] for n in names])
-
-
-def _evidence(lib, **kw):
-    return _call(lib.wn_pileup_evidence, EVIDENCE,
-                 dict(ops=FAKE, ops_stride=900, ops_len=FAKE, lo=FAKE, ref_lengths=FAKE, strand=FAKE, query=FAKE, query_stride=400, query_lengths=FAKE,
-                      qual=None, qual_stride=0, keep=None, batch=2, max_query_len=400, max_ops=900, reference_len=5000, cap=None, weights_host=GOOD,
-                      flat_qual=20, gap_qual=20, min_qual=0, evidence=FAKE, used=FAKE, bad=None, stream=None), kw)
-
-
-def _genotype(lib, **kw):
-    return _call(lib.wn_genotype_call, CALL,
-                 dict(evidence=FAKE, counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE, reference=FAKE, reference_len=5000, max_ins=4, min_depth=3,
-                      alt_prior=3000, weights_host=GOOD, gap_qual=20, alleles=FAKE, gq=FAKE, qual=FAKE, flags=FAKE, ins_copies=FAKE, ins_len=FAKE,
-                      ins_out=FAKE, ins_gq=FAKE, ins_qual=FAKE, costs=None, stream=None), kw)
-
-
-def _both_sides(call, lib, null, shape, unsupported, accepted):
-    """every accepted call goes on to the NULL check (`null`=None): nothing is ever launched"""
-    for kw in shape:
-        assert call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in unsupported:
-        assert call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in accepted:
-        assert call(lib, **dict(kw, **{null: None})) == WN_ERR_NULL, kw
+    EVIDENCE.check_declared()                                        # 25 arguments
+    CALL.check_declared()                                            # 22
+    assert header_names("wn_pileup_evidence")[:16] == header_names("wn_pileup")[:16] == list(READ_BATCH)      # the same read arguments
 
 
 def test_pileup_evidence_rejects_on_the_host_in_order(lib):
-    _both_sides(_evidence, lib, "ops",
-                shape=(dict(batch=0), dict(batch=-1), dict(max_query_len=0), dict(max_ops=0), dict(reference_len=0), dict(ops_stride=-1),
-                       dict(query_stride=-1), dict(qual_stride=-1), dict(min_qual=-1), dict(flat_qual=-1), dict(gap_qual=-1)),
-                unsupported=(dict(batch=65536), dict(max_query_len=8193), dict(max_ops=65535 + 8192 + 1), dict(reference_len=2 ** 26 + 1),
-                             dict(min_qual=94), dict(flat_qual=94), dict(gap_qual=94)),
-                accepted=(dict(batch=1), dict(batch=65535), dict(max_query_len=1), dict(max_query_len=8192), dict(max_ops=1),
-                          dict(max_ops=65535 + 8192), dict(reference_len=1), dict(reference_len=2 ** 26), dict(min_qual=0), dict(min_qual=93),
-                          dict(flat_qual=0), dict(flat_qual=93), dict(gap_qual=0), dict(gap_qual=93), dict(ops_stride=0),
-                          dict(qual=FAKE, qual_stride=400), dict(keep=FAKE), dict(cap=FAKE), dict(bad=FAKE)))
-    for name in ("ops", "ops_len", "lo", "ref_lengths", "strand", "query", "query_lengths", "weights_host", "evidence", "used"):
-        assert _evidence(lib, **{name: None}) == WN_ERR_NULL, name
+    EVIDENCE.rejects(lib, "ops", shape=READ_SHAPE + (dict(flat_qual=-1), dict(gap_qual=-1)),
+                     unsupported=READ_UNSUPPORTED + (dict(flat_qual=94), dict(gap_qual=94)),
+                     accepted=READ_ACCEPTED + (dict(reference_len=1), dict(flat_qual=0), dict(flat_qual=93), dict(gap_qual=0), dict(gap_qual=93),
+                                               dict(cap=FAKE)),
+                     required=READ_REQUIRED + ("weights_host", "evidence", "used"))
     # the weights are read last, once the table is known not to be NULL: both sides of [0, 2^20], first and last entry
     for kw in (dict(w0=-1), dict(w0=2 ** 20 + 1), dict(w281=-1), dict(w281=2 ** 20 + 1), dict(w94=2 ** 31 - 1)):
-        assert _evidence(lib, weights_host=_table(**kw)) == WN_ERR_UNSUPPORTED, kw
-        assert _evidence(lib, weights_host=_table(**kw), ops=None) == WN_ERR_NULL, kw
+        assert EVIDENCE(lib, weights_host=_table(**kw)) == WN_ERR_UNSUPPORTED, kw
+        assert EVIDENCE(lib, weights_host=_table(**kw), ops=None) == WN_ERR_NULL, kw
     for t in (_table(0), _table(2 ** 20), _table(w0=0, w281=2 ** 20)):
-        assert _evidence(lib, weights_host=t, ops=None) == WN_ERR_NULL                            # accepted: on to the NULL check
-    assert _evidence(lib, batch=0, gap_qual=94, ops=None) == WN_ERR_BAD_SHAPE                   # the order: shape, unsupported, NULL, weights
-    assert _evidence(lib, flat_qual=-1, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
-    assert _evidence(lib, flat_qual=94, ops=None, weights_host=_table(w0=-1)) == WN_ERR_UNSUPPORTED
+        assert EVIDENCE(lib, weights_host=t, ops=None) == WN_ERR_NULL                            # accepted: on to the NULL check
+    assert EVIDENCE(lib, batch=0, gap_qual=94, ops=None) == WN_ERR_BAD_SHAPE                   # the order: shape, unsupported, NULL, weights
+    assert EVIDENCE(lib, flat_qual=-1, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
+    assert EVIDENCE(lib, flat_qual=94, ops=None, weights_host=_table(w0=-1)) == WN_ERR_UNSUPPORTED
 
 
 def test_genotype_call_rejects_on_the_host_in_order(lib):
-    _both_sides(_genotype, lib, "evidence",
-                shape=(dict(reference_len=0), dict(reference_len=-1), dict(max_ins=-1), dict(min_depth=0), dict(gap_qual=-1)),
-                unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9), dict(gap_qual=94), dict(alt_prior=-1), dict(alt_prior=2 ** 30 + 1)),
-                accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(min_depth=1),
-                          dict(min_depth=2 ** 31 - 1), dict(gap_qual=0), dict(gap_qual=93), dict(alt_prior=0), dict(alt_prior=2 ** 30),
-                          dict(costs=FAKE)))
-    for name in ("evidence", "counts", "ins_lengths", "ins_bases", "reference", "weights_host", "alleles", "gq", "qual", "flags", "ins_copies",
-                 "ins_len", "ins_out", "ins_gq", "ins_qual"):
-        assert _genotype(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _genotype(lib, max_ins=0, ins_bases=None, ins_out=None, evidence=None) == WN_ERR_NULL
+    CALL.rejects(lib, "evidence",
+                 shape=(dict(reference_len=0), dict(reference_len=-1), dict(max_ins=-1), dict(min_depth=0), dict(gap_qual=-1)),
+                 unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9), dict(gap_qual=94), dict(alt_prior=-1), dict(alt_prior=2 ** 30 + 1)),
+                 accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(min_depth=1),
+                           dict(min_depth=2 ** 31 - 1), dict(gap_qual=0), dict(gap_qual=93), dict(alt_prior=0), dict(alt_prior=2 ** 30),
+                           dict(costs=FAKE)),
+                 required=("evidence", "counts", "ins_lengths", "ins_bases", "reference", "weights_host", "alleles", "gq", "qual", "flags",
+                           "ins_copies", "ins_len", "ins_out", "ins_gq", "ins_qual"))
+    assert CALL(lib, max_ins=0, ins_bases=None, ins_out=None, evidence=None) == WN_ERR_NULL
     for kw in (dict(w0=-1), dict(w0=2 ** 20 + 1), dict(w281=-1), dict(w281=2 ** 20 + 1)):
-        assert _genotype(lib, weights_host=_table(**kw)) == WN_ERR_UNSUPPORTED, kw
-        assert _genotype(lib, weights_host=_table(**kw), evidence=None) == WN_ERR_NULL, kw
-    assert _genotype(lib, weights_host=_table(2 ** 20), evidence=None) == WN_ERR_NULL
-    assert _genotype(lib, min_depth=0, max_ins=9, evidence=None) == WN_ERR_BAD_SHAPE
-    assert _genotype(lib, alt_prior=-1, evidence=None) == WN_ERR_UNSUPPORTED
-
-
-def _alignment(B=2, n=30):
-    import wavenet_speech_amd as W
-    return W.PairwiseAlignment(None, None, None, None, None, torch.ones(B, n, dtype=torch.uint8), torch.full((B,), n, dtype=torch.int32))
+        assert CALL(lib, weights_host=_table(**kw)) == WN_ERR_UNSUPPORTED, kw
+        assert CALL(lib, weights_host=_table(**kw), evidence=None) == WN_ERR_NULL, kw
+    assert CALL(lib, weights_host=_table(2 ** 20), evidence=None) == WN_ERR_NULL
+    assert CALL(lib, min_depth=0, max_ins=9, evidence=None) == WN_ERR_BAD_SHAPE
+    assert CALL(lib, alt_prior=-1, evidence=None) == WN_ERR_UNSUPPORTED
 
 
 def test_python_surface_refusals():
@@ -131,7 +81,7 @@ def test_python_surface_refusals():
         with pytest.raises(ValueError, match="wavenet_speech_amd.genotype_weights: scale must be an integer in"):
             W.genotype_weights(scale)
     query, n = torch.ones(2, 30, dtype=torch.int32), [30, 30]
-    args = dict(alignment=_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, R=100, weights=w)
+    args = dict(alignment=host_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, R=100, weights=w)
     with pytest.raises(ValueError, match="wavenet_speech_amd.pileup_evidence: alignment must be a PairwiseAlignment with ops"):
         W.pileup_evidence(**dict(args, alignment=W.PairwiseAlignment(None, None, None, None, None, None, None)))
     with pytest.raises(RuntimeError, match="wavenet_speech_amd.pileup_evidence: alignment.ops must be a GPU tensor \\(there is no CPU fallback\\)"):

@@ -3,29 +3,24 @@ workspace formula, and the shape / limit / pointer checks, which run on the host
 below touches a device."""
 import ctypes
 
-import pytest
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row
-
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+PAIR = Entry("wn_pair_align", dict(ref=FAKE, ref_stride=lambda a: a["max_ref_len"], ref_lengths=FAKE, query=FAKE,
+                                   query_stride=lambda a: a["max_query_len"], query_lengths=FAKE, batch=2, max_ref_len=10, max_query_len=12,
+                                   match=10, mismatch=-8, gap_open=20, gap_extend=1, end_gaps_free=1, score=FAKE, stats=FAKE, ops=FAKE,
+                                   ops_len=FAKE, workspace=FAKE, workspace_bytes=1 << 40, bad=None, stream=None))
+SIZE = Entry("wn_pair_align_workspace_bytes", dict(batch=2, max_ref_len=10, max_query_len=12))
 
 
 def test_pair_align_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_pair_align_workspace_bytes", "wn_pair_align"):
-        assert name in _lib.SIGNATURES
-        assert hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # an additive entry point
+    PAIR.check_exported(lib)
+    SIZE.check_exported(lib)
 
 
 def test_signature_table_matches_the_header():
-    for name in ("wn_pair_align_workspace_bytes", "wn_pair_align"):
-        check_row(name, opaque=True)
+    PAIR.check_declared()                                            # 22 arguments
+    SIZE.check_declared()                                            # 3
 
 
 def _want_bytes(B, N, M):
@@ -47,42 +42,26 @@ def test_workspace_bytes(lib):
         assert lib.wn_pair_align_workspace_bytes(B, N, M) == 0, (B, N, M)
 
 
-def _call(lib, B=2, N=10, M=12, costs=(10, -8, 20, 1), free=1, ref=FAKE, ref_len=FAKE, query=FAKE, query_len=FAKE, score=FAKE,
-          stats=FAKE, ops=FAKE, ops_len=FAKE, ws=FAKE, ws_bytes=1 << 40):
-    return lib.wn_pair_align(ref, N, ref_len, query, M, query_len, B, N, M, costs[0], costs[1], costs[2], costs[3], free, score,
-                             stats, ops, ops_len, ws, ws_bytes, None, None)
-
-
 def test_pair_align_rejects_on_the_host(lib):
-    # every limit: WN_ERR_UNSUPPORTED, nothing launched
-    assert _call(lib, M=8193) == WN_ERR_UNSUPPORTED
-    assert _call(lib, N=65536) == WN_ERR_UNSUPPORTED
-    assert _call(lib, B=65536) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(10, -8, 1025, 1)) == WN_ERR_UNSUPPORTED         # gap_open > 1024
-    assert _call(lib, costs=(10, -8, 20, 21)) == WN_ERR_UNSUPPORTED          # gap_extend > gap_open
-    assert _call(lib, costs=(10, -8, 20, -1)) == WN_ERR_UNSUPPORTED          # gap_extend < 0
-    assert _call(lib, costs=(10, -8, -1, -2)) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(1025, -8, 20, 1)) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(-1025, -8, 20, 1)) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(10, 1025, 20, 1)) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(10, -1025, 20, 1)) == WN_ERR_UNSUPPORTED
-    # non-positive shapes
-    assert _call(lib, B=0) == WN_ERR_BAD_SHAPE
-    assert _call(lib, N=0) == WN_ERR_BAD_SHAPE
-    assert _call(lib, M=0) == WN_ERR_BAD_SHAPE
-    assert _call(lib, M=-4) == WN_ERR_BAD_SHAPE
-    # required pointers; ops and ops_len come together; stats or ops need the workspace
-    for name in ("ref", "ref_len", "query", "query_len", "score", "ops", "ops_len", "ws"):
-        assert _call(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _call(lib, stats=None, ws=None) == WN_ERR_NULL                    # ops still want it
-    need = lib.wn_pair_align_workspace_bytes(2, 10, 12)
+    PAIR.rejects(lib, "ref",
+                 shape=(dict(batch=0), dict(max_ref_len=0), dict(max_query_len=0), dict(max_query_len=-4)),         # non-positive shapes
+                 # every limit: WN_ERR_UNSUPPORTED, nothing launched
+                 unsupported=(dict(max_query_len=8193), dict(max_ref_len=65536), dict(batch=65536),
+                              dict(gap_open=1025),                   # gap_open > 1024
+                              dict(gap_extend=21),                   # gap_extend > gap_open
+                              dict(gap_extend=-1),                   # gap_extend < 0
+                              dict(gap_open=-1, gap_extend=-2), dict(match=1025), dict(match=-1025), dict(mismatch=1025), dict(mismatch=-1025)),
+                 # required pointers; ops and ops_len come together; stats or ops need the workspace
+                 required=("ref", "ref_lengths", "query", "query_lengths", "score", "ops", "ops_len", "workspace"))
+    assert PAIR(lib, stats=None, workspace=None) == WN_ERR_NULL                          # ops still want it
+    need = SIZE(lib)
     assert need > 0
-    assert _call(lib, ws_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _call(lib, ws_bytes=0) == WN_ERR_WORKSPACE
-    assert _call(lib, ops=None, ops_len=None, ws_bytes=need - 1) == WN_ERR_WORKSPACE     # stats alone need it too
-    assert _call(lib, ws=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE             # not 16-byte aligned
+    assert PAIR(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert PAIR(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
+    assert PAIR(lib, ops=None, ops_len=None, workspace_bytes=need - 1) == WN_ERR_WORKSPACE             # stats alone need it too
+    assert PAIR(lib, workspace=ctypes.c_void_p((1 << 20) + 8)) == WN_ERR_WORKSPACE                     # not 16-byte aligned
     # the order of the checks: shape, then unsupported, then NULL, then workspace
-    assert _call(lib, B=0, M=8193, ref=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, M=8193, ref=None, ws_bytes=0) == WN_ERR_UNSUPPORTED
-    assert _call(lib, costs=(10, -8, 20, 21), ref=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, ref=None, ws_bytes=0) == WN_ERR_NULL
+    assert PAIR(lib, batch=0, max_query_len=8193, ref=None) == WN_ERR_BAD_SHAPE
+    assert PAIR(lib, max_query_len=8193, ref=None, workspace_bytes=0) == WN_ERR_UNSUPPORTED
+    assert PAIR(lib, gap_extend=21, ref=None) == WN_ERR_UNSUPPORTED
+    assert PAIR(lib, ref=None, workspace_bytes=0) == WN_ERR_NULL

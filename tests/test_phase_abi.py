@@ -6,113 +6,60 @@ import numpy as np
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+from tests.abi_util import FAKE, READ_ACCEPTED, READ_BATCH, READ_REQUIRED, READ_SHAPE, READ_UNSUPPORTED, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, \
+    Entry, header_names, host_alignment
+from tests.abi_util import lib  # noqa: F401
 
-READS = ["ops", "ops_stride", "ops_len", "lo", "ref_lengths", "strand", "query", "query_stride", "query_lengths", "qual", "qual_stride", "keep",
-         "batch", "max_query_len", "max_ops", "reference_len", "cap", "flat_qual", "gap_qual", "min_qual", "site_of", "alleles", "n_sites"]
-LINKS = READS + ["reach", "links", "observed", "used", "bad", "stream"]
-TAG = READS + ["pos", "root", "parity", "set_size", "hp", "ps", "weight", "n_observed", "bad", "stream"]
-CHAIN = ["links", "pos", "n_sites", "reach", "min_margin", "parent", "flip", "margin", "root", "parity", "ps", "set_size", "work", "stream"]
-READ_DEFAULTS = dict(ops=FAKE, ops_stride=900, ops_len=FAKE, lo=FAKE, ref_lengths=FAKE, strand=FAKE, query=FAKE, query_stride=400, query_lengths=FAKE,
-                     qual=None, qual_stride=0, keep=None, batch=2, max_query_len=400, max_ops=900, reference_len=5000, cap=None, flat_qual=20,
-                     gap_qual=20, min_qual=0, site_of=FAKE, alleles=FAKE, n_sites=40)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+READS = dict(READ_BATCH, cap=None, flat_qual=20, gap_qual=20, min_qual=0, site_of=FAKE, alleles=FAKE, n_sites=40)
+LINKS = Entry("wn_phase_links", dict(READS, reach=4, links=FAKE, observed=FAKE, used=FAKE, bad=None, stream=None))
+TAG = Entry("wn_haplotag", dict(READS, pos=FAKE, root=FAKE, parity=FAKE, set_size=FAKE, hp=FAKE, ps=FAKE, weight=FAKE, n_observed=FAKE, bad=None,
+                                stream=None))
+CHAIN = Entry("wn_phase_chain", dict(links=FAKE, pos=FAKE, n_sites=40, reach=4, min_margin=1, parent=FAKE, flip=FAKE, margin=FAKE, root=FAKE,
+                                     parity=FAKE, ps=FAKE, set_size=FAKE, work=FAKE, stream=None))
+# what the sites add to the read batch: the qualities of wn_pileup_evidence, and a reference that holds n_sites positions
+SITES_SHAPE = READ_SHAPE + (dict(flat_qual=-1), dict(gap_qual=-1), dict(n_sites=0), dict(n_sites=-1))
+SITES_UNSUPPORTED = READ_UNSUPPORTED + (dict(reference_len=2 ** 26 + 1, n_sites=1), dict(flat_qual=94), dict(gap_qual=94), dict(n_sites=5001),
+                                        dict(reference_len=39))
+SITES_ACCEPTED = READ_ACCEPTED + (dict(reference_len=40), dict(reference_len=2 ** 26, n_sites=2 ** 26), dict(flat_qual=0), dict(flat_qual=93),
+                                  dict(gap_qual=0), dict(gap_qual=93), dict(n_sites=1), dict(n_sites=5000), dict(cap=FAKE))
+SITES_REQUIRED = READ_REQUIRED + ("site_of", "alleles")
 
 
 def test_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in ("wn_phase_links", "wn_phase_chain", "wn_haplotag"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # additive entry points
+    for entry in (LINKS, CHAIN, TAG):
+        entry.check_exported(lib)
 
 
 def test_signature_rows_match_the_header():
-    check_row("wn_phase_links", count=29, opaque=True)
-    check_row("wn_phase_chain", count=14, opaque=True)
-    check_row("wn_haplotag", count=33, opaque=True)
-    assert header_names("wn_phase_links") == LINKS and header_names("wn_haplotag") == TAG and header_names("wn_phase_chain") == CHAIN
-    assert header_names("wn_phase_links")[:16] == header_names("wn_pileup")[:16]             # the same read arguments
+    for entry in (LINKS, CHAIN, TAG):                                # 29, 14 and 33 arguments
+        entry.check_declared()
+    assert header_names("wn_phase_links")[:16] == header_names("wn_pileup")[:16] == list(READ_BATCH)          # the same read arguments
     evidence = header_names("wn_pileup_evidence")
-    assert [n for n in LINKS[:20]] == [n for n in evidence[:21] if n != "weights_host"]      # and pileup_evidence's qualities
-
-
-def _call(fn, names, defaults, kw):
-    assert set(kw) <= set(defaults), kw
-    a = dict(defaults, **kw)
-    return fn(*[a[n] for n in names])
-
-
-def _links(lib, **kw):
-    return _call(lib.wn_phase_links, LINKS, dict(READ_DEFAULTS, reach=4, links=FAKE, observed=FAKE, used=FAKE, bad=None, stream=None), kw)
-
-
-def _tag(lib, **kw):
-    return _call(lib.wn_haplotag, TAG, dict(READ_DEFAULTS, pos=FAKE, root=FAKE, parity=FAKE, set_size=FAKE, hp=FAKE, ps=FAKE, weight=FAKE,
-                                            n_observed=FAKE, bad=None, stream=None), kw)
-
-
-def _chain(lib, **kw):
-    return _call(lib.wn_phase_chain, CHAIN, dict(links=FAKE, pos=FAKE, n_sites=40, reach=4, min_margin=1, parent=FAKE, flip=FAKE, margin=FAKE,
-                                                 root=FAKE, parity=FAKE, ps=FAKE, set_size=FAKE, work=FAKE, stream=None), kw)
-
-
-def _both_sides(call, lib, null, shape, unsupported, accepted):
-    """every accepted call goes on to the NULL check (`null`=None): nothing is ever launched"""
-    for kw in shape:
-        assert call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in unsupported:
-        assert call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in accepted:
-        assert call(lib, **dict(kw, **{null: None})) == WN_ERR_NULL, kw
-
-
-READ_SHAPE = (dict(batch=0), dict(batch=-1), dict(max_query_len=0), dict(max_ops=0), dict(reference_len=0), dict(ops_stride=-1), dict(query_stride=-1),
-              dict(qual_stride=-1), dict(min_qual=-1), dict(flat_qual=-1), dict(gap_qual=-1), dict(n_sites=0), dict(n_sites=-1))
-READ_UNSUPPORTED = (dict(batch=65536), dict(max_query_len=8193), dict(max_ops=65535 + 8192 + 1), dict(reference_len=2 ** 26 + 1, n_sites=1),
-                    dict(min_qual=94), dict(flat_qual=94), dict(gap_qual=94), dict(n_sites=5001), dict(reference_len=39))
-READ_ACCEPTED = (dict(batch=1), dict(batch=65535), dict(max_query_len=1), dict(max_query_len=8192), dict(max_ops=1), dict(max_ops=65535 + 8192),
-                 dict(reference_len=40), dict(reference_len=2 ** 26), dict(reference_len=2 ** 26, n_sites=2 ** 26), dict(min_qual=0), dict(min_qual=93),
-                 dict(flat_qual=0), dict(flat_qual=93), dict(gap_qual=0), dict(gap_qual=93), dict(ops_stride=0), dict(n_sites=1), dict(n_sites=5000),
-                 dict(qual=FAKE, qual_stride=400), dict(keep=FAKE), dict(cap=FAKE), dict(bad=FAKE))
+    assert list(LINKS.defaults)[:20] == [n for n in evidence[:21] if n != "weights_host"]    # and pileup_evidence's qualities
 
 
 def test_phase_links_rejects_on_the_host_in_order(lib):
-    _both_sides(_links, lib, "ops", shape=READ_SHAPE + (dict(reach=0), dict(reach=-1)), unsupported=READ_UNSUPPORTED + (dict(reach=9),),
-                accepted=READ_ACCEPTED + (dict(reach=1), dict(reach=8)))
-    for name in ("ops", "ops_len", "lo", "ref_lengths", "strand", "query", "query_lengths", "site_of", "alleles", "links", "observed", "used"):
-        assert _links(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _links(lib, batch=0, reach=9, ops=None) == WN_ERR_BAD_SHAPE                          # the order: shape, unsupported, NULL
-    assert _links(lib, reach=0, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
-    assert _links(lib, reach=9, ops=None) == WN_ERR_UNSUPPORTED
+    LINKS.rejects(lib, "ops", shape=SITES_SHAPE + (dict(reach=0), dict(reach=-1)), unsupported=SITES_UNSUPPORTED + (dict(reach=9),),
+                  accepted=SITES_ACCEPTED + (dict(reach=1), dict(reach=8)), required=SITES_REQUIRED + ("links", "observed", "used"))
+    assert LINKS(lib, batch=0, reach=9, ops=None) == WN_ERR_BAD_SHAPE                           # the order: shape, unsupported, NULL
+    assert LINKS(lib, reach=0, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
+    assert LINKS(lib, reach=9, ops=None) == WN_ERR_UNSUPPORTED
 
 
 def test_haplotag_rejects_on_the_host_in_order(lib):
-    _both_sides(_tag, lib, "ops", shape=READ_SHAPE, unsupported=READ_UNSUPPORTED, accepted=READ_ACCEPTED)
-    for name in ("ops", "ops_len", "lo", "ref_lengths", "strand", "query", "query_lengths", "site_of", "alleles", "pos", "root", "parity", "set_size",
-                 "hp", "ps", "weight", "n_observed"):
-        assert _tag(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _tag(lib, n_sites=0, gap_qual=94, ops=None) == WN_ERR_BAD_SHAPE
-    assert _tag(lib, n_sites=5001, ops=None) == WN_ERR_UNSUPPORTED
+    TAG.rejects(lib, "ops", shape=SITES_SHAPE, unsupported=SITES_UNSUPPORTED, accepted=SITES_ACCEPTED,
+                required=SITES_REQUIRED + ("pos", "root", "parity", "set_size", "hp", "ps", "weight", "n_observed"))
+    assert TAG(lib, n_sites=0, gap_qual=94, ops=None) == WN_ERR_BAD_SHAPE
+    assert TAG(lib, n_sites=5001, ops=None) == WN_ERR_UNSUPPORTED
 
 
 def test_phase_chain_rejects_on_the_host_in_order(lib):
-    _both_sides(_chain, lib, "links", shape=(dict(n_sites=0), dict(n_sites=-1), dict(reach=0), dict(min_margin=-1)),
-                unsupported=(dict(n_sites=2 ** 26 + 1), dict(reach=9)),
-                accepted=(dict(n_sites=1), dict(n_sites=2 ** 26), dict(reach=1), dict(reach=8), dict(min_margin=0), dict(min_margin=2 ** 31 - 1)))
-    for name in ("links", "pos", "parent", "flip", "margin", "root", "parity", "ps", "set_size", "work"):
-        assert _chain(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _chain(lib, n_sites=0, reach=9, links=None) == WN_ERR_BAD_SHAPE
-    assert _chain(lib, reach=9, links=None) == WN_ERR_UNSUPPORTED
-
-
-def _alignment(B=2, n=30):
-    import wavenet_speech_amd as W
-    return W.PairwiseAlignment(None, None, None, None, None, torch.ones(B, n, dtype=torch.uint8), torch.full((B,), n, dtype=torch.int32))
+    CHAIN.rejects(lib, "links", shape=(dict(n_sites=0), dict(n_sites=-1), dict(reach=0), dict(min_margin=-1)),
+                  unsupported=(dict(n_sites=2 ** 26 + 1), dict(reach=9)),
+                  accepted=(dict(n_sites=1), dict(n_sites=2 ** 26), dict(reach=1), dict(reach=8), dict(min_margin=0), dict(min_margin=2 ** 31 - 1)),
+                  required=("links", "pos", "parent", "flip", "margin", "root", "parity", "ps", "set_size", "work"))
+    assert CHAIN(lib, n_sites=0, reach=9, links=None) == WN_ERR_BAD_SHAPE
+    assert CHAIN(lib, reach=9, links=None) == WN_ERR_UNSUPPORTED
 
 
 def _host_sites(S=3, R=100):
@@ -126,7 +73,7 @@ def test_python_surface_refusals():
     import wavenet_speech_amd as W
     sites = _host_sites()
     query, n = torch.ones(2, 30, dtype=torch.int32), [30, 30]
-    args = dict(alignment=_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, sites=sites)
+    args = dict(alignment=host_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, sites=sites)
     phasing = W.Phasing(*[torch.zeros(3, dtype=d) for d in (torch.int32, torch.uint8, torch.int32, torch.int32, torch.uint8, torch.int32, torch.int32)])
     for fn, extra, what in ((W.phase_links, {}, "phase_links"), (W.haplotag, dict(phasing=phasing), "haplotag")):
         args_fn = dict(args, **extra)

@@ -5,123 +5,68 @@ Python surface: the refusals, "no CPU fallback", ReadMapping.window, variant_rec
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+from tests.abi_util import FAKE, READ_ACCEPTED, READ_BATCH, READ_REQUIRED, READ_SHAPE, READ_UNSUPPORTED, WN_ERR_BAD_SHAPE, WN_ERR_NULL, \
+    WN_ERR_UNSUPPORTED, Entry, host_alignment
+from tests.abi_util import lib  # noqa: F401
 
-PILEUP = ["ops", "ops_stride", "ops_len", "lo", "ref_lengths", "strand", "query", "query_stride", "query_lengths", "qual", "qual_stride", "keep",
-          "batch", "max_query_len", "max_ops", "reference_len", "min_qual", "max_ins", "counts", "ins_lengths", "ins_bases", "used", "bad",
-          "stream"]
-CALL = ["counts", "ins_lengths", "ins_bases", "reference", "reference_len", "max_ins", "min_depth", "num", "den", "call", "ins_len", "ins_out",
-        "flags", "alt_count", "tile_offsets", "total", "stream"]
-EMIT = ["call", "ins_len", "ins_out", "tile_offsets", "reference_len", "max_ins", "capacity", "offsets", "consensus", "stream"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+PILEUP = Entry("wn_pileup", dict(READ_BATCH, min_qual=0, max_ins=4, counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE, used=FAKE, bad=None, stream=None))
+CALL = Entry("wn_consensus_call", dict(counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE, reference=FAKE, reference_len=5000, max_ins=4, min_depth=3,
+                                       num=1, den=2, call=FAKE, ins_len=FAKE, ins_out=FAKE, flags=FAKE, alt_count=FAKE, tile_offsets=FAKE,
+                                       total=FAKE, stream=None))
+EMIT = Entry("wn_consensus_emit", dict(call=FAKE, ins_len=FAKE, ins_out=FAKE, tile_offsets=FAKE, reference_len=5000, max_ins=4, capacity=5000,
+                                       offsets=FAKE, consensus=FAKE, stream=None))
 
 
 def test_symbols_are_exported(lib):
     from wavenet_speech_amd import _lib
-    for name in ("wn_pileup", "wn_consensus_call", "wn_consensus_emit"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    for entry in (PILEUP, CALL, EMIT):
+        entry.check_exported(lib)
     assert "wn_pileup_workspace_bytes" not in _lib.SIGNATURES        # no workspace is needed
-    assert lib.wn_version() == 300                                   # additive entry points
 
 
 def test_signature_rows_match_the_header():
-    check_row("wn_pileup", count=24, opaque=True)
-    check_row("wn_consensus_call", count=17, opaque=True)
-    check_row("wn_consensus_emit", count=10, opaque=True)
-    assert header_names("wn_pileup") == PILEUP and header_names("wn_consensus_call") == CALL and header_names("wn_consensus_emit") == EMIT
-
-
-def _call(fn, names, defaults, kw):
-    assert set(kw) <= set(defaults), kw
-    a = dict(defaults, **kw)
-    return fn(*[a[n] for n in names])
-
-
-def _pileup(lib, **kw):
-    return _call(lib.wn_pileup, PILEUP, dict(ops=FAKE, ops_stride=900, ops_len=FAKE, lo=FAKE, ref_lengths=FAKE, strand=FAKE, query=FAKE,
-                                             query_stride=400, query_lengths=FAKE, qual=None, qual_stride=0, keep=None, batch=2, max_query_len=400,
-                                             max_ops=900, reference_len=5000, min_qual=0, max_ins=4, counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE,
-                                             used=FAKE, bad=None, stream=None), kw)
-
-
-def _consensus_call(lib, **kw):
-    return _call(lib.wn_consensus_call, CALL, dict(counts=FAKE, ins_lengths=FAKE, ins_bases=FAKE, reference=FAKE, reference_len=5000, max_ins=4,
-                                                   min_depth=3, num=1, den=2, call=FAKE, ins_len=FAKE, ins_out=FAKE, flags=FAKE, alt_count=FAKE,
-                                                   tile_offsets=FAKE, total=FAKE, stream=None), kw)
-
-
-def _consensus_emit(lib, **kw):
-    return _call(lib.wn_consensus_emit, EMIT, dict(call=FAKE, ins_len=FAKE, ins_out=FAKE, tile_offsets=FAKE, reference_len=5000, max_ins=4,
-                                                   capacity=5000, offsets=FAKE, consensus=FAKE, stream=None), kw)
-
-
-def _both_sides(call, lib, null, shape, unsupported, accepted):
-    """every accepted call goes on to the NULL check (`null`=None): nothing is ever launched"""
-    for kw in shape:
-        assert call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in unsupported:
-        assert call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in accepted:
-        assert call(lib, **dict(kw, **{null: None})) == WN_ERR_NULL, kw
+    for entry in (PILEUP, CALL, EMIT):                               # 24, 17 and 10 arguments
+        entry.check_declared()
 
 
 def test_pileup_rejects_on_the_host_in_order(lib):
-    _both_sides(_pileup, lib, "ops",
-                shape=(dict(batch=0), dict(batch=-1), dict(max_query_len=0), dict(max_ops=0), dict(reference_len=0), dict(ops_stride=-1),
-                       dict(query_stride=-1), dict(qual_stride=-1), dict(min_qual=-1), dict(max_ins=-1)),
-                unsupported=(dict(batch=65536), dict(max_query_len=8193), dict(max_ops=65535 + 8192 + 1), dict(reference_len=2 ** 26 + 1),
-                             dict(min_qual=94), dict(max_ins=9)),
-                accepted=(dict(batch=1), dict(batch=65535), dict(max_query_len=1), dict(max_query_len=8192), dict(max_ops=1),
-                          dict(max_ops=65535 + 8192), dict(reference_len=1), dict(reference_len=2 ** 26), dict(min_qual=0), dict(min_qual=93),
-                          dict(max_ins=0), dict(max_ins=8), dict(ops_stride=0), dict(qual=FAKE, qual_stride=400), dict(keep=FAKE), dict(bad=FAKE)))
-    for name in ("ops", "ops_len", "lo", "ref_lengths", "strand", "query", "query_lengths", "counts", "ins_lengths", "ins_bases", "used"):
-        assert _pileup(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _pileup(lib, max_ins=0, ins_bases=None, ops=None) == WN_ERR_NULL          # reached the NULL check: no table is needed there
-    assert _pileup(lib, batch=0, max_ins=9, ops=None) == WN_ERR_BAD_SHAPE            # the order: shape, then unsupported, then NULL
-    assert _pileup(lib, min_qual=-1, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
-    assert _pileup(lib, max_ins=9, ops=None) == WN_ERR_UNSUPPORTED
+    PILEUP.rejects(lib, "ops", shape=READ_SHAPE + (dict(max_ins=-1),), unsupported=READ_UNSUPPORTED + (dict(max_ins=9),),
+                   accepted=READ_ACCEPTED + (dict(reference_len=1), dict(max_ins=0), dict(max_ins=8)),
+                   required=READ_REQUIRED + ("counts", "ins_lengths", "ins_bases", "used"))
+    assert PILEUP(lib, max_ins=0, ins_bases=None, ops=None) == WN_ERR_NULL          # reached the NULL check: no table is needed there
+    assert PILEUP(lib, batch=0, max_ins=9, ops=None) == WN_ERR_BAD_SHAPE            # the order: shape, then unsupported, then NULL
+    assert PILEUP(lib, min_qual=-1, reference_len=2 ** 26 + 1) == WN_ERR_BAD_SHAPE
+    assert PILEUP(lib, max_ins=9, ops=None) == WN_ERR_UNSUPPORTED
 
 
 def test_consensus_call_rejects_on_the_host_in_order(lib):
-    _both_sides(_consensus_call, lib, "counts",
-                shape=(dict(reference_len=0), dict(reference_len=-1), dict(max_ins=-1), dict(min_depth=0), dict(num=-1), dict(den=0)),
-                unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9), dict(den=2 ** 15 + 1), dict(num=3, den=2)),
-                accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(min_depth=1),
-                          dict(min_depth=2 ** 31 - 1), dict(num=0), dict(num=2, den=2), dict(den=1, num=1), dict(den=2 ** 15)))
-    for name in ("counts", "ins_lengths", "ins_bases", "reference", "call", "ins_len", "ins_out", "flags", "alt_count", "tile_offsets", "total"):
-        assert _consensus_call(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _consensus_call(lib, max_ins=0, ins_bases=None, ins_out=None, counts=None) == WN_ERR_NULL
-    assert _consensus_call(lib, min_depth=0, max_ins=9, counts=None) == WN_ERR_BAD_SHAPE
-    assert _consensus_call(lib, max_ins=9, counts=None) == WN_ERR_UNSUPPORTED
+    CALL.rejects(lib, "counts",
+                 shape=(dict(reference_len=0), dict(reference_len=-1), dict(max_ins=-1), dict(min_depth=0), dict(num=-1), dict(den=0)),
+                 unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9), dict(den=2 ** 15 + 1), dict(num=3, den=2)),
+                 accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(min_depth=1),
+                           dict(min_depth=2 ** 31 - 1), dict(num=0), dict(num=2, den=2), dict(den=1, num=1), dict(den=2 ** 15)),
+                 required=("counts", "ins_lengths", "ins_bases", "reference", "call", "ins_len", "ins_out", "flags", "alt_count", "tile_offsets",
+                           "total"))
+    assert CALL(lib, max_ins=0, ins_bases=None, ins_out=None, counts=None) == WN_ERR_NULL
+    assert CALL(lib, min_depth=0, max_ins=9, counts=None) == WN_ERR_BAD_SHAPE
+    assert CALL(lib, max_ins=9, counts=None) == WN_ERR_UNSUPPORTED
 
 
 def test_consensus_emit_rejects_on_the_host_in_order(lib):
-    _both_sides(_consensus_emit, lib, "call",
-                shape=(dict(reference_len=0), dict(max_ins=-1), dict(capacity=-1)),
-                unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9)),
-                accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(capacity=0),
-                          dict(capacity=2 ** 31 - 1)))
-    for name in ("call", "ins_len", "ins_out", "tile_offsets", "offsets", "consensus"):
-        assert _consensus_emit(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _consensus_emit(lib, max_ins=0, ins_out=None, capacity=0, consensus=None, call=None) == WN_ERR_NULL
-    assert _consensus_emit(lib, capacity=-1, max_ins=9, call=None) == WN_ERR_BAD_SHAPE
-    assert _consensus_emit(lib, max_ins=9, call=None) == WN_ERR_UNSUPPORTED
-
-
-def _alignment(B=2, n=30):
-    import wavenet_speech_amd as W
-    return W.PairwiseAlignment(None, None, None, None, None, torch.ones(B, n, dtype=torch.uint8), torch.full((B,), n, dtype=torch.int32))
+    EMIT.rejects(lib, "call", shape=(dict(reference_len=0), dict(max_ins=-1), dict(capacity=-1)),
+                 unsupported=(dict(reference_len=2 ** 26 + 1), dict(max_ins=9)),
+                 accepted=(dict(reference_len=1), dict(reference_len=2 ** 26), dict(max_ins=0), dict(max_ins=8), dict(capacity=0),
+                           dict(capacity=2 ** 31 - 1)),
+                 required=("call", "ins_len", "ins_out", "tile_offsets", "offsets", "consensus"))
+    assert EMIT(lib, max_ins=0, ins_out=None, capacity=0, consensus=None, call=None) == WN_ERR_NULL
+    assert EMIT(lib, capacity=-1, max_ins=9, call=None) == WN_ERR_BAD_SHAPE
+    assert EMIT(lib, max_ins=9, call=None) == WN_ERR_UNSUPPORTED
 
 
 def test_python_surface_refusals():
     import wavenet_speech_amd as W
     query, n = torch.ones(2, 30, dtype=torch.int32), [30, 30]
-    args = dict(alignment=_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, R=100)
+    args = dict(alignment=host_alignment(), lo=[0, 0], ref_lengths=[30, 30], strand=[0, 1], query=query, query_lengths=n, R=100)
     with pytest.raises(ValueError, match="wavenet_speech_amd.pileup: alignment must be a PairwiseAlignment with ops"):
         W.pileup(**dict(args, alignment=W.PairwiseAlignment(None, None, None, None, None, None, None)))
     with pytest.raises(RuntimeError, match="wavenet_speech_amd.pileup: alignment.ops must be a GPU tensor \\(there is no CPU fallback\\)"):

@@ -8,111 +8,65 @@ import numpy as np
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, check_row, header_names
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, Entry
+from tests.abi_util import lib  # noqa: F401
 
-MINIMIZERS = ["labels", "labels_stride", "lengths", "batch", "max_len", "k", "w", "chunk", "code", "flag", "bad", "stream"]
-SEEDS = ["code", "flag", "lengths", "index", "n_index", "batch", "max_len", "k", "max_occ", "anchors_per_read", "keys", "n_minimizers",
-         "n_anchors", "truncated", "bad", "stream"]
-CHAIN = ["keys", "n_anchors", "lengths", "batch", "max_len", "anchors_per_read", "k", "h", "max_dist", "bandwidth", "gap_base", "gap_log",
-         "result", "f", "pred", "bad", "stream"]
+MINIMIZERS = Entry("wn_minimizers", dict(labels=FAKE, labels_stride=400, lengths=FAKE, batch=2, max_len=400, k=15, w=10, chunk=0, code=FAKE,
+                                         flag=FAKE, bad=None, stream=None))
+SEEDS = Entry("wn_read_seeds", dict(code=FAKE, flag=FAKE, lengths=FAKE, index=FAKE, n_index=1000, batch=2, max_len=400, k=15, max_occ=8,
+                                    anchors_per_read=4096, keys=FAKE, n_minimizers=FAKE, n_anchors=FAKE, truncated=FAKE, bad=None, stream=None))
+CHAIN = Entry("wn_chain", dict(keys=FAKE, n_anchors=FAKE, lengths=FAKE, batch=2, max_len=400, anchors_per_read=4096, k=15, h=64, max_dist=5000,
+                               bandwidth=500, gap_base=2, gap_log=8, result=FAKE, f=None, pred=None, bad=None, stream=None))
 INT_MIN = -2 ** 31
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
 
 
 def test_symbols_are_exported(lib):
     from wavenet_speech_amd import _lib
-    for name in ("wn_minimizers", "wn_read_seeds", "wn_chain"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    for entry in (MINIMIZERS, SEEDS, CHAIN):
+        entry.check_exported(lib)
     assert "wn_chain_workspace_bytes" not in _lib.SIGNATURES         # no workspace is needed: f and pred are outputs
-    assert lib.wn_version() == 300                                   # additive entry points
 
 
 def test_signature_rows_match_the_header():
-    check_row("wn_minimizers", count=12, opaque=True)
-    check_row("wn_read_seeds", count=16, opaque=True)
-    check_row("wn_chain", count=17, opaque=True)
-    assert header_names("wn_minimizers") == MINIMIZERS and header_names("wn_read_seeds") == SEEDS and header_names("wn_chain") == CHAIN
-
-
-def _call(fn, names, defaults, kw):
-    assert set(kw) <= set(defaults), kw
-    a = dict(defaults, **kw)
-    return fn(*[a[n] for n in names])
-
-
-def _minimizers(lib, **kw):
-    return _call(lib.wn_minimizers, MINIMIZERS, dict(labels=FAKE, labels_stride=400, lengths=FAKE, batch=2, max_len=400, k=15, w=10, chunk=0,
-                                                     code=FAKE, flag=FAKE, bad=None, stream=None), kw)
-
-
-def _seeds(lib, **kw):
-    return _call(lib.wn_read_seeds, SEEDS, dict(code=FAKE, flag=FAKE, lengths=FAKE, index=FAKE, n_index=1000, batch=2, max_len=400, k=15, max_occ=8,
-                                                anchors_per_read=4096, keys=FAKE, n_minimizers=FAKE, n_anchors=FAKE, truncated=FAKE, bad=None,
-                                                stream=None), kw)
-
-
-def _chain(lib, **kw):
-    return _call(lib.wn_chain, CHAIN, dict(keys=FAKE, n_anchors=FAKE, lengths=FAKE, batch=2, max_len=400, anchors_per_read=4096, k=15, h=64,
-                                           max_dist=5000, bandwidth=500, gap_base=2, gap_log=8, result=FAKE, f=None, pred=None, bad=None,
-                                           stream=None), kw)
-
-
-def _both_sides(call, lib, null, shape, unsupported, accepted):
-    """every accepted call goes on to the NULL check (`null`=None): nothing is ever launched"""
-    for kw in shape:
-        assert call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in unsupported:
-        assert call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in accepted:
-        assert call(lib, **dict(kw, **{null: None})) == WN_ERR_NULL, kw
+    for entry in (MINIMIZERS, SEEDS, CHAIN):                         # 12, 16 and 17 arguments
+        entry.check_declared()
 
 
 def test_minimizers_rejects_on_the_host_in_order(lib):
-    _both_sides(_minimizers, lib, "labels",
-                shape=(dict(batch=0), dict(batch=-1), dict(max_len=0), dict(labels_stride=-1), dict(chunk=-1)),
-                unsupported=(dict(batch=65536), dict(max_len=2 ** 26 + 1), dict(k=0), dict(k=17), dict(w=0), dict(w=65), dict(chunk=2049)),
-                accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=2 ** 26), dict(k=1), dict(k=16), dict(w=1), dict(w=64),
-                          dict(chunk=0), dict(chunk=1), dict(chunk=2048), dict(labels_stride=0)))
-    for name in ("labels", "lengths", "code", "flag"):
-        assert _minimizers(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _minimizers(lib, batch=0, k=17, labels=None) == WN_ERR_BAD_SHAPE          # the order: shape, then unsupported, then NULL
-    assert _minimizers(lib, chunk=-1, w=65, code=None) == WN_ERR_BAD_SHAPE
-    assert _minimizers(lib, k=17, labels=None) == WN_ERR_UNSUPPORTED
+    MINIMIZERS.rejects(lib, "labels", shape=(dict(batch=0), dict(batch=-1), dict(max_len=0), dict(labels_stride=-1), dict(chunk=-1)),
+                       unsupported=(dict(batch=65536), dict(max_len=2 ** 26 + 1), dict(k=0), dict(k=17), dict(w=0), dict(w=65), dict(chunk=2049)),
+                       accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=2 ** 26), dict(k=1), dict(k=16), dict(w=1),
+                                 dict(w=64), dict(chunk=0), dict(chunk=1), dict(chunk=2048), dict(labels_stride=0)),
+                       required=("labels", "lengths", "code", "flag"))
+    assert MINIMIZERS(lib, batch=0, k=17, labels=None) == WN_ERR_BAD_SHAPE          # the order: shape, then unsupported, then NULL
+    assert MINIMIZERS(lib, chunk=-1, w=65, code=None) == WN_ERR_BAD_SHAPE
+    assert MINIMIZERS(lib, k=17, labels=None) == WN_ERR_UNSUPPORTED
 
 
 def test_read_seeds_rejects_on_the_host_in_order(lib):
-    _both_sides(_seeds, lib, "code",
-                shape=(dict(batch=0), dict(batch=-1), dict(max_len=0), dict(n_index=-1)),
-                unsupported=(dict(batch=65536), dict(max_len=65536), dict(n_index=2 ** 26 + 1), dict(k=0), dict(k=17), dict(max_occ=0),
-                             dict(max_occ=65), dict(anchors_per_read=0), dict(anchors_per_read=32769)),
-                accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=65535), dict(n_index=0), dict(n_index=2 ** 26),
-                          dict(k=1), dict(k=16), dict(max_occ=1), dict(max_occ=64), dict(anchors_per_read=1), dict(anchors_per_read=32768)))
-    for name in ("code", "flag", "lengths", "index", "keys", "n_minimizers", "n_anchors", "truncated"):
-        assert _seeds(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _seeds(lib, n_index=-1, max_occ=65, keys=None) == WN_ERR_BAD_SHAPE
-    assert _seeds(lib, max_occ=65, keys=None) == WN_ERR_UNSUPPORTED
+    SEEDS.rejects(lib, "code", shape=(dict(batch=0), dict(batch=-1), dict(max_len=0), dict(n_index=-1)),
+                  unsupported=(dict(batch=65536), dict(max_len=65536), dict(n_index=2 ** 26 + 1), dict(k=0), dict(k=17), dict(max_occ=0),
+                               dict(max_occ=65), dict(anchors_per_read=0), dict(anchors_per_read=32769)),
+                  accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=65535), dict(n_index=0), dict(n_index=2 ** 26),
+                            dict(k=1), dict(k=16), dict(max_occ=1), dict(max_occ=64), dict(anchors_per_read=1), dict(anchors_per_read=32768)),
+                  required=("code", "flag", "lengths", "index", "keys", "n_minimizers", "n_anchors", "truncated"))
+    assert SEEDS(lib, n_index=-1, max_occ=65, keys=None) == WN_ERR_BAD_SHAPE
+    assert SEEDS(lib, max_occ=65, keys=None) == WN_ERR_UNSUPPORTED
 
 
 def test_chain_rejects_on_the_host_in_order(lib):
-    _both_sides(_chain, lib, "keys",
-                shape=(dict(batch=0), dict(batch=-1), dict(max_len=0)),
-                unsupported=(dict(batch=65536), dict(max_len=65536), dict(anchors_per_read=0), dict(anchors_per_read=32769), dict(k=0), dict(k=17),
-                             dict(h=0), dict(h=1025), dict(max_dist=0), dict(max_dist=2 ** 26 + 1), dict(bandwidth=0), dict(bandwidth=2 ** 26 + 1),
-                             dict(gap_base=-1), dict(gap_base=1025), dict(gap_log=-1), dict(gap_log=1025)),
-                accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=65535), dict(anchors_per_read=1),
-                          dict(anchors_per_read=32768), dict(k=1), dict(k=16), dict(h=1), dict(h=1024), dict(max_dist=1), dict(max_dist=2 ** 26),
-                          dict(bandwidth=1), dict(bandwidth=2 ** 26), dict(gap_base=0), dict(gap_base=1024), dict(gap_log=0), dict(gap_log=1024),
-                          dict(f=FAKE, pred=FAKE)))
-    for name in ("keys", "n_anchors", "lengths", "result"):
-        assert _chain(lib, **{name: None}) == WN_ERR_NULL, name
-    assert _chain(lib, f=FAKE) == WN_ERR_NULL and _chain(lib, pred=FAKE) == WN_ERR_NULL        # the table comes whole or not at all
-    assert _chain(lib, batch=0, h=1025, keys=None) == WN_ERR_BAD_SHAPE
-    assert _chain(lib, h=1025, keys=None) == WN_ERR_UNSUPPORTED
+    CHAIN.rejects(lib, "keys", shape=(dict(batch=0), dict(batch=-1), dict(max_len=0)),
+                  unsupported=(dict(batch=65536), dict(max_len=65536), dict(anchors_per_read=0), dict(anchors_per_read=32769), dict(k=0), dict(k=17),
+                               dict(h=0), dict(h=1025), dict(max_dist=0), dict(max_dist=2 ** 26 + 1), dict(bandwidth=0), dict(bandwidth=2 ** 26 + 1),
+                               dict(gap_base=-1), dict(gap_base=1025), dict(gap_log=-1), dict(gap_log=1025)),
+                  accepted=(dict(batch=1), dict(batch=65535), dict(max_len=1), dict(max_len=65535), dict(anchors_per_read=1),
+                            dict(anchors_per_read=32768), dict(k=1), dict(k=16), dict(h=1), dict(h=1024), dict(max_dist=1), dict(max_dist=2 ** 26),
+                            dict(bandwidth=1), dict(bandwidth=2 ** 26), dict(gap_base=0), dict(gap_base=1024), dict(gap_log=0), dict(gap_log=1024),
+                            dict(f=FAKE, pred=FAKE)),
+                  required=("keys", "n_anchors", "lengths", "result"))
+    assert CHAIN(lib, f=FAKE) == WN_ERR_NULL and CHAIN(lib, pred=FAKE) == WN_ERR_NULL          # the table comes whole or not at all
+    assert CHAIN(lib, batch=0, h=1025, keys=None) == WN_ERR_BAD_SHAPE
+    assert CHAIN(lib, h=1025, keys=None) == WN_ERR_UNSUPPORTED
 
 
 def test_anchors_from_table_packs_and_sorts():

@@ -5,34 +5,26 @@ import ctypes
 import os
 import re
 
-import pytest
-
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row
+from tests.abi_util import FAKE, ROOT, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
 ODD = ctypes.c_void_p((1 << 20) + 8)     # 8-byte but not 16-byte aligned
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("wn_read_select_workspace_bytes", "wn_read_select")
 EDGE = 2 ** 31 - 1024                    # the first ld that is refused
 BIG = 1 << 40                            # a workspace size that is always enough
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+SELECT = Entry("wn_read_select", dict(signal=FAKE, signal_is_int16=0, batch=2, ld=100, signal_lengths=FAKE, ranks=FAKE, K=2, center=None, out=FAKE,
+                                      workspace=FAKE, workspace_bytes=BIG, bad=None, stream=None))
+SIZE = Entry("wn_read_select_workspace_bytes", dict(batch=2, K=2, signal_is_int16=0, has_center=0))
+REQUIRED = ("signal", "signal_lengths", "ranks", "out", "workspace")       # center and bad are optional (NULL in every call here)
 
 
 def test_select_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in NAMES:
-        assert name in _lib.SIGNATURES
-        assert hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # additive entry points
+    SELECT.check_exported(lib)
+    SIZE.check_exported(lib)
 
 
 def test_signature_table_matches_the_header():
-    for name in NAMES:
-        check_row(name, opaque=True)
+    SELECT.check_declared()                                          # 13 arguments
+    SIZE.check_declared()                                            # 4
 
 
 def test_tile_matches_the_kernel():
@@ -57,46 +49,33 @@ def test_workspace_bytes(lib):
         assert ws(batch, K, 1, 0) == 0 and ws(batch, K, 0, 1) == 0
 
 
-def _select(lib, signal=FAKE, is_int16=0, batch=2, ld=100, signal_lengths=FAKE, ranks=FAKE, K=2, center=None, out=FAKE, workspace=FAKE,
-            workspace_bytes=BIG, bad=None):
-    return lib.wn_read_select(signal, is_int16, batch, ld, signal_lengths, ranks, K, center, out, workspace, workspace_bytes, bad, None)
-
-
 def test_read_select_rejects_on_the_host(lib):
-    for kw in (dict(batch=0), dict(batch=-1), dict(ld=0), dict(ld=-7), dict(K=0), dict(K=-3)):
-        assert _select(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    assert _select(lib, K=9) == WN_ERR_UNSUPPORTED
-    assert _select(lib, batch=65536) == WN_ERR_UNSUPPORTED
-    assert _select(lib, ld=EDGE) == WN_ERR_UNSUPPORTED
-    # the accepted side of each edge goes on to the pointer checks
-    assert _select(lib, K=8, out=None) == WN_ERR_NULL
-    assert _select(lib, K=1, out=None) == WN_ERR_NULL
-    assert _select(lib, batch=65535, out=None) == WN_ERR_NULL
-    assert _select(lib, batch=1, ld=1, out=None) == WN_ERR_NULL
-    assert _select(lib, batch=1, ld=EDGE - 1, out=None) == WN_ERR_NULL
-    # a launch stays below 2^32 threads: 256 * ceil(ld / 8192) * batch
-    assert _select(lib, ld=8192 * 256, batch=65535, out=None) == WN_ERR_NULL                            # 2^32 - 2^16
-    assert _select(lib, ld=8192 * 512, batch=32768) == WN_ERR_UNSUPPORTED                               # 2^32
-    assert _select(lib, ld=8192 * 512, batch=32767, out=None) == WN_ERR_NULL
-    assert _select(lib, ld=8192 * 256 + 1, batch=65535) == WN_ERR_UNSUPPORTED
-    for is_int16 in (0, 1):
-        for name in ("signal", "signal_lengths", "ranks", "out", "workspace"):       # center and bad are optional (NULL in every call here)
-            assert _select(lib, is_int16=is_int16, **{name: None}) == WN_ERR_NULL, name
+    SELECT.rejects(lib, "out", shape=(dict(batch=0), dict(batch=-1), dict(ld=0), dict(ld=-7), dict(K=0), dict(K=-3)),
+                   unsupported=(dict(K=9), dict(batch=65536), dict(ld=EDGE),
+                                # a launch stays below 2^32 threads: 256 * ceil(ld / 8192) * batch
+                                dict(ld=8192 * 512, batch=32768),                              # 2^32
+                                dict(ld=8192 * 256 + 1, batch=65535)),
+                   accepted=(dict(K=8), dict(K=1), dict(batch=65535), dict(batch=1, ld=1), dict(batch=1, ld=EDGE - 1),
+                             dict(ld=8192 * 256, batch=65535),                                 # 2^32 - 2^16
+                             dict(ld=8192 * 512, batch=32767)),
+                   required=REQUIRED)
+    for name in REQUIRED:
+        assert SELECT(lib, signal_is_int16=1, **{name: None}) == WN_ERR_NULL, name
     # the workspace: 16-byte aligned and at least wn_read_select_workspace_bytes
-    assert _select(lib, workspace=ODD) == WN_ERR_WORKSPACE
-    assert _select(lib, workspace=ctypes.c_void_p((1 << 20) + 4)) == WN_ERR_WORKSPACE
+    assert SELECT(lib, workspace=ODD) == WN_ERR_WORKSPACE
+    assert SELECT(lib, workspace=ctypes.c_void_p((1 << 20) + 4)) == WN_ERR_WORKSPACE
     for is_int16 in (0, 1):
         for center in (None, FAKE):
-            need = lib.wn_read_select_workspace_bytes(2, 2, is_int16, int(center is not None))
-            assert _select(lib, is_int16=is_int16, center=center, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _select(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
+            need = SIZE(lib, signal_is_int16=is_int16, has_center=int(center is not None))
+            assert SELECT(lib, signal_is_int16=is_int16, center=center, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert SELECT(lib, workspace_bytes=0) == WN_ERR_WORKSPACE
     # a signal that is not aligned to its element could not be read 16 bytes at a time from any boundary
-    assert _select(lib, is_int16=1, signal=ctypes.c_void_p((1 << 20) + 1)) == WN_ERR_WORKSPACE
-    assert _select(lib, is_int16=0, signal=ctypes.c_void_p((1 << 20) + 2)) == WN_ERR_WORKSPACE
+    assert SELECT(lib, signal_is_int16=1, signal=ctypes.c_void_p((1 << 20) + 1)) == WN_ERR_WORKSPACE
+    assert SELECT(lib, signal_is_int16=0, signal=ctypes.c_void_p((1 << 20) + 2)) == WN_ERR_WORKSPACE
     # the order of the checks: shape, then unsupported, then NULL, then the workspace
-    assert _select(lib, K=0, batch=65536, ranks=None) == WN_ERR_BAD_SHAPE
-    assert _select(lib, batch=0, ld=EDGE, ranks=None) == WN_ERR_BAD_SHAPE
-    assert _select(lib, K=9, ranks=None, workspace=ODD) == WN_ERR_UNSUPPORTED
-    assert _select(lib, ld=EDGE, signal=None) == WN_ERR_UNSUPPORTED
-    assert _select(lib, ranks=None, workspace=ODD) == WN_ERR_NULL
-    assert _select(lib, ranks=None, workspace_bytes=0) == WN_ERR_NULL
+    assert SELECT(lib, K=0, batch=65536, ranks=None) == WN_ERR_BAD_SHAPE
+    assert SELECT(lib, batch=0, ld=EDGE, ranks=None) == WN_ERR_BAD_SHAPE
+    assert SELECT(lib, K=9, ranks=None, workspace=ODD) == WN_ERR_UNSUPPORTED
+    assert SELECT(lib, ld=EDGE, signal=None) == WN_ERR_UNSUPPORTED
+    assert SELECT(lib, ranks=None, workspace=ODD) == WN_ERR_NULL
+    assert SELECT(lib, ranks=None, workspace_bytes=0) == WN_ERR_NULL

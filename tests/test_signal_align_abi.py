@@ -8,43 +8,25 @@ from fractions import Fraction
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row, header_names
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry
+from tests.abi_util import lib  # noqa: F401
 
-NAME = "wn_signal_align"
-ARGS = ["signal", "signal_kind", "signal_stride", "signal_lengths", "scale_shift", "labels", "labels_stride", "label_lengths", "model",
-        "batch", "max_signal", "max_labels", "max_events", "k", "first", "frac_bits", "weight_shift", "max_cost", "band", "starts", "score",
-        "band_hits", "sample_state", "workspace", "workspace_bytes", "bad", "stream"]
-REQUIRED = ("signal", "signal_lengths", "labels", "label_lengths", "model", "starts", "score", "band_hits", "workspace")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+ALIGN = Entry("wn_signal_align", dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, labels=FAKE,
+                                      labels_stride=100, label_lengths=FAKE, model=FAKE, batch=2, max_signal=1000, max_labels=100, max_events=96,
+                                      k=5, first=0, frac_bits=12, weight_shift=40, max_cost=2 ** 31 - 1, band=64, starts=FAKE, score=FAKE,
+                                      band_hits=FAKE, sample_state=FAKE, workspace=FAKE, workspace_bytes=0, bad=None,
+                                      stream=None))                  # workspace_bytes 0: never launches
+SIZE = Entry("wn_signal_align_workspace_bytes", dict(batch=2, max_signal=1000, band=64))
 
 
 def test_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in (NAME, NAME + "_workspace_bytes"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # an additive entry point
+    ALIGN.check_exported(lib)
+    SIZE.check_exported(lib)
 
 
 def test_signature_rows_match_the_header():
-    for name, count in ((NAME, 27), (NAME + "_workspace_bytes", 3)):
-        check_row(name, count=count, opaque=True)
-    names = header_names(NAME)
-    assert names == ARGS
-
-
-def _call(lib, **kw):
-    a = dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, labels=FAKE, labels_stride=100,
-             label_lengths=FAKE, model=FAKE, batch=2, max_signal=1000, max_labels=100, max_events=96, k=5, first=0, frac_bits=12,
-             weight_shift=40, max_cost=2 ** 31 - 1, band=64, starts=FAKE, score=FAKE, band_hits=FAKE, sample_state=FAKE, workspace=FAKE,
-             workspace_bytes=0, bad=None, stream=None)                 # workspace_bytes 0: never launches
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_signal_align(*[a[n] for n in ARGS])
+    ALIGN.check_declared()                                           # 27 arguments
+    SIZE.check_declared()                                            # 3
 
 
 def test_workspace_size(lib):
@@ -58,40 +40,36 @@ def test_workspace_size(lib):
 
 
 def test_rejects_on_the_host_in_order(lib):
-    assert _call(lib) == WN_ERR_WORKSPACE                            # everything else about the default call is accepted
-    for kw in (dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(max_labels=0), dict(max_events=0),
-               dict(max_events=-1), dict(signal_stride=-1), dict(labels_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)):
-        assert _call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(k=0), dict(k=7), dict(first=-1), dict(first=9), dict(frac_bits=-1), dict(frac_bits=21), dict(weight_shift=15),
-               dict(weight_shift=64), dict(max_cost=0), dict(max_cost=-1), dict(band=0), dict(band=32), dict(band=96), dict(band=2112),
-               dict(band=-64), dict(batch=65536), dict(max_signal=2 ** 24 + 1), dict(max_events=2 ** 20 + 1)):
-        assert _call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    # the accepted side of each limit goes on to the pointer checks
-    for kw in (dict(k=1), dict(k=6), dict(first=0), dict(first=8), dict(frac_bits=0), dict(frac_bits=20), dict(weight_shift=16),
-               dict(weight_shift=63), dict(max_cost=1), dict(max_cost=2 ** 31 - 1), dict(band=64), dict(band=128), dict(band=576),
-               dict(band=2048), dict(batch=65535), dict(batch=1), dict(max_signal=2 ** 24), dict(max_events=2 ** 20), dict(signal_kind=1),
-               dict(signal_stride=0, labels_stride=0)):
-        assert _call(lib, signal=None, **kw) == WN_ERR_NULL, kw
-    for name in REQUIRED:
-        assert _call(lib, **{name: None}) == WN_ERR_NULL, name
+    assert ALIGN(lib) == WN_ERR_WORKSPACE                            # everything else about the default call is accepted
+    ALIGN.rejects(lib, "signal",
+                  shape=(dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(max_labels=0), dict(max_events=0),
+                         dict(max_events=-1), dict(signal_stride=-1), dict(labels_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)),
+                  unsupported=(dict(k=0), dict(k=7), dict(first=-1), dict(first=9), dict(frac_bits=-1), dict(frac_bits=21), dict(weight_shift=15),
+                               dict(weight_shift=64), dict(max_cost=0), dict(max_cost=-1), dict(band=0), dict(band=32), dict(band=96),
+                               dict(band=2112), dict(band=-64), dict(batch=65536), dict(max_signal=2 ** 24 + 1), dict(max_events=2 ** 20 + 1)),
+                  accepted=(dict(k=1), dict(k=6), dict(first=0), dict(first=8), dict(frac_bits=0), dict(frac_bits=20), dict(weight_shift=16),
+                            dict(weight_shift=63), dict(max_cost=1), dict(max_cost=2 ** 31 - 1), dict(band=64), dict(band=128), dict(band=576),
+                            dict(band=2048), dict(batch=65535), dict(batch=1), dict(max_signal=2 ** 24), dict(max_events=2 ** 20),
+                            dict(signal_kind=1), dict(signal_stride=0, labels_stride=0)),
+                  required=("signal", "signal_lengths", "labels", "label_lengths", "model", "starts", "score", "band_hits", "workspace"))
     for name in ("scale_shift", "sample_state", "bad"):              # optional
-        assert _call(lib, **{name: None}) == WN_ERR_WORKSPACE, name
+        assert ALIGN(lib, **{name: None}) == WN_ERR_WORKSPACE, name
     # the workspace: too small by one byte, misaligned, and a signal off its element size
-    need = lib.wn_signal_align_workspace_bytes(2, 1000, 64)
+    need = SIZE(lib)
     assert need == 16000
-    assert _call(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _call(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, band=128, workspace_bytes=need) == WN_ERR_WORKSPACE            # the size follows the band
+    assert ALIGN(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert ALIGN(lib, band=128, workspace_bytes=need) == WN_ERR_WORKSPACE            # the size follows the band
     # the order: shape, then unsupported, then NULL, then workspace
-    assert _call(lib, batch=0, k=7, signal=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, signal_kind=2, band=96, model=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, max_events=0, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, k=7, signal=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, weight_shift=64, score=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, batch=65536, workspace=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, model=None, workspace_bytes=0) == WN_ERR_NULL
+    assert ALIGN(lib, batch=0, k=7, signal=None) == WN_ERR_BAD_SHAPE
+    assert ALIGN(lib, signal_kind=2, band=96, model=None) == WN_ERR_BAD_SHAPE
+    assert ALIGN(lib, max_events=0, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
+    assert ALIGN(lib, k=7, signal=None) == WN_ERR_UNSUPPORTED
+    assert ALIGN(lib, weight_shift=64, score=None) == WN_ERR_UNSUPPORTED
+    assert ALIGN(lib, batch=65536, workspace=None) == WN_ERR_UNSUPPORTED
+    assert ALIGN(lib, model=None, workspace_bytes=0) == WN_ERR_NULL
 
 
 # ---- signal_model: the host-side integer table

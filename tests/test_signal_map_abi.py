@@ -7,34 +7,28 @@ import ctypes
 import pytest
 import torch
 
-from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, check_row, header_names, header_text
+from tests.abi_util import FAKE, WN_ERR_BAD_SHAPE, WN_ERR_NULL, WN_ERR_UNSUPPORTED, WN_ERR_WORKSPACE, Entry, header_text
+from tests.abi_util import lib  # noqa: F401
 
-NAME = "wn_signal_map"
-ARGS = ["signal", "signal_kind", "signal_stride", "signal_lengths", "scale_shift", "prepared", "ref_len", "k", "batch", "max_signal",
-        "frac_bits", "weight_shift", "max_cost", "strip_states", "score", "end", "start", "runner_up", "block_cost", "block_end", "end_cost",
-        "workspace", "workspace_bytes", "bad", "stream"]
-REQUIRED = ("signal", "signal_lengths", "prepared", "score", "end", "start", "runner_up", "block_cost", "block_end", "workspace")
-REF_ARGS = ["ref", "ref_len", "model", "k", "prepared", "prepared_bytes", "bad", "stream"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from wavenet_speech_amd import _lib
-    return _lib.load()
+MAP = Entry("wn_signal_map", dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, prepared=FAKE, ref_len=5000,
+                                  k=5, batch=2, max_signal=1000, frac_bits=12, weight_shift=40, max_cost=2 ** 31 - 1, strip_states=0, score=FAKE,
+                                  end=FAKE, start=FAKE, runner_up=FAKE, block_cost=FAKE, block_end=FAKE, end_cost=FAKE, workspace=FAKE,
+                                  workspace_bytes=0, bad=None, stream=None))         # workspace_bytes 0: never launches
+MAP_SIZE = Entry("wn_signal_map_workspace_bytes", dict(batch=2, max_signal=1000, ref_len=5000, k=5, strip_states=0))
+REFERENCE = Entry("wn_signal_map_reference", dict(ref=FAKE, ref_len=1000, model=FAKE, k=5, prepared=FAKE, prepared_bytes=0, bad=None,
+                                                  stream=None))      # prepared_bytes 0: never launches
+REFERENCE_SIZE = Entry("wn_signal_map_reference_bytes", dict(ref_len=1000, k=5))
 
 
 def test_symbols_are_exported(lib):
-    from wavenet_speech_amd import _lib
-    for name in (NAME, NAME + "_workspace_bytes", NAME + "_reference", NAME + "_reference_bytes"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.wn_version() == 300                                   # additive entry points
+    for entry in (MAP, MAP_SIZE, REFERENCE, REFERENCE_SIZE):
+        entry.check_exported(lib)
     assert "#define WN_MAP_GRANULE 64" in header_text()
 
 
 def test_signature_rows_match_the_header():
-    for name, count in ((NAME, 25), (NAME + "_workspace_bytes", 5), (NAME + "_reference", 8), (NAME + "_reference_bytes", 2)):
-        check_row(name, count=count, opaque=True)
-    assert header_names(NAME) == ARGS and header_names(NAME + "_reference") == REF_ARGS
+    for entry in (MAP, MAP_SIZE, REFERENCE, REFERENCE_SIZE):         # 25, 5, 8 and 2 arguments
+        entry.check_declared()
 
 
 def test_size_functions(lib):
@@ -56,80 +50,56 @@ def test_size_functions(lib):
     assert ws(2, 100, 1000, 5, 64) == ws(2, 100, 1000, 5, 0) == ws(2, 4096, 1000, 5, 576)                  # the strip tunes, it sizes nothing
 
 
-def _ref_call(lib, **kw):
-    a = dict(ref=FAKE, ref_len=1000, model=FAKE, k=5, prepared=FAKE, prepared_bytes=0, bad=None, stream=None)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_signal_map_reference(*[a[n] for n in REF_ARGS])
-
-
 def test_reference_rejects_on_the_host_in_order(lib):
-    assert _ref_call(lib) == WN_ERR_WORKSPACE                        # prepared_bytes 0: never launches
-    for kw in (dict(ref_len=0), dict(ref_len=-1), dict(ref_len=4), dict(ref_len=4, k=7)):
-        assert _ref_call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(k=0), dict(k=-1), dict(k=7), dict(ref_len=2 ** 26 + 1)):
-        assert _ref_call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    for kw in (dict(k=1), dict(k=6), dict(ref_len=5), dict(ref_len=2 ** 26), dict(ref_len=1, k=1)):
-        assert _ref_call(lib, ref=None, **kw) == WN_ERR_NULL, kw
-    for name in ("ref", "model", "prepared"):
-        assert _ref_call(lib, **{name: None}) == WN_ERR_NULL, name
-    need = lib.wn_signal_map_reference_bytes(1000, 5)
-    assert _ref_call(lib, prepared_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _ref_call(lib, prepared=ctypes.c_void_p((1 << 20) + 8), prepared_bytes=need) == WN_ERR_WORKSPACE
-    assert _ref_call(lib, ref_len=0, k=7, ref=None) == WN_ERR_BAD_SHAPE
-    assert _ref_call(lib, k=7, ref=None) == WN_ERR_UNSUPPORTED
-    assert _ref_call(lib, model=None, prepared_bytes=0) == WN_ERR_NULL
-
-
-def _call(lib, **kw):
-    a = dict(signal=FAKE, signal_kind=0, signal_stride=1000, signal_lengths=FAKE, scale_shift=FAKE, prepared=FAKE, ref_len=5000, k=5,
-             batch=2, max_signal=1000, frac_bits=12, weight_shift=40, max_cost=2 ** 31 - 1, strip_states=0, score=FAKE, end=FAKE,
-             start=FAKE, runner_up=FAKE, block_cost=FAKE, block_end=FAKE, end_cost=FAKE, workspace=FAKE, workspace_bytes=0, bad=None,
-             stream=None)                                            # workspace_bytes 0: never launches
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return lib.wn_signal_map(*[a[n] for n in ARGS])
+    assert REFERENCE(lib) == WN_ERR_WORKSPACE
+    REFERENCE.rejects(lib, "ref", shape=(dict(ref_len=0), dict(ref_len=-1), dict(ref_len=4), dict(ref_len=4, k=7)),
+                      unsupported=(dict(k=0), dict(k=-1), dict(k=7), dict(ref_len=2 ** 26 + 1)),
+                      accepted=(dict(k=1), dict(k=6), dict(ref_len=5), dict(ref_len=2 ** 26), dict(ref_len=1, k=1)),
+                      required=("ref", "model", "prepared"))
+    need = REFERENCE_SIZE(lib)
+    assert REFERENCE(lib, prepared_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert REFERENCE(lib, prepared=ctypes.c_void_p((1 << 20) + 8), prepared_bytes=need) == WN_ERR_WORKSPACE
+    assert REFERENCE(lib, ref_len=0, k=7, ref=None) == WN_ERR_BAD_SHAPE
+    assert REFERENCE(lib, k=7, ref=None) == WN_ERR_UNSUPPORTED
+    assert REFERENCE(lib, model=None, prepared_bytes=0) == WN_ERR_NULL
 
 
 def test_rejects_on_the_host_in_order(lib):
-    assert _call(lib) == WN_ERR_WORKSPACE                            # everything else about the default call is accepted
-    for kw in (dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(ref_len=0), dict(ref_len=-1), dict(ref_len=4),
-               dict(signal_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)):
-        assert _call(lib, **kw) == WN_ERR_BAD_SHAPE, kw
-    for kw in (dict(k=0), dict(k=7, ref_len=5000), dict(frac_bits=-1), dict(frac_bits=21), dict(weight_shift=15), dict(weight_shift=64),
-               dict(max_cost=0), dict(max_cost=-1), dict(max_signal=4097), dict(ref_len=2 ** 26 + 1), dict(batch=65536),
-               dict(strip_states=32), dict(strip_states=96), dict(strip_states=-64), dict(strip_states=2 ** 20 + 64), dict(strip_states=1)):
-        assert _call(lib, **kw) == WN_ERR_UNSUPPORTED, kw
-    # the accepted side of each limit goes on to the pointer checks
-    for kw in (dict(k=1), dict(k=6), dict(frac_bits=0), dict(frac_bits=20), dict(weight_shift=16), dict(weight_shift=63), dict(max_cost=1),
-               dict(max_cost=2 ** 31 - 1), dict(max_signal=4096), dict(max_signal=1), dict(ref_len=2 ** 26), dict(ref_len=5), dict(batch=65535),
-               dict(batch=1), dict(strip_states=64), dict(strip_states=576), dict(strip_states=2 ** 20), dict(signal_kind=1),
-               dict(signal_stride=0), dict(ref_len=1, k=1)):
-        assert _call(lib, signal=None, **kw) == WN_ERR_NULL, kw
-    # a grid of 2^31 workgroups or more: 2^20 strips of 64 states for each of 2048 reads; one strip fewer per read passes
-    assert _call(lib, ref_len=2 ** 26, k=1, strip_states=64, batch=2048, signal=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, ref_len=2 ** 26 - 64, k=1, strip_states=64, batch=2048, signal=None) == WN_ERR_NULL
-    assert _call(lib, ref_len=2 ** 26, k=1, strip_states=128, batch=2048, signal=None) == WN_ERR_NULL
-    for name in REQUIRED:
-        assert _call(lib, **{name: None}) == WN_ERR_NULL, name
+    assert MAP(lib) == WN_ERR_WORKSPACE                              # everything else about the default call is accepted
+    MAP.rejects(lib, "signal",
+                shape=(dict(batch=0), dict(batch=-2), dict(max_signal=0), dict(max_signal=-5), dict(ref_len=0), dict(ref_len=-1), dict(ref_len=4),
+                       dict(signal_stride=-1), dict(signal_kind=2), dict(signal_kind=-1)),
+                unsupported=(dict(k=0), dict(k=7, ref_len=5000), dict(frac_bits=-1), dict(frac_bits=21), dict(weight_shift=15),
+                             dict(weight_shift=64), dict(max_cost=0), dict(max_cost=-1), dict(max_signal=4097), dict(ref_len=2 ** 26 + 1),
+                             dict(batch=65536), dict(strip_states=32), dict(strip_states=96), dict(strip_states=-64),
+                             dict(strip_states=2 ** 20 + 64), dict(strip_states=1),
+                             # a grid of 2^31 workgroups or more: 2^20 strips of 64 states for each of 2048 reads
+                             dict(ref_len=2 ** 26, k=1, strip_states=64, batch=2048, signal=None)),
+                accepted=(dict(k=1), dict(k=6), dict(frac_bits=0), dict(frac_bits=20), dict(weight_shift=16), dict(weight_shift=63),
+                          dict(max_cost=1), dict(max_cost=2 ** 31 - 1), dict(max_signal=4096), dict(max_signal=1), dict(ref_len=2 ** 26),
+                          dict(ref_len=5), dict(batch=65535), dict(batch=1), dict(strip_states=64), dict(strip_states=576),
+                          dict(strip_states=2 ** 20), dict(signal_kind=1), dict(signal_stride=0), dict(ref_len=1, k=1),
+                          # one strip fewer per read passes, and so do strips twice as wide
+                          dict(ref_len=2 ** 26 - 64, k=1, strip_states=64, batch=2048), dict(ref_len=2 ** 26, k=1, strip_states=128, batch=2048)),
+                required=("signal", "signal_lengths", "prepared", "score", "end", "start", "runner_up", "block_cost", "block_end", "workspace"))
     for name in ("scale_shift", "end_cost", "bad"):                  # optional
-        assert _call(lib, **{name: None}) == WN_ERR_WORKSPACE, name
+        assert MAP(lib, **{name: None}) == WN_ERR_WORKSPACE, name
     # the workspace: too small by one byte, misaligned, and a signal off its element size
-    need = lib.wn_signal_map_workspace_bytes(2, 1000, 5000, 5, 0)
+    need = MAP_SIZE(lib)
     assert need == (2 * 4 * 79 + 15) // 16 * 16                      # 4996 states: 79 blocks
-    assert _call(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
-    assert _call(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
-    assert _call(lib, batch=3, workspace_bytes=need) == WN_ERR_WORKSPACE             # the size follows the batch
+    assert MAP(lib, workspace_bytes=need - 1) == WN_ERR_WORKSPACE
+    assert MAP(lib, workspace=ctypes.c_void_p((1 << 20) + 8), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert MAP(lib, signal=ctypes.c_void_p((1 << 20) + 2), workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert MAP(lib, signal=ctypes.c_void_p((1 << 20) + 1), signal_kind=1, workspace_bytes=need) == WN_ERR_WORKSPACE
+    assert MAP(lib, batch=3, workspace_bytes=need) == WN_ERR_WORKSPACE               # the size follows the batch
     # the order: shape, then unsupported, then NULL, then workspace
-    assert _call(lib, batch=0, k=7, signal=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, signal_kind=2, strip_states=96, prepared=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, ref_len=4, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
-    assert _call(lib, k=7, signal=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, weight_shift=64, score=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, max_signal=4097, workspace=None) == WN_ERR_UNSUPPORTED
-    assert _call(lib, prepared=None, workspace_bytes=0) == WN_ERR_NULL
+    assert MAP(lib, batch=0, k=7, signal=None) == WN_ERR_BAD_SHAPE
+    assert MAP(lib, signal_kind=2, strip_states=96, prepared=None) == WN_ERR_BAD_SHAPE
+    assert MAP(lib, ref_len=4, batch=65536, workspace=None) == WN_ERR_BAD_SHAPE
+    assert MAP(lib, k=7, signal=None) == WN_ERR_UNSUPPORTED
+    assert MAP(lib, weight_shift=64, score=None) == WN_ERR_UNSUPPORTED
+    assert MAP(lib, max_signal=4097, workspace=None) == WN_ERR_UNSUPPORTED
+    assert MAP(lib, prepared=None, workspace_bytes=0) == WN_ERR_NULL
 
 
 def _hand_model():
