@@ -131,3 +131,25 @@ def host_alignment(B=2, n=30):
     import torch
     import wavenet_speech_amd as W
     return W.PairwiseAlignment(None, None, None, None, None, torch.ones(B, n, dtype=torch.uint8), torch.full((B,), n, dtype=torch.int32))
+
+
+def hand_made_genotypes():
+    """the case of tests/test_genotype_ref.py::test_records_by_hand as tensors"""
+    import torch
+    import wavenet_speech_amd as W
+    U = W.Genotypes
+    ref = [1, 2, 3, 4, 1, 2, 3, 4]
+    alleles = [(0, 0), (2, 0), (1, 0), (4, 0), (2, 2), (2, 0), (0, 0), (1, 2)]
+    flags = [U.DELETION, U.DELETION | U.HET, U.SUBSTITUTION | U.DELETION | U.HET, U.DELETION | U.HET, U.SUBSTITUTION | U.INSERTION | U.INS_HET,
+             U.DELETION | U.HET, U.DELETION, U.SUBSTITUTION | U.HET]
+    R = len(ref)
+    counts = torch.zeros(R, 2, 6, dtype=torch.int32)
+    counts[:, 0, 0] = torch.arange(R, dtype=torch.int32) + 3
+    pile = W.Pileup(counts, torch.zeros(R, 3, dtype=torch.int32), torch.zeros(R, 2, 4, dtype=torch.int32), None)
+    u8 = lambda v: torch.tensor(v, dtype=torch.uint8)                # noqa: E731
+    i32 = lambda k, c: (torch.arange(R) * k + c).to(torch.int32)     # noqa: E731
+    ins_bases = torch.zeros(R, 2, dtype=torch.uint8)
+    ins_bases[4] = u8([4, 1])
+    g = W.Genotypes(u8(alleles), i32(100, 1), i32(1000, 2), u8(flags), u8([0, 0, 0, 0, 1, 0, 0, 0]), u8([0, 0, 0, 0, 2, 0, 0, 0]), ins_bases,
+                    i32(10, 5), i32(10, 7), None)
+    return ref, g, pile

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ORACLE_TOL = 2e-5          # the oracle and the exact references against the golden vectors (tests/test_oracle_golden.py, test_halfref.py)
 
 
 class Golden:

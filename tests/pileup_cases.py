@@ -38,6 +38,31 @@ def rows(seqs, width=None, dtype=np.int32):
     return out, np.array([len(s) for s in seqs], dtype=np.int32)
 
 
+def read(ops, rng, odd=0.1, quals=True):
+    """(ops, n_ref, query, qual) with random labels, a share `odd` of them outside 1..4, and random quals; without quals none
+    are drawn and the tuple ends at the query"""
+    n_query = sum(v != 3 for v in ops)
+    query = [int(v) if rng.random() >= odd else int(rng.choice([0, 5, 9])) for v in rng.integers(1, 5, size=n_query)]
+    head = (list(ops), sum(v != 4 for v in ops), query)
+    return head + ([int(v) for v in rng.integers(0, 94, size=n_query)],) if quals else head
+
+
+def random_ops(rng, n):
+    return [int(v) for v in rng.choice([1, 2, 3, 4], size=n, p=[0.6, 0.2, 0.1, 0.1])]
+
+
+def cols(reads):
+    """the reads of read() as their four columns"""
+    return [r[0] for r in reads], [r[1] for r in reads], [r[2] for r in reads], [r[3] for r in reads]
+
+
+def random_pile(rng, R, max_ins, top=4):
+    counts = rng.integers(0, top, size=(R, 2, 6))
+    ins_lengths = rng.integers(0, top, size=(R, max_ins + 1)) * (rng.random((R, 1)) < 0.5)
+    ins_bases = rng.integers(0, 3, size=(R, max_ins, 4)) * (rng.random((R, max_ins, 1)) < 0.7)
+    return P.Pile(counts.astype(np.int64), ins_lengths.astype(np.int64), ins_bases.astype(np.int64), None, 0)
+
+
 def _ambiguous(ref, kind, p, n, inserted):
     """a deletion of ref[p:p + n], or an insertion of `inserted` between p and p + 1, that a shift by one position leaves unchanged"""
     if kind == "del":

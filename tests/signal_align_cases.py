@@ -133,15 +133,19 @@ def reference(name):
     return call_ref(CASES[name])
 
 
-@functools.lru_cache(maxsize=None)
-def int16_form(name):
-    """(raw int16 [B, L], scale_shift float32 [B, 2]) of a case"""
-    case = CASES[name]
+def int16_of(case):
+    """(raw int16 [B, L], scale_shift float32 [B, 2]) of a case of any of the signal tools: the samples in eighths, under a scale
+    near 1/8 and a shift, both seeded"""
     rng = np.random.default_rng(99)
     raw = np.rint(case.signal.astype(np.float64) * 8.0).astype(np.int16)
     B = raw.shape[0]
     ss = np.stack([0.125 * (1.0 + 0.01 * rng.standard_normal(B)), 3.0 * rng.standard_normal(B)], axis=1).astype(np.float32)
     return raw, ss
+
+
+@functools.lru_cache(maxsize=None)
+def int16_form(name):
+    return int16_of(CASES[name])
 
 
 @functools.lru_cache(maxsize=None)

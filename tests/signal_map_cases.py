@@ -118,13 +118,7 @@ def reference(name):
 
 @functools.lru_cache(maxsize=None)
 def int16_form(name):
-    """(raw int16 [B, L], scale_shift float32 [B, 2]) of a case"""
-    case = CASES[name]
-    rng = np.random.default_rng(99)
-    raw = np.rint(case.signal.astype(np.float64) * 8.0).astype(np.int16)
-    B = raw.shape[0]
-    ss = np.stack([0.125 * (1.0 + 0.01 * rng.standard_normal(B)), 3.0 * rng.standard_normal(B)], axis=1).astype(np.float32)
-    return raw, ss
+    return A.int16_of(CASES[name])
 
 
 @functools.lru_cache(maxsize=None)

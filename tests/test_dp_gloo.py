@@ -2,7 +2,6 @@
 the same gradients as a single process on the concatenated batch.  The model here is the CPU oracle's residual
 block stack (tests may use the oracle); on the GPU the same FlatGradAllReduce object drives RCCL."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
@@ -10,6 +9,7 @@ import torch.multiprocessing as mp
 
 from oracle import wavenet_oracle as O
 from wavenet_speech_amd.parallel import FlatGradAllReduce, shard_bounds
+from tests.cpu_util import free_port as _free_port
 
 LAYERS = [(6, 6, 2, 1), (6, 6, 2, 2), (6, 6, 2, 4)]
 
@@ -56,14 +56,6 @@ def _worker(rank, world, port, out, async_op=False):
     if rank == 0:
         torch.save({k: p.grad.clone() for k, p in params.items() if p.grad is not None}, out)
     dist.destroy_process_group()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def test_two_rank_allreduce_matches_single_process(tmp_path):

@@ -10,7 +10,7 @@ import torch
 
 from tests.abi_util import FAKE, READ_ACCEPTED, READ_BATCH, READ_REQUIRED, READ_SHAPE, READ_UNSUPPORTED, WN_ERR_BAD_SHAPE, WN_ERR_NULL, \
     WN_ERR_UNSUPPORTED, Entry, header_names, host_alignment
-from tests.abi_util import lib  # noqa: F401
+from tests.abi_util import hand_made_genotypes as _hand_made, lib  # noqa: F401
 
 
 def _table(fill=1, **at):
@@ -114,27 +114,6 @@ def test_python_surface_refusals():
         W.call_genotypes(pile, ev, [1] * 6, w)
     assert (W.Genotypes.HET, W.Genotypes.INS_HET, W.Genotypes.LOW_DEPTH, W.Genotypes.SUBSTITUTION, W.Genotypes.DELETION, W.Genotypes.INSERTION) == \
         (32, 64, 1, 4, 8, 16)
-
-
-def _hand_made():
-    """the case of tests/test_genotype_ref.py::test_records_by_hand as tensors"""
-    import wavenet_speech_amd as W
-    U = W.Genotypes
-    ref = [1, 2, 3, 4, 1, 2, 3, 4]
-    alleles = [(0, 0), (2, 0), (1, 0), (4, 0), (2, 2), (2, 0), (0, 0), (1, 2)]
-    flags = [U.DELETION, U.DELETION | U.HET, U.SUBSTITUTION | U.DELETION | U.HET, U.DELETION | U.HET, U.SUBSTITUTION | U.INSERTION | U.INS_HET,
-             U.DELETION | U.HET, U.DELETION, U.SUBSTITUTION | U.HET]
-    R = len(ref)
-    counts = torch.zeros(R, 2, 6, dtype=torch.int32)
-    counts[:, 0, 0] = torch.arange(R, dtype=torch.int32) + 3
-    pile = W.Pileup(counts, torch.zeros(R, 3, dtype=torch.int32), torch.zeros(R, 2, 4, dtype=torch.int32), None)
-    u8 = lambda v: torch.tensor(v, dtype=torch.uint8)                # noqa: E731
-    i32 = lambda k, c: (torch.arange(R) * k + c).to(torch.int32)     # noqa: E731
-    ins_bases = torch.zeros(R, 2, dtype=torch.uint8)
-    ins_bases[4] = u8([4, 1])
-    g = W.Genotypes(u8(alleles), i32(100, 1), i32(1000, 2), u8(flags), u8([0, 0, 0, 0, 1, 0, 0, 0]), u8([0, 0, 0, 0, 2, 0, 0, 0]), ins_bases,
-                    i32(10, 5), i32(10, 7), None)
-    return ref, g, pile
 
 
 def test_genotype_and_vcf_records_on_hand_made_tensors():

@@ -14,30 +14,15 @@ import wavenet_speech_amd as W
 from tests import align_limits_cases as C
 from tests import ctc_align_ref as A
 from tests import pairwise_align_ref as R
-from tests.test_gpu_align import _run
-from tests.test_gpu_pairalign import _align
-from tests.test_gpu_profile import _equal
+from tests.gpu_labels import assert_profile as _equal, forced_align as _run, pair_align as _align
+from tests.gpu_util import DEV, dev as _dev, no_stale_flags  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-@pytest.fixture(autouse=True)
-def _no_flags_left_by_another_test():
-    """a test that failed between a call with bad rows and its check leaves their flag behind: it is not this test's"""
-    try:
-        W.check_device_flags()
-    except RuntimeError:
-        pass
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ========================================================================================================= the forced aligner
 def _check_exact(labels, blank, Tb, want, states, frame_labels, spans, score, tag):
-    """one utterance, as tests/test_gpu_align.py::_check_utterance(exact=True) has it, against a cached reference"""
+    """one utterance, as tests/gpu_labels.py::check_utterance(exact=True) has it, against a cached reference"""
     want_states, want_score, want_spans = want
     L = len(labels)
     assert (states[Tb:] == -1).all() and (frame_labels[Tb:] == -1).all() and (spans[L:] == -1).all(), tag
@@ -71,7 +56,7 @@ def test_forced_alignment_equals_the_reference(name):
 
 # ======================================================================================================= the pairwise aligner
 def _check_pair(a, b, costs, free, want, score, stats, ops, ops_len, tag):
-    """one pair, as tests/test_gpu_pairalign.py::_check_pair has it, against a cached reference or a closed form"""
+    """one pair, as tests/gpu_labels.py::check_pair has it, against a cached reference or a closed form"""
     assert score == want.score, (tag, score, want.score)
     assert tuple(stats) == (want.matches, want.mismatches, want.gaps, want.length), (tag, tuple(stats), want[1:5])
     assert ops_len == want.length, (tag, ops_len, want.length)

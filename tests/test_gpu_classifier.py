@@ -4,15 +4,14 @@ output block -- forward, dx and every parameter gradient, in all four precisions
 f32 and f16x3 are held to the project's 1e-4 against the oracle (oracle.wavenet_classifier).  The plain modes are held to the error
 their storage format implies: tests/halfref.py::wavenet_classifier, predicate e_hip <= KAPPA e_fmt + FLOOR in max-norm and RMS.
 References that pool differently -- each what a plausible kernel bug would compute -- must be REJECTED for the unaltered GPU result."""
-import os
-
 import pytest
 import torch
 
 import wavenet_speech_amd as W
 from oracle import wavenet_oracle as O
 from tests import halfref as R
-from tests.test_gpu_half import DEV, PLAIN, TOL, _condition, _launched
+from tests.gpu_stack import PLAIN, TOL, Env as _Env, condition as _condition, launched as _launched, plain_slopes as _plain_slopes
+from tests.gpu_util import DEV
 from wavenet_speech_amd import functional as HF
 
 pytestmark = pytest.mark.gpu
@@ -24,42 +23,6 @@ def _classifier(in_dim, layers, out_dim, pool, kw=2, dil=1, seed=0):
     torch.manual_seed(seed)
     net = WaveNetClassifier(in_dim, 5, layers, out_dim, pool_kernel_size=pool, input_kernel_size=kw, input_dilation=dil, softmax=False)
     return _condition(net)
-
-
-class _Env(object):
-    def __init__(self, env):
-        self.env, self.old = env or {}, {}
-
-    def __enter__(self):
-        for k, v in self.env.items():
-            self.old[k] = os.environ.get(k)
-            os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _plain_slopes(net, xg):
-    """the GPU's LeakyReLU pattern in a plain mode: one extra forward on the training path with the output block outside the stack
-    function (as tests/test_gpu_half.py::_run takes it)"""
-    slopes, handles = {}, []
-    for name, mod in net.named_modules():
-        if isinstance(mod, torch.nn.LeakyReLU):
-            def hook(_m, inp, name=name, ns=mod.negative_slope):
-                xin = inp[0].detach()
-                slopes[name] = torch.where(xin > 0, torch.ones_like(xin), torch.full_like(xin, ns)).cpu()
-            handles.append(mod.register_forward_pre_hook(hook))
-    try:
-        with _Env({"WN_SERIES_HEAD": "0"}):
-            net(xg.detach().requires_grad_(xg.requires_grad))
-    finally:
-        for h in handles:
-            h.remove()
-    return slopes
 
 
 def gpu_run(net, x, cot, precision, input_grad=True, env=None):

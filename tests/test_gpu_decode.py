@@ -5,33 +5,14 @@ import pytest
 import torch
 
 from tests import ctc_decode_ref as R
+from tests.gpu_labels import decoding as _D
+from tests.gpu_util import DEV, peaked_logits, random_logits as _random_logits
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _D():
-    from wavenet_speech_amd import decoding
-    return decoding
-
-
-def _random_logits(seed, B, C, T, scale=1.5):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(B, C, T, generator=g) * scale
 
 
 def _peaked_logits(seed, B, C, T, margin=5.0):
-    """'trained-looking' output: a random path of runs (the blank between runs) well above noisy other classes"""
-    rng = np.random.default_rng(seed)
-    x = rng.normal(size=(B, C, T)) * 1.0
-    for b in range(B):
-        t = 0
-        while t < T:
-            c = int(rng.integers(0, C))
-            d = int(rng.integers(1, 6))
-            x[b, c, t:t + d] += margin * rng.uniform(0.6, 1.0)
-            t += d
-    return torch.tensor(x, dtype=torch.float32)
+    return peaked_logits(seed, B, C, T, margin)[0]
 
 
 def test_greedy_matches_the_reference_bitwise_in_both_layouts():

@@ -10,14 +10,10 @@ import torch
 
 from tests import ctc_decode_cases as K
 from tests import ctc_decode_ref as R
+from tests.gpu_labels import decoding as _D
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _D():
-    from wavenet_speech_amd import decoding
-    return decoding
 
 
 def _no_flag():

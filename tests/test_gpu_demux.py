@@ -8,29 +8,10 @@ import torch
 import wavenet_speech_amd as W
 from tests import demux_cases as C
 from tests import demux_ref as R
+from tests.gpu_labels import INT_MIN, assert_pick as _assert_pick, assert_scores as _assert_scores, kit as _kit, kw as _kw
+from tests.gpu_util import DEV, dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-INT_MIN = -2 ** 31
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _kit(case):
-    ends = [0] * case.n_front + [1] * (len(case.group) - case.n_front)
-    return W.BarcodeSet.from_table(case.patterns, case.pattern_lengths, ends, case.group)
-
-
-def _kw(case):
-    return dict(zip(("match", "mismatch", "gap_open", "gap_extend"), (c / 2.0 for c in case.costs)), window=case.window)
-
-
-def _assert_scores(got, ref):
-    assert got.score.dtype == torch.float32 and got.start.dtype == torch.int32 and got.end.dtype == torch.int32
-    assert np.array_equal(got.score.cpu().numpy().astype(np.float64) * 2.0, ref["score"].astype(np.float64))
-    assert np.array_equal(got.start.cpu().numpy(), ref["start"]) and np.array_equal(got.end.cpu().numpy(), ref["end"])
 
 
 def test_the_case_worked_by_hand():
@@ -104,12 +85,6 @@ def test_a_poisoned_pattern_length():
     for got, name in zip(out, ("score", "start", "end")):
         assert np.array_equal(got.cpu().numpy(), want[name]), name
     assert int(bad[0]) == want["bad"]
-
-
-def _assert_pick(got, want):
-    for name in ("barcode", "trim", "hits", "runner_up"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int32 and np.array_equal(t.cpu().numpy(), want[name]), name
 
 
 def test_the_planted_run():

@@ -3,7 +3,6 @@ so the collective here is gloo (ProcessGroupGloo stages device tensors through t
 replica / shard / flat-gradient logic around the HIP kernels, with the same FlatGradAllReduce object bench.py drives over
 RCCL.  Two processes use the card at once (the box allows six)."""
 import os
-import socket
 
 import pytest
 import torch
@@ -11,6 +10,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import wavenet_oracle as O
+from tests.cpu_util import free_port as _free_port
 
 pytestmark = pytest.mark.gpu
 LAYERS = [(32, 32, 2, 2 ** i) for i in range(4)]
@@ -52,14 +52,6 @@ def _worker(rank, world, port, out):
         torch.save({k: p.grad.detach().cpu().clone() for k, p in net.named_parameters() if p.grad is not None}, out)
     dist.barrier()
     dist.destroy_process_group()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def test_two_ranks_on_one_gpu_match_single_process(tmp_path):

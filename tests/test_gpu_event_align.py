@@ -8,50 +8,11 @@ import torch
 import wavenet_speech_amd as W
 from tests import event_align_cases as C
 from tests import event_align_ref as R
+from tests.gpu_signal import assert_event_alignment as _assert_equal, assert_move_counts as _assert_counts, event_align as _call
+from tests.gpu_signal import event_model as _model, event_tables as _events
+from tests.gpu_util import DEV, dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _model(case):
-    return W.SignalModel(torch.from_numpy(case.model), case.kw["weight_shift"], frac_bits=C.F, cost_bits=C.COST_BITS)
-
-
-def _events(case):
-    return (_dev(case.n_events), _dev(case.ev_starts), _dev(case.ev_sum), _dev(case.ev_sumsq))
-
-
-def _call(case, band=None, states=True, labels=None, model=None, moves=None):
-    kw = case.kw
-    return W.event_align(_events(case), _dev(case.labels) if labels is None else labels, _dev(case.label_lengths),
-                         _model(case) if model is None else model, first=kw["first"], band=kw["band"] if band is None else band,
-                         moves=kw["move_cost"] if moves is None else moves, max_cost=kw["max_cost"], want_states=states, frac_bits=C.F)
-
-
-def _assert_equal(got, ref, states=True):
-    assert got.score.dtype == torch.int64 and got.score.tolist() == [int(v) for v in ref["score"]]
-    for name in ("starts", "band_hits", "moves"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int32 and np.array_equal(t.cpu().numpy(), ref[name]), name
-    if states:
-        assert got.states.dtype == torch.int32 and np.array_equal(got.states.cpu().numpy(), ref["states"])
-    else:
-        assert got.states is None
-
-
-def _assert_counts(got, case, ref):
-    """1 + sum counts = E and counts[1] + 2 counts[2] + 3 counts[3] = N - 1 on every aligned read"""
-    kw = case.kw
-    moves = got.moves.cpu().numpy().astype(np.int64)
-    for b, sc in enumerate(ref["score"]):
-        if sc in (R.NO_ALIGNMENT, R.BAD_READ):
-            continue
-        N = int(case.label_lengths[b]) - (kw["k"] - 1) - 2 * kw["first"]
-        assert 1 + moves[b].sum() == case.n_events[b] and moves[b, 1] + 2 * moves[b, 2] + 3 * moves[b, 3] == N - 1
 
 
 def test_the_case_worked_by_hand():

@@ -8,41 +8,10 @@ import torch
 
 import wavenet_speech_amd as W
 from tests import event_detect_cases as C
+from tests.gpu_signal import assert_detected as _assert_equal, detect_events as _call
+from tests.gpu_util import DEV, dev as _dev, strided as _strided
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _strided(a, channel):
-    """the rows of `a` as a view into a wider device buffer (row stride L + 5, one element in); [B, 1, L] with channel"""
-    B, L = a.shape
-    wide = torch.zeros(B, L + 5, dtype=torch.from_numpy(a[:1, :1]).dtype, device=DEV)
-    wide[:, 1:1 + L] = _dev(a)
-    view = wide[:, 1:1 + L]
-    return view.unsqueeze(1) if channel else view
-
-
-def _call(case, signal=None, scale_shift=None, chunk=C.CHUNK, **more):
-    signal = _dev(case.signal) if signal is None else signal
-    kw = dict(case.kw, **more)
-    return W.detect_events(signal, _dev(case.signal_lengths), scale_shift=None if scale_shift is None else _dev(scale_shift), chunk=chunk, **kw)
-
-
-def _i64(a):
-    return np.array(a.tolist(), dtype=np.int64).reshape(a.shape)
-
-
-def _assert_equal(got, ref):
-    for name, field in (("n_events", "n_events"), ("starts", "starts"), ("kind", "kind")):
-        t = getattr(got, field)
-        assert t.dtype == torch.int32 and np.array_equal(t.cpu().numpy(), ref[name]), name
-    for name in ("sum", "sumsq"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int64 and np.array_equal(t.cpu().numpy(), _i64(ref[name])), name
 
 
 def test_lengths_around_the_windows_and_the_seams():

@@ -11,55 +11,11 @@ import torch
 import wavenet_speech_amd as W
 from tests import kmer_events_cases as EC
 from tests import kmer_events_ref as R
+from tests.gpu_signal import assert_kmer_events as _assert_equal, kmer_events as _call
+from tests.gpu_util import DEV, dev as _dev, same as _same
 from wavenet_speech_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-EVENT_FIELDS = ("kmer", "start", "length", "sum", "sumsq")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _strided(a, channel):
-    """the rows of `a` as a view into a wider device buffer (row stride L + 5, one element in); [B, 1, L] with channel"""
-    B, L = a.shape
-    wide = torch.zeros(B, L + 5, dtype=torch.from_numpy(a[:1, :1]).dtype, device=DEV)
-    wide[:, 1:1 + L] = _dev(a)
-    view = wide[:, 1:1 + L]
-    assert not view.is_contiguous() or B == 1
-    return view.unsqueeze(1) if channel else view
-
-
-def _call(case, layout, kind, frac_bits, seg=None, strided=False, **more):
-    if kind == "f32":
-        signal, ss = case.signal, None
-    else:
-        signal, ss = more.pop("int16")
-    signal = _strided(signal, kind == "f32") if strided else _dev(signal)
-    if seg is None:
-        seg = EC.spans_of(case) if layout == "spans" else case.starts
-    kw = dict(dict(max_dwell=255), **case.kw)
-    kw.update(more)
-    return W.kmer_events(signal, _dev(case.signal_lengths), _dev(case.labels), _dev(case.label_lengths), frac_bits=frac_bits,
-                         scale_shift=None if ss is None else _dev(ss), **{layout: _dev(seg)}, **kw)
-
-
-def _assert_equal(got, ref, events=True):
-    if events:
-        for name, field in zip(EVENT_FIELDS, got[:5]):
-            assert field.dtype == (torch.int64 if name in ("sum", "sumsq") else torch.int32), name
-            assert np.array_equal(field.cpu().numpy(), ref[name]), name
-    else:
-        assert all(f is None for f in got[:5])
-    assert got.read_counts.dtype == torch.int32 and np.array_equal(got.read_counts.cpu().numpy(), ref["read_counts"])
-    assert got.kmer_stats.dtype == torch.int64 and np.array_equal(got.kmer_stats.cpu().numpy(), ref["kmer_stats"])
-    assert got.dwell_hist.dtype == torch.int64 and np.array_equal(got.dwell_hist.cpu().numpy(), ref["dwell_hist"])
-
-
-def _same(a, b):
-    return all((u is None and v is None) or torch.equal(u, v) for u, v in zip(a, b))
 
 
 @pytest.mark.parametrize("frac_bits", [0, 12])

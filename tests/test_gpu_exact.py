@@ -7,7 +7,6 @@ wgrad slab that drops a 32-step chunk, a reduce that skips a slab, an f16x3 prod
 Two points rest on the hardware: v_rcp_f32(2) = 0.5 and the saturation values of the exp2 / rcp tanh and sigmoid.
 test_gate_values_at_multiples_of_q (and its f16x3 twin) asserts them on their own; every fp32 block and stack test asserts them
 on the saved sigmoid / z of its own case before it looks at anything else."""
-import os
 import time
 
 import pytest
@@ -20,49 +19,11 @@ from wavenet_speech_amd.modules.block import ResidualBlock, fusable_head, run_st
 from wavenet_speech_amd.modules.wavenet import WaveNet
 
 from tests import exactref as X
+from tests.gpu_stack import UNFUSED, Env as _Env, assert_saved_gate as _assert_saved_gate, exact_dev as _dev, exact_same as _same
+from tests.gpu_stack import launches as _launches, timed as _timed
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _dev(t, grad=False):
-    assert X.is_fp32(t)
-    return t.float().to(DEV).requires_grad_(grad)
-
-
-def _same(got, want, what):
-    """every tensor of `want` is bit for bit in `got`; the message names the tensor and the first differing element"""
-    missing = sorted(set(want) - set(got))
-    assert not missing, (what, "missing", missing)
-    for k in sorted(want):
-        diff = X.first_difference(got[k], want[k].float())
-        assert diff is None, "%s: %s differs, first at %s: got %r, exact %r (%s)" % ((what, k) + diff[:3] + (diff[3:],))
-
-
-class _Env(object):
-    def __init__(self, env):
-        self.env, self.old = dict(env or {}), {}
-
-    def __enter__(self):
-        for k, v in self.env.items():
-            self.old[k] = os.environ.get(k)
-            os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.time()
-    out = fn()
-    torch.cuda.synchronize()
-    print("device part: %.3f s" % (time.time() - t0))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -89,12 +50,6 @@ def test_gate_values_at_multiples_of_q():
     assert X.pairs_seen(ta, sg) == set(X.NINE)
     _same({"z": z}, {"z": ta * sg}, "gate")
     assert seen == [-1.0, -0.5, 0.0, 0.5, 1.0]
-
-
-def _assert_saved_gate(fn_node, want_sg, want_z, what):
-    """the precondition of a case, on what the function saved for backward: sigmoid and z are the three-valued ones"""
-    _x, sg, z = fn_node.saved[:3]
-    _same({"sg": sg.view(), "z": z.view()}, {"sg": want_sg, "z": want_z}, what + " (precondition: saved gate)")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -194,17 +149,6 @@ def _net(c):
     return net.to(DEV)
 
 
-def _launches(fn):
-    HF.profile_reset()
-    HF.profile_enable(True)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        HF.profile_enable(False)
-    return out, {k: v[1] for k, v in HF.profile_read().items() if v[1]}
-
-
 def _assert_saved_gates_of_stack(node, c, what):
     n = len(c.layers)
     assert len(node.saved) == n
@@ -294,9 +238,6 @@ def test_f16x3_stack_is_exact():
     want["forward (no_grad)"] = c.ref["forward"]
     _same(got, want, "f16x3 stack")
     assert set(got) == set(want), sorted(set(got) ^ set(want))
-
-
-UNFUSED = {"head": {"WN_SERIES_HEAD": "0"}, "entry": {"WN_SERIES_FRONT": "0"}, "both": {"WN_SERIES_HEAD": "0", "WN_SERIES_FRONT": "0"}}
 
 
 def _step(net, c, levels=False, input_grad=False, env=None, check_gates=None):

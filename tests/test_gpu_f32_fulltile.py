@@ -17,13 +17,12 @@ from wavenet_speech_amd.modules.block import ResidualBlock, fold_bottlenecks, fu
 from wavenet_speech_amd.modules.wavenet import WaveNet
 
 from tests import exactref as X
-from tests.test_gpu_exact import _assert_saved_gate, _dev, _same, _timed
-from tests.test_gpu_f32_series import UNFUSED, _launches
-from tests.test_gpu_f32_series import _same as _same_bits
-from tests.test_gpu_f32_series import _step
+from tests.gpu_stack import UNFUSED, assert_saved_gate as _assert_saved_gate, exact_dev as _dev, exact_same as _same
+from tests.gpu_stack import launches as _launches, same_step as _same_bits, step as _step, timed as _timed
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+
 
 # (ci, co, k, d, causal, L, B); dz runs 64-row slabs (MT = 2) from 64 channels on, 128 columns per tile
 FULL_TILE_CASES = [
@@ -120,7 +119,7 @@ def test_fused_step_on_full_tiles_is_bitwise_the_op_by_op_step():
     fused = _step(net, x, cot, input_grad=True)
     for _what, env in sorted(UNFUSED.items()):
         _same_bits(fused, _step(net, x, cot, input_grad=True, env=env))
-    ran = _launches(lambda: _step(net, x, cot))
+    _, ran = _launches(lambda: _step(net, x, cot))
     assert ran["series_gemm_kernel<conv_bwd_data>"] == 2 and ran["series_gemm_kernel<skips_sum>"] == 1, ran
 
 
@@ -135,7 +134,7 @@ def test_inference_accumulates_skips_on_full_tiles():
     S = run_stack(x, net.convolutions, net.bottlenecks, net.stack_state)
     out = {}
     with torch.no_grad():
-        ran = _launches(lambda: out.update(S=run_stack(x, net.convolutions, net.bottlenecks, net.stack_state)))
+        _, ran = _launches(lambda: out.update(S=run_stack(x, net.convolutions, net.bottlenecks, net.stack_state)))
         wfs, bfs = fold_bottlenecks(list(net.convolutions), list(net.bottlenecks))
     S_inf = out["S"]
     assert ran["series_gemm_kernel<skips_sum>"] == len(LAYERS), ran

@@ -5,44 +5,23 @@ in the epilogues is torch's own rule -- and the op-by-op fallback against an fp6
 Shapes are the smallest that reach the edges: 40 channels (a ragged 32-row tile, cp8 padding), skip / out dim 24, k = 2 blocks at
 dilations 1, 2, 4 and a stack of one k = 3 block, B = 2, L in {130 (a full 128-column tile and a 2-column one: the clip), 128 (one
 tile exactly), 5 (shorter than a dilation)}."""
-import os
-
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import wavenet_speech_amd as W
-from wavenet_speech_amd import functional as HF
 from wavenet_speech_amd.modules.block import fusable_head, run_stack
 from wavenet_speech_amd.modules.pointwise import run_sequential
 from wavenet_speech_amd.modules.wavenet import WaveNet
 
 from oracle import wavenet_oracle as O
+from tests.gpu_stack import TOL, UNFUSED, Env as _Env, launches as _launches, same_step as _same, step as _step, train as _train
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL = 1e-4                 # the bound of the fp32 parity tests (tests/test_gpu_parity.py)
 C, MS, IN, B = 40, 24, 11, 2
 STACKS = {"three_k2": [(C, C, 2, 1), (C, C, 2, 2), (C, C, 2, 4)], "one_k3": [(C, C, 3, 2)]}
 LENGTHS = [130, 128, 5]
-
-
-class _Env(object):
-    def __init__(self, env):
-        self.env, self.old = dict(env or {}), {}
-
-    def __enter__(self):
-        for k, v in self.env.items():
-            self.old[k] = os.environ.get(k)
-            os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _net(stack, seed):
@@ -53,40 +32,6 @@ def _net(stack, seed):
             if p.dim() == 1:                      # the reference's init zeroes every bias: give them values
                 p.normal_(0.0, 0.1)
     return net.to(DEV)
-
-
-def _step(net, x, cot, levels=False, input_grad=False, env=None):
-    """{"forward", parameter names, "dx0"} of one forward and backward"""
-    net.zero_grad(set_to_none=True)
-    xg = x if levels else x.detach().clone().requires_grad_(input_grad)
-    with _Env(env):
-        y = net.forward_levels(xg) if levels else net(xg)
-        (y * cot).sum().backward()
-    out = {"forward": y.detach().clone()}
-    out.update({k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None})
-    if input_grad:
-        out["dx0"] = xg.grad.clone()
-    return out
-
-
-def _same(a, b):
-    assert set(a) == set(b), sorted(set(a) ^ set(b))
-    for k in a:
-        assert torch.equal(a[k], b[k]), (k, float((a[k] - b[k]).abs().max()))
-
-
-def _launches(fn):
-    HF.profile_reset()
-    HF.profile_enable(True)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        HF.profile_enable(False)
-    return {k: v[1] for k, v in HF.profile_read().items() if v[1]}
-
-
-UNFUSED = {"head": {"WN_SERIES_HEAD": "0"}, "entry": {"WN_SERIES_FRONT": "0"}, "both": {"WN_SERIES_HEAD": "0", "WN_SERIES_FRONT": "0"}}
 
 
 @pytest.mark.parametrize("L", LENGTHS)
@@ -108,7 +53,7 @@ def test_fused_step_is_bitwise_the_op_by_op_step(stack, L):
             _same(fused, _step(net, inp, cot, levels, input_grad, env))
     # the fused step launches no stand-alone pack per block and one pack in all
     n = len(STACKS[stack])
-    ran = _launches(lambda: _step(net, x, cot))
+    _, ran = _launches(lambda: _step(net, x, cot))
     assert ran["pack_kernel"] == 1, ran
     assert ran["series_gemm_kernel<conv_fwd>"] == 3 and ran["series_gemm_kernel<conv_bwd_data>"] == 2, ran
     assert ran["series_gemm_kernel<skips_sum>"] == 1 and ran["series_gemm_kernel<gate>"] == n, ran
@@ -228,7 +173,7 @@ def test_heads_outside_the_pattern_run_op_by_op_and_match_fp64(kind):
     cot = torch.randn(B, MS, L + (2 if kind == "k3" else 0), generator=g)
     slopes, remove = O.capture_leaky_slopes(net)
     xg = x.to(DEV).requires_grad_(True)
-    ran = _launches(lambda: (net(xg) * cot.to(DEV)).sum().backward())
+    _, ran = _launches(lambda: (net(xg) * cot.to(DEV)).sum().backward())
     remove()
     assert set(slopes) == {"output_stack.0", "output_stack.2"}          # the LeakyReLU modules ran: the head was not fused
     # three convs forward in the measured pass (entry in the series, two of the head on their own) + three in the pattern pass
@@ -247,27 +192,6 @@ def test_heads_outside_the_pattern_run_op_by_op_and_match_fp64(kind):
     assert errs[worst] < TOL, errs
 
 
-def _train(net, x, cot, steps, graphed):
-    from wavenet_speech_amd.parallel import FlatGradAllReduce
-    opt = torch.optim.Adam(net.parameters(), lr=1e-2, fused=True, capturable=True)
-    sync = FlatGradAllReduce(net.parameters())
-    losses = []
-    if graphed:
-        g = W.GraphedStep(lambda: (net(x) * cot).sum(), net.parameters(), optimizer=opt, sync=sync, warmup=2)
-        for _ in range(steps):
-            losses.append(float(g()))
-        g.check()
-        return losses, 2
-    for _ in range(steps):
-        sync.zero()
-        loss = (net(x) * cot).sum()
-        loss.backward()
-        sync.reduce()
-        opt.step()
-        losses.append(float(loss.detach()))
-    return losses, 0
-
-
 def test_graphed_step_replays_bitwise_the_eager_steps():
     """a small fp32 WaveNet step captured by GraphedStep, replayed twice with a weight update between the replays, equals the eager
     steps.  The pack table is uploaded during the warm-up, outside the captured region; the one captured pack launch reads the
@@ -279,8 +203,8 @@ def test_graphed_step_replays_bitwise_the_eager_steps():
     cot = torch.randn(B, MS, L, generator=g).to(DEV)
     base = _net("three_k2", 9)
     nets = [copy.deepcopy(base), copy.deepcopy(base)]
-    lg, warm = _train(nets[1], x, cot, 2, graphed=True)
-    le, _ = _train(nets[0], x, cot, 2 + warm, graphed=False)     # the graphed run took `warm` eager steps before its capture
+    lg, warm = _train(nets[1], x, cot, 2, graphed=True, lr=1e-2)
+    le, _ = _train(nets[0], x, cot, 2 + warm, graphed=False, lr=1e-2)     # the graphed run took `warm` eager steps before its capture
     assert lg == le[warm:], (lg, le)
     assert lg[0] != lg[1]                                        # the weights did move between the replays
     for (k, a), (_, b) in zip(nets[0].state_dict().items(), nets[1].state_dict().items()):

@@ -20,35 +20,10 @@ import pytest
 import torch
 
 from oracle import wavenet_oracle as O
+from tests.gpu_stack import TOL, cycles_of as _layers, onehot as _onehot, properties as _properties, wavenet as _wavenet
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
-DEV = "cuda:0"
-
-
-def _layers(c, cycles):
-    return [(c, c, 2, 2 ** i) for _ in range(cycles) for i in range(10)]
-
-
-def _wavenet(c, layers, seed=0, conditioned=True):
-    from wavenet_speech_amd.modules.wavenet import WaveNet
-    torch.manual_seed(seed)
-    net = WaveNet(c, 2, layers, c, softmax=False)
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn(p.shape))
-        if conditioned:
-            for blk in net.convolutions:
-                blk.residual_proj.weight.copy_(torch.eye(blk.out_channels, blk.in_channels)
-                                               + 0.02 * torch.randn(blk.out_channels, blk.in_channels))
-                blk.conv1x1_residual.weight.mul_(0.3)
-    return net
-
-
-def _onehot(b, c, l, seed):
-    g = torch.Generator().manual_seed(seed)
-    return O.one_hot_encoding(torch.randint(0, c, (b, l), generator=g), c), torch.randn(b, c, l, generator=g)
 
 
 def test_cfg3_one_utterance_vs_oracle():
@@ -159,33 +134,6 @@ def test_cfg2_shape_raw_ctcnet_vs_oracle():
             assert p.grad is None, k
             continue
         assert O.rel_err(p.grad.cpu(), sd[k].grad) < TOL, k
-
-
-def _properties(net, x, cot, prefix, split, causal_prefix, additivity_tol=1e-5):
-    """size-independent properties at a configuration's full size: bitwise determinism of outputs and gradients,
-    [causality: prefix of the output == output of the prefix], batch additivity of the weight gradients,
-    per-utterance independence."""
-    def grads(xs, cs):
-        net.zero_grad(set_to_none=True)
-        y = net(xs)
-        (y * cs).sum().backward()
-        return y.detach(), {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}
-
-    y, g_all = grads(x, cot)
-    y2, g_again = grads(x, cot)
-    assert torch.equal(y, y2) and all(torch.equal(g_all[k], g_again[k]) for k in g_all)
-    assert bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in g_all.values())
-    if causal_prefix:
-        y_prefix = net(x[:, :, :prefix].contiguous()).detach()     # same grad mode as y (see test_cfg3_full_batch_properties)
-        assert torch.equal(y_prefix, y[:, :, :prefix])
-    _, g_a = grads(x[:split].contiguous(), cot[:split].contiguous())
-    _, g_b = grads(x[split:].contiguous(), cot[split:].contiguous())
-    for k in g_all:
-        assert O.rel_err((g_a[k] + g_b[k]).cpu(), g_all[k].cpu()) < additivity_tol, k
-    i = x.shape[0] - 1
-    yi = net(x[i:i + 1].contiguous()).detach()
-    assert torch.equal(yi[0], y[i])
-    return y
 
 
 def test_cfg2_full_batch_properties():

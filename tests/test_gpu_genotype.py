@@ -11,73 +11,17 @@ from tests import genotype_cases as K
 from tests import genotype_ref as G
 from tests import pileup_cases as C
 from tests import pileup_ref as P
+from tests.gpu_calls import TABLE, alignment as _alignment, assert_evidence as _assert_evidence, assert_genotypes as _assert_calls
+from tests.gpu_calls import evidence_both as _both, pile_dev as _pile_dev, weights as _weights
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 T, S = 256, 256
-TABLE = G.weights(100)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _i32(v):
-    return _dev(np.asarray(v, dtype=np.int32))
-
-
-def _weights(table=TABLE, scale=100):
-    return W.GenotypeWeights(torch.tensor(table, dtype=torch.int32), scale)
-
-
-def _alignment(ops_rows, ops_len):
-    return W.PairwiseAlignment(None, None, None, None, None, _dev(ops_rows), _i32(ops_len))
-
-
-def _assert_evidence(got, want):
-    assert got.evidence.dtype == torch.int64 and got.used.dtype == torch.int8 and tuple(got.evidence.shape) == (len(want.evidence), 5, 3)
-    assert got.used.cpu().tolist() == want.used.tolist()
-    assert got.evidence.cpu().tolist() == want.evidence
-
-
-def _both(ops, lo, n_ref, strand, query, R, table=TABLE, qual=None, keep=None, cap=None, ops_len=None, query_len=None, into=None, pile=False, **kw):
-    """the same reads through the reference and the kernel; the table and `used` must agree exactly -> (Evidence, reference Evidence)
-    and, with pile=True, the Pileup of the same batch beside them"""
-    ops_rows, lens = C.rows(ops, dtype=np.uint8)
-    ops_len = lens if ops_len is None else np.asarray(ops_len, dtype=np.int32)
-    q_rows, q_len = C.rows(query)
-    q_len = q_len if query_len is None else np.asarray(query_len, dtype=np.int32)
-    qual_rows = None if qual is None else C.rows(qual, width=q_rows.shape[1], dtype=np.uint8)[0]
-    want = G.evidence_ref(table, ops_rows, ops_len, lo, n_ref, strand, q_rows, q_len, R, qual=qual_rows, keep=keep, cap=cap,
-                          into=None if into is None else into[1].evidence, **kw)
-    args = (_alignment(ops_rows, ops_len), _i32(lo), _i32(n_ref), _i32(strand), _dev(q_rows), _i32(q_len), R)
-    common = dict(qual=None if qual is None else _dev(qual_rows), keep=None if keep is None else torch.tensor(keep, device=DEV))
-    got = W.pileup_evidence(*args, _weights(table), cap=None if cap is None else _dev(np.asarray(cap, dtype=np.uint8)),
-                            into=None if into is None else into[0], **common, **kw)
-    _assert_evidence(got, want)
-    if pile:
-        return got, want, W.pileup(*args, min_qual=kw.get("min_qual", 0), **common)
-    return got, want
-
-
-def _read(ops, rng, odd=0.1):
-    """(ops, n_ref, query, qual) with random labels, a share `odd` of them outside 1..4, and random quals"""
-    n_query = sum(v != 3 for v in ops)
-    query = [int(v) if rng.random() >= odd else int(rng.choice([0, 5, 9])) for v in rng.integers(1, 5, size=n_query)]
-    return list(ops), sum(v != 4 for v in ops), query, [int(v) for v in rng.integers(0, 94, size=n_query)]
-
-
-def _random_ops(rng, n):
-    return [int(v) for v in rng.choice([1, 2, 3, 4], size=n, p=[0.6, 0.2, 0.1, 0.1])]
-
-
-def _cols(reads):
-    return [r[0] for r in reads], [r[1] for r in reads], [r[2] for r in reads], [r[3] for r in reads]
 
 
 def test_tile_edges_on_both_strands():
     rng = np.random.default_rng(1)
-    strings = [_random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
+    strings = [C.random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
     strings += [[1] * (T - 6) + [4] * 12 + [1] * 9,                  # an insertion run and a deletion run across the first tile edge
                 [2] * (T - 6) + [3] * 12 + [2] * 9,
                 [3] * T + [1] * 20 + [4] * 3,                        # the first aligned column on a tile edge, end columns before it
@@ -86,8 +30,8 @@ def test_tile_edges_on_both_strands():
                 [3] * 7 + [1] * (T - 7) + [1] + [4] * 30,
                 [1] * T + [4, 4] + [3] + [4] + [1] * (T - 3)]
     strings += [s[::-1] for s in strings[4:]]                        # a reverse-strand read walks its columns back to front
-    reads = [_read(s, rng) for s in strings]
-    ops, n_ref, query, qual = _cols(reads)
+    reads = [C.read(s, rng) for s in strings]
+    ops, n_ref, query, qual = C.cols(reads)
     n = len(reads)
     cap = [int(v) for v in rng.integers(0, 120, size=n)]
     for strands in ([0] * n, [1] * n, [b & 1 for b in range(n)]):
@@ -98,8 +42,8 @@ def test_tile_edges_on_both_strands():
 
 def test_windows_clamped_at_both_ends_and_a_reference_of_one():
     rng = np.random.default_rng(2)
-    reads = [_read(_random_ops(rng, 70), rng, odd=0.0) for _ in range(6)] + [_read([1] * 40, rng, odd=0.0)] * 2
-    ops, n_ref, query, qual = _cols(reads)
+    reads = [C.read(C.random_ops(rng, 70), rng, odd=0.0) for _ in range(6)] + [C.read([1] * 40, rng, odd=0.0)] * 2
+    ops, n_ref, query, qual = C.cols(reads)
     R = max(n_ref)
     lo = [0 if b & 1 else R - r[1] for b, r in enumerate(reads[:6])] + [0, R - 40]          # a window at 0, a window that ends at R
     for strands in ([0] * 8, [1] * 8, [0, 1, 1, 0, 0, 1, 1, 0]):
@@ -113,8 +57,8 @@ def test_windows_clamped_at_both_ends_and_a_reference_of_one():
 
 def test_quals_caps_and_flat_qual():
     rng = np.random.default_rng(4)
-    reads = [_read([4, 1, 1, 4, 4, 4, 1, 3, 2, 1, 4], rng, odd=0.0) for _ in range(6)]
-    ops, n_ref, query, _ = _cols(reads)
+    reads = [C.read([4, 1, 1, 4, 4, 4, 1, 3, 2, 1, 4], rng, odd=0.0) for _ in range(6)]
+    ops, n_ref, query, _ = C.cols(reads)
     quals = [[9, 10, 11, 9, 10, 9, 10, 9, 10, 0], [10] * 10, [93] * 10, [0, 93, 0, 93, 0, 93, 0, 93, 0, 93], [0] * 10, [92, 93] * 5]
     args = (ops, [0, 1, 2, 3, 0, 1], n_ref, [0, 1, 0, 1, 1, 0], query, 12)
     for min_qual in (0, 1, 10, 11, 93):                              # quals 0 and 93 on both sides of min_qual
@@ -136,7 +80,7 @@ def test_quals_caps_and_flat_qual():
 
 def test_skipped_reads_are_not_looked_at():
     rng = np.random.default_rng(5)
-    good = _read([3, 1, 2, 4, 1, 3, 1, 4], rng, odd=0.0)
+    good = C.read([3, 1, 2, 4, 1, 3, 1, 4], rng, odd=0.0)
     ops = [good[0], good[0], good[0], [3] * 6, [3, 3, 3, 4, 4], good[0], [9] * 8]
     query = [good[2], good[2], good[2], [], [1, 2], good[2], good[2]]
     # unmapped (strand -1, with a window that would be bad), ref_lengths 0, keep false, empty, end columns only, good, unmapped garbage
@@ -148,7 +92,7 @@ def test_skipped_reads_are_not_looked_at():
 
 def test_bad_pairs_add_nothing_and_are_counted():
     rng = np.random.default_rng(6)
-    ops, n_ref, query, _ = _read([3, 1, 2, 4, 4, 1, 3, 1, 4], rng, odd=0.0)
+    ops, n_ref, query, _ = C.read([3, 1, 2, 4, 4, 1, 3, 1, 4], rng, odd=0.0)
     n_query = len(query)
     bad = [dict(ops=ops[:4] + [0] + ops[5:]), dict(ops=ops[:4] + [5] + ops[5:]), dict(ops=ops[:4] + [255] + ops[5:]), dict(ops_len=13),
            dict(ops_len=-1), dict(ops_len=8), dict(ops=ops[:-1] + [3]), dict(n_ref=n_ref + 1), dict(n_ref=n_ref - 1), dict(n_ref=-2),
@@ -187,12 +131,12 @@ def test_the_carry_of_a_true_64_bit_add():
 
 def test_contention_on_one_locus():
     rng = np.random.default_rng(8)
-    ops, n_ref, query, qual = _read([1] * 12 + [4, 4] + [1] * 10 + [3] + [2] * 17, rng, odd=0.05)
+    ops, n_ref, query, qual = C.read([1] * 12 + [4, 4] + [1] * 10 + [3] + [2] * 17, rng, odd=0.05)
     assert n_ref == 40
     got, want = _both([ops] * 300, [0] * 300, [40] * 300, [0] * 300, [query] * 300, 40, qual=[qual] * 300, gap_qual=2)
     assert want.evidence[22][4] == [300 * TABLE[t][2] for t in range(3)]
-    reads = [r for r in (_read(_random_ops(rng, 42), rng) for _ in range(300)) if r[1] <= 40]
-    ops, n_ref, query, qual = _cols(reads)
+    reads = [r for r in (C.read(C.random_ops(rng, 42), rng) for _ in range(300)) if r[1] <= 40]
+    ops, n_ref, query, qual = C.cols(reads)
     n = len(reads)
     got, want = _both(ops, [40 - r[1] if b % 3 else 0 for b, r in enumerate(reads)], n_ref, [int(v) for v in rng.integers(0, 2, size=n)], query, 40,
                       qual=qual, cap=[int(v) for v in rng.integers(0, 94, size=n)])
@@ -202,10 +146,10 @@ def test_contention_on_one_locus():
 
 def test_accumulation_over_batches_reproducibility_and_the_pileup_counts():
     rng = np.random.default_rng(9)
-    reads = [_read(_random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
-    args = lambda part, first=0: (_cols(part)[0], [2 * b for b in range(first, first + len(part))], _cols(part)[1],      # noqa: E731
-                                  [b & 1 for b in range(first, first + len(part))], _cols(part)[2], 400)
-    kw = lambda part: dict(qual=_cols(part)[3], min_qual=9)          # noqa: E731
+    reads = [C.read(C.random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
+    args = lambda part, first=0: (C.cols(part)[0], [2 * b for b in range(first, first + len(part))], C.cols(part)[1],      # noqa: E731
+                                  [b & 1 for b in range(first, first + len(part))], C.cols(part)[2], 400)
+    kw = lambda part: dict(qual=C.cols(part)[3], min_qual=9)          # noqa: E731
     whole, _ = _both(*args(reads), **kw(reads))
     again, _ = _both(*args(reads), **kw(reads))
     assert torch.equal(whole.evidence, again.evidence) and torch.equal(whole.used, again.used)   # bitwise: integer addition commutes
@@ -223,11 +167,11 @@ def test_accumulation_over_batches_reproducibility_and_the_pileup_counts():
 
 def test_strided_rows_and_int64_labels():
     rng = np.random.default_rng(10)
-    reads = [_read(_random_ops(rng, 90), rng) for _ in range(5)]
-    ops_rows, ops_len = C.rows(_cols(reads)[0], dtype=np.uint8)
-    q_rows, q_len = C.rows(_cols(reads)[2])
-    qual_rows = C.rows(_cols(reads)[3], width=q_rows.shape[1], dtype=np.uint8)[0]
-    lo, n_ref, strand = [0, 3, 6, 9, 12], _cols(reads)[1], [0, 1, 0, 1, 1]
+    reads = [C.read(C.random_ops(rng, 90), rng) for _ in range(5)]
+    ops_rows, ops_len = C.rows(C.cols(reads)[0], dtype=np.uint8)
+    q_rows, q_len = C.rows(C.cols(reads)[2])
+    qual_rows = C.rows(C.cols(reads)[3], width=q_rows.shape[1], dtype=np.uint8)[0]
+    lo, n_ref, strand = [0, 3, 6, 9, 12], C.cols(reads)[1], [0, 1, 0, 1, 1]
     want = G.evidence_ref(TABLE, ops_rows, ops_len, lo, n_ref, strand, q_rows, q_len, 120, qual=qual_rows, min_qual=12)
     wide = lambda a, fill: _dev(np.concatenate([a, np.full((a.shape[0], 37), fill, dtype=a.dtype)], axis=1))    # noqa: E731
     ops_wide, q_wide, qual_wide = wide(ops_rows, 7), wide(q_rows.astype(np.int64), 2), wide(qual_rows, 200)
@@ -241,31 +185,13 @@ def test_strided_rows_and_int64_labels():
 
 # ---- call_genotypes -------------------------------------------------------------------------------------------------------------
 
-def _assert_calls(got, want):
-    assert got.alleles.dtype == got.flags.dtype == got.ins_copies.dtype == got.ins_len.dtype == got.ins_bases.dtype == torch.uint8
-    assert got.gq.dtype == got.qual.dtype == got.ins_gq.dtype == got.ins_qual.dtype == torch.int32
-    for name in ("alleles", "gq", "qual", "flags", "ins_copies", "ins_len", "ins_bases", "ins_gq", "ins_qual"):
-        g, w = getattr(got, name).cpu().numpy(), getattr(want, name)
-        assert g.shape == w.shape and np.array_equal(g.astype(np.int64), w.astype(np.int64)), name
-    if got.costs is not None:
-        assert got.costs.dtype == torch.int64 and got.costs.cpu().tolist() == want.costs
-
-
 def _calls_both(pile, evidence, ref, table=TABLE, **kw):
     """pile: a pileup_ref Pile of numpy tables; evidence: nested lists [R][5][3] -> (Genotypes, reference Calls), equal exactly"""
     want = G.call_genotypes_ref(pile, evidence, ref, table, **kw)
-    dev_pile = W.Pileup(_dev(pile.counts.astype(np.int32)), _dev(pile.ins_lengths.astype(np.int32)), _dev(pile.ins_bases.astype(np.int32)), None)
-    got = W.call_genotypes(dev_pile, W.Evidence(torch.tensor(evidence, dtype=torch.int64, device=DEV), None), _dev(np.asarray(ref, dtype=np.int64)),
+    got = W.call_genotypes(_pile_dev(pile), W.Evidence(torch.tensor(evidence, dtype=torch.int64, device=DEV), None), _dev(np.asarray(ref, dtype=np.int64)),
                            _weights(table), return_costs=True, **kw)
     _assert_calls(got, want)
     return got, want
-
-
-def _random_pile(rng, R, max_ins, top=4):
-    counts = rng.integers(0, top, size=(R, 2, 6))
-    ins_lengths = rng.integers(0, top, size=(R, max_ins + 1)) * (rng.random((R, 1)) < 0.5)
-    ins_bases = rng.integers(0, 3, size=(R, max_ins, 4)) * (rng.random((R, max_ins, 1)) < 0.7)
-    return P.Pile(counts.astype(np.int64), ins_lengths.astype(np.int64), ins_bases.astype(np.int64), None, 0)
 
 
 @pytest.mark.parametrize("R", [1, S - 1, S, S + 1])
@@ -273,12 +199,11 @@ def test_call_genotypes_at_the_tile_edges(R):
     rng = np.random.default_rng(R)
     ref = rng.integers(0, 6, size=R)
     for max_ins, min_depth, prior, gap_qual in ((2, 3, 3000, 20), (0, 1, 0, 0), (8, 6, 7, 93), (3, 4, 2 ** 30, 5)):
-        pile = _random_pile(rng, R, max_ins)
+        pile = C.random_pile(rng, R, max_ins)
         evidence = (rng.integers(0, 40, size=(R, 5, 3)) * (rng.random((R, 5, 1)) < 0.6)).tolist()      # small: ties are common
         got, want = _calls_both(pile, evidence, ref, min_depth=min_depth, alt_prior=prior, gap_qual=gap_qual)
         assert tuple(got.costs.shape) == (R, 15) and tuple(got.ins_bases.shape) == (R, max_ins)
-    plain = W.call_genotypes(W.Pileup(_dev(pile.counts.astype(np.int32)), _dev(pile.ins_lengths.astype(np.int32)), _dev(pile.ins_bases.astype(np.int32)),
-                                      None), W.Evidence(torch.tensor(evidence, device=DEV), None), _dev(ref), _weights())
+    plain = W.call_genotypes(_pile_dev(pile), W.Evidence(torch.tensor(evidence, device=DEV), None), _dev(ref), _weights())
     assert plain.costs is None and tuple(plain.alleles.shape) == (R, 2)
 
 

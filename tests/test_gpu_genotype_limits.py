@@ -12,26 +12,12 @@ from tests import call_limits_cases as K
 from tests import genotype_ref as G
 from tests import pileup_limits_cases as L
 from tests import pileup_ref as P
-from tests.test_gpu_genotype import DEV, _alignment, _assert_calls, _assert_evidence, _dev, _i32, _weights
-from tests.test_gpu_pileup import U, _assert_pile
+from tests.gpu_calls import U, assert_evidence as _assert_evidence, assert_genotypes as _assert_calls, assert_pile as _assert_pile
+from tests.gpu_calls import capture as _capture, copy_reads as _copy_reads, pile_rules as _pile_rules, reads_dev as _reads_dev
+from tests.gpu_calls import rules_dev as _rules_dev, weights as _weights
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
-
-
-def _reads_dev(reads):
-    """a Reads as the leading arguments of pileup, pileup_evidence, phase_links and haplotag"""
-    return (_alignment(reads.ops, reads.ops_len), _i32(reads.lo), _i32(reads.n_ref), _i32(reads.strand), _dev(reads.query), _i32(reads.query_len))
-
-
-def _rules_dev(rules):
-    """the keyword arguments of K.rules() / K.small_rules() with their arrays on the device"""
-    on = lambda v: None if v is None else _dev(v)                    # noqa: E731
-    return dict(rules, qual=on(rules["qual"]), cap=on(rules["cap"]), **({"keep": on(rules["keep"])} if "keep" in rules else {}))
-
-
-def _pile_rules(rules):
-    """what pileup takes of them: it knows no cap and no gap_qual"""
-    return {k: v for k, v in rules.items() if k in ("qual", "min_qual", "keep")}
 
 
 def _run(name, strand=None):
@@ -97,29 +83,6 @@ def test_call_genotypes_on_the_size_limit_pile():
 
 
 # ---- captured into a graph ------------------------------------------------------------------------------------------------------
-
-def _capture(step):
-    """step() run once eagerly on a side stream (it warms the allocator there), then captured on it -> (graph, what the captured
-    call returned)"""
-    torch.cuda.synchronize()
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        step()
-    torch.cuda.current_stream().wait_stream(stream)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=stream):
-        captured = step()
-    return graph, captured
-
-
-def _copy_reads(args, rules, reads, qual, cap):
-    """another batch of the same shapes, written over the tensors the graph reads"""
-    for t, a in zip((args[0].ops, args[0].ops_len) + args[1:], (reads.ops, reads.ops_len, reads.lo, reads.n_ref, reads.strand, reads.query, reads.query_len)):
-        t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-    rules["qual"].copy_(torch.from_numpy(qual))
-    rules["cap"].copy_(torch.from_numpy(cap))
-
 
 def test_evidence_and_calls_captured_into_a_graph():
     """pileup_evidence(into=) and call_genotypes in one capture: the weight table travels by value, nothing is read back.  The pile is

@@ -8,30 +8,9 @@ import torch
 import wavenet_speech_amd as W
 from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
 from wavenet_speech_amd.modules.wavenet import WaveNet
-from wavenet_speech_amd.parallel import FlatGradAllReduce
+from tests.gpu_stack import train as _train
 
 pytestmark = pytest.mark.gpu
-
-
-def _train(net, x, cot, steps, graphed):
-    opt = torch.optim.Adam(net.parameters(), lr=1e-3, fused=True, capturable=True)
-    sync = FlatGradAllReduce(net.parameters())
-    losses = []
-    if graphed:
-        xs, cs = x.clone(), cot.clone()
-        g = W.GraphedStep(lambda: (net(xs) * cs).sum(), net.parameters(), optimizer=opt, sync=sync, warmup=2)
-        for _ in range(steps):
-            losses.append(float(g()))
-        g.check()
-        return losses, 2
-    for _ in range(steps):
-        sync.zero()
-        loss = (net(x) * cot).sum()
-        loss.backward()
-        sync.reduce()
-        opt.step()
-        losses.append(float(loss.detach()))
-    return losses, 0
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16", "f16x3"])
@@ -46,8 +25,8 @@ def test_graphed_steps_equal_eager_steps(precision):
     for n in nets:
         W.set_precision(n, precision)
     # the graphed run performs `warm` extra eager steps before capture: give the eager run the same head start
-    lg, warm = _train(nets[1], x, cot, 3, graphed=True)
-    le, _ = _train(nets[0], x, cot, 3 + warm, graphed=False)
+    lg, warm = _train(nets[1], x, cot, 3, graphed=True, lr=1e-3)
+    le, _ = _train(nets[0], x, cot, 3 + warm, graphed=False, lr=1e-3)
     assert lg == le[warm:], (lg, le)
     for (k, a), (_, b) in zip(nets[0].state_dict().items(), nets[1].state_dict().items()):
         assert torch.equal(a, b), k

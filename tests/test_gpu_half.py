@@ -12,12 +12,12 @@ import wavenet_speech_amd as W
 from oracle import wavenet_oracle as O
 from tests import goldenio
 from tests import halfref as R
+from tests.gpu_stack import PLAIN, TOL, condition as _condition, cycles_of as _layers, launched as _launched, onehot as _onehot
+from tests.gpu_stack import properties as _properties, run_golden as _run_golden, wavenet as _wavenet
+from tests.gpu_util import DEV
 from wavenet_speech_amd import functional as HF
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL = 1e-4
-PLAIN = ("f16", "bf16")
 
 
 def _cond_wavenet(c, layers, in_dim=None, seed=0, out_dim=None):
@@ -25,20 +25,6 @@ def _cond_wavenet(c, layers, in_dim=None, seed=0, out_dim=None):
     torch.manual_seed(seed)
     net = WaveNet(in_dim or c, 2, layers, out_dim or c, softmax=False)
     _condition(net)
-    return net
-
-
-def _condition(net):
-    """noisy biases and a conditioned residual path, as in a trained network"""
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn(p.shape))
-        blocks = list(net.convolutions) + ([net.input_block] if hasattr(net, "input_block") else [])
-        for blk in blocks:
-            blk.residual_proj.weight.copy_(torch.eye(blk.out_channels, blk.in_channels)
-                                           + 0.02 * torch.randn(blk.out_channels, blk.in_channels))
-            blk.conv1x1_residual.weight.mul_(0.3)
     return net
 
 
@@ -67,10 +53,6 @@ def _half_ref(net, precision, slopes, layers_override=None):
     fused = fusable_head(net.output_stack, precision) is not None
     layers = layers_override or [(b.in_channels, b.out_channels, b.kernel_width, b.dilation) for b in net.convolutions]
     return lambda x, sd, fmt: R.wavenet(x, sd, layers, fmt, slopes=slopes, fused_head=fused)
-
-
-def _launched():
-    return {k: v[1] for k, v in HF.profile_read().items() if v[1]}
 
 
 def _run(net, x, cot, layers, precision, tol=None, replay_slopes=True, input_grad=True, kernels=None, label="", mutants=None):
@@ -199,10 +181,9 @@ def test_f16x3_mixed_widths_k3_and_dilation_beyond_length():
 @pytest.mark.parametrize("name", goldenio.names("wavenet_") + goldenio.names("rawctc_") + goldenio.names("classifier_"))
 def test_f16x3_golden_models(name):
     """the reference's own outputs and autograd gradients (tests/golden) through the f16x3 stack, same tolerance as fp32"""
-    from tests.test_gpu_parity import _mods, _run_golden
     g = goldenio.load(name)
     m = g.meta
-    M = _mods()
+    import wavenet_speech_amd.modules as M
     if m["kind"] == "wavenet":
         net = M.WaveNet(m["in_dim"], m["entry_kwidth"], m["layers"], m["out_dim"], softmax=m["softmax"])
     elif m["kind"] == "rawctc":
@@ -321,7 +302,6 @@ def test_fp16_overflow_is_loud():
 
 def test_f16x3_cfg3_one_utterance_vs_oracle():
     """the full configs[2] utterance (256 ch x 30 blocks x 16000 steps) at the fp32 path's own 1e-4 bar"""
-    from tests.test_gpu_fullsize import _layers, _onehot, _wavenet
     c, L = 256, 16000
     layers = _layers(c, 3)
     net = _wavenet(c, layers)
@@ -335,7 +315,6 @@ def test_f16x3_survives_the_reference_init_at_30_blocks():
     built-in power-of-two scales leave (no overflow error).  This map is ill-conditioned (two CPU fp32 summation orders
     differ by 4.5e-4 themselves); hi+lo carries 22-23 significant bits against fp32's 24, and the
     amplification multiplies that: the f16x3 result is allowed 10x the CPU fp32 path's own distance from fp64."""
-    from tests.test_gpu_fullsize import _layers, _onehot, _wavenet
     c, L = 256, 4000
     layers = _layers(c, 3)
     net = _wavenet(c, layers, seed=7, conditioned=False)
@@ -357,7 +336,6 @@ def test_f16x3_survives_the_reference_init_at_30_blocks():
 def test_cfg2_bf16_full_batch():
     """BASELINE configs[1] as stated: RawCTCNet 128 ch x (10 + input) blocks, L=4096, batch 32, bf16.  Size-independent
     properties at the full size plus one utterance against the oracle; the bf16 error is the storage format's (8 bits)."""
-    from tests.test_gpu_fullsize import _properties
     from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
     torch.manual_seed(12)
     layers = [(128, 128, 2, 2 ** i) for i in range(10)]
@@ -381,7 +359,6 @@ def test_cfg2_bf16_full_batch():
 def test_cfg5_f16_full_depth_and_length():
     """BASELINE configs[4]'s shape on one GPU in its stated dtype: WaveNet 512 ch x 60 blocks x L=48000, batch 2, fp16
     (conditioned residual path: 60 random-init blocks amplify by ~2^30, beyond fp16 whatever the kernel)."""
-    from tests.test_gpu_fullsize import _layers, _properties, _wavenet
     c, L, B = 512, 48000, 2
     layers = _layers(c, 6)
     net = _wavenet(c, layers, seed=21).to(DEV)
@@ -395,7 +372,6 @@ def test_cfg5_f16_full_depth_and_length():
 def test_cfg5_f16_full_depth_gradients_vs_rounding_reference():
     """all 60 blocks of configs[4] (512 ch, f16) on one utterance of 3000 steps: forward, dx and every parameter gradient against
     the rounding reference (tests/halfref.py)"""
-    from tests.test_gpu_fullsize import _layers, _wavenet
     c, L = 512, 3000
     layers = _layers(c, 6)
     net = _wavenet(c, layers, seed=23)

@@ -24,10 +24,9 @@ import torch.nn.functional as F
 
 from oracle import wavenet_oracle as O
 from tests import halfref as R
+from tests.gpu_stack import PLAIN, TOL, condition as _condition, launched as _launched, plain_slopes as _plain_slopes
+from tests.gpu_util import DEV
 
-DEV = "cuda:0"
-TOL = 1e-4
-PLAIN = ("f16", "bf16")
 PRECISIONS = ("f32", "f16x3", "bf16", "f16")
 MUTANTS = ("nll x B", "ctc not / T'", "classifier dx dropped", "labels not shifted")
 
@@ -43,7 +42,6 @@ CASES = {  # levels, WaveNet layers, classifier layers, classifier out_dim, num_
 def make_case(name):
     """(wavenet, classifier, sig one-hot [B, levels, L], seq [B, S] labels in 1 .. num_labels - 2, lengths) on the CPU.  Labels avoid 0
     so that the un-shifted labels of the mutant reference are still legal (never the blank)."""
-    from tests.test_gpu_half import _condition
     from wavenet_speech_amd.modules import WaveNet, WaveNetClassifier
     levels, wl, cl, cout, nlab, pool, L, lens = CASES[name]
     torch.manual_seed(len(name) + L)
@@ -99,8 +97,6 @@ def test_reference_cases_have_finite_ctc(case):
 def gpu_step(wavenet, ctcnet, sig, seq, lengths, precision):
     """the two halves of joint_losses by hand, so that pred's gradient can be kept: (tensors, slopes of both networks, launched)"""
     import wavenet_speech_amd as W
-    from tests.test_gpu_classifier import _Env, _plain_slopes
-    from tests.test_gpu_half import _launched
     from wavenet_speech_amd import functional as HF
     from wavenet_speech_amd import training as T
     wavenet, ctcnet = wavenet.to(DEV), ctcnet.to(DEV)

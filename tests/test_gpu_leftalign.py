@@ -11,22 +11,11 @@ import wavenet_speech_amd as W
 from tests import leftalign_cases as K
 from tests import leftalign_ref as L
 from tests import pileup_cases as C
+from tests.gpu_calls import alignment as _alignment
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 A_, G_, C_, T_ = 1, 2, 3, 4
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _i32(v):
-    return _dev(np.asarray(v, dtype=np.int32))
-
-
-def _alignment(ops_rows, ops_len):
-    return W.PairwiseAlignment(None, None, None, None, None, _dev(ops_rows), _i32(ops_len))
 
 
 def _assert_equal(got, want):

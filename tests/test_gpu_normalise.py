@@ -9,17 +9,13 @@ import torch
 import wavenet_speech_amd as W
 from tests import read_stats_cases as C
 from tests import read_stats_ref as R
+from tests.gpu_util import DEV, dev as _dev
 from wavenet_speech_amd import normalise as N
 from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 T = N.TILE
 LINEAR_BOUND = 2.0 ** -22          # "linear" quantiles and 1 / (1.4826 mad): see tests/test_read_stats_ref.py and the docstrings below
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _select(x, lengths, ranks, centers=None, bad=None):

@@ -10,13 +10,9 @@ import torch
 import wavenet_speech_amd as W
 from tests import genotype_ref as G
 from tests import opwalk_cases as K
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _report():

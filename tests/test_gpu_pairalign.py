@@ -12,68 +12,14 @@ import pytest
 import torch
 
 from tests import pairwise_align_ref as R
+from tests.gpu_labels import check_pair as _check_pair, check_pair_batch as _check_batch, package as _W, pad_rows as _pad, pair_align as _align
+from tests.gpu_util import DEV, peaked_logits as _peaked_logits
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "emboss_pairs.json")
 BASES = {"A": 1, "G": 2, "C": 3, "T": 4}
 COST_SETS = {"emboss": R.EMBOSS, "unit": R.UNIT, "open_eq_extend": (2, -3, 2, 2)}      # integers: half units
 INT_MIN = -2 ** 31
-
-
-def _W():
-    import wavenet_speech_amd as W
-    return W
-
-
-def _pad(rows, width=None, fill=0, dtype=torch.int32):
-    width = max([len(r) for r in rows] + [1]) if width is None else width
-    out = np.full((len(rows), width), fill, dtype=np.int64)
-    for n, r in enumerate(rows):
-        out[n, :len(r)] = r
-    return torch.tensor(out, dtype=dtype), torch.tensor([len(r) for r in rows], dtype=torch.int32)
-
-
-def _align(refs, queries, costs, free, ref_width=None, query_width=None, fill=0, dtype=torch.int32, return_ops=True):
-    """the device result of a batch of label lists as numpy arrays: score in half units (int), stats [B][4], ops, ops_len"""
-    a, an = _pad(refs, ref_width, fill, dtype)
-    b, bn = _pad(queries, query_width, fill, dtype)
-    out = _W().pairwise_align(a.to(DEV), an.to(DEV), b.to(DEV), bn.to(DEV), match=costs[0] / 2, mismatch=costs[1] / 2,
-                              gap_open=costs[2] / 2, gap_extend=costs[3] / 2, end_gaps_free=free, return_ops=return_ops)
-    torch.cuda.synchronize()
-    assert out.score.dtype == torch.float32 and out.score.is_cuda and out.matches.dtype == torch.int32
-    score2 = (out.score.double() * 2).cpu().numpy()
-    assert (score2 == np.round(score2)).all()
-    stats = torch.stack([out.matches, out.mismatches, out.gaps, out.length], dim=1).cpu().numpy()
-    if not return_ops:
-        assert out.ops is None and out.ops_len is None
-        return score2.astype(np.int64), stats, None, None
-    assert out.ops.dtype == torch.uint8 and out.ops.shape == (len(refs), a.shape[1] + b.shape[1]) and out.ops_len.dtype == torch.int32
-    return score2.astype(np.int64), stats, out.ops.cpu().numpy(), out.ops_len.cpu().numpy()
-
-
-def _check_pair(a, b, costs, free, score, stats, ops, ops_len, tag=""):
-    """one pair of a device result: equal to the reference in every number, and consistent in itself"""
-    want = R.align(a, b, *costs, free)
-    assert score == want.score, (tag, score, want.score)
-    assert tuple(stats) == (want.matches, want.mismatches, want.gaps, want.length), (tag, tuple(stats), want[1:5])
-    if ops is None:
-        return want
-    assert ops_len == want.length, (tag, ops_len, want.length)
-    got = ops[:ops_len]
-    assert np.array_equal(got, want.ops), (tag, np.nonzero(got != want.ops)[0][:10])
-    assert (ops[ops_len:] == 0).all(), tag
-    # without the reference: both rows come out exactly once, the ops rescore to the score, the counts are the op counts
-    assert R.replay(a, b, got) == (list(a), list(b)), tag
-    assert R.rescore(got, *costs, free) == score, tag
-    assert (int((got == 1).sum()), int((got == 2).sum()), int((got >= 3).sum()), len(got)) == tuple(stats), tag
-    return want
-
-
-def _check_batch(refs, queries, costs, free, got, tag=""):
-    score, stats, ops, ops_len = got
-    return [_check_pair(a, b, costs, free, int(score[n]), stats[n], None if ops is None else ops[n],
-                        None if ops is None else int(ops_len[n]), "%s[%d]" % (tag, n)) for n, (a, b) in enumerate(zip(refs, queries))]
 
 
 def _mutate(rng, ref, rate, alphabet):
@@ -346,22 +292,6 @@ def test_cpu_tensors_and_bad_arguments_raise():
 
 
 # --------------------------------------------------------------------------------------------------------------- 6. end to end
-
-def _peaked_logits(seed, B, C, T, margin=5.0):
-    """the 'trained-looking' generator of tests/test_gpu_decode.py (same draws), returning its run path [B][T] too"""
-    rng = np.random.default_rng(seed)
-    x = rng.normal(size=(B, C, T)) * 1.0
-    path = np.zeros((B, T), dtype=np.int64)
-    for b in range(B):
-        t = 0
-        while t < T:
-            c = int(rng.integers(0, C))
-            d = int(rng.integers(1, 6))
-            x[b, c, t:t + d] += margin * rng.uniform(0.6, 1.0)
-            path[b, t:t + d] = c
-            t += d
-    return torch.tensor(x, dtype=torch.float32), path
-
 
 def _collapse(path):
     out, prev = [], 0

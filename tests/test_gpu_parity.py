@@ -8,45 +8,15 @@ import torch
 
 from oracle import wavenet_oracle as O
 from tests import goldenio
+from tests.gpu_stack import TOL, run_golden as _run_golden
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
-DEV = "cuda:0"
 
 
 def _mods():
     import wavenet_speech_amd.modules as M
     return M
-
-
-def _compare_grads(g, module, tol=TOL):
-    for k, p in module.named_parameters():
-        if not g.hasgrad[k]:
-            continue
-        assert p.grad is not None, k
-        err = O.rel_err(p.grad.cpu(), g.grads[k])
-        assert err < tol, (g.name, k, err)
-
-
-def _run_golden(g, module, tol=TOL):
-    missing = module.load_state_dict(g.sd, strict=True)  # reference checkpoints must load unchanged
-    assert not missing.missing_keys and not missing.unexpected_keys
-    module = module.to(DEV)
-    x = g.inputs["x"].to(DEV).requires_grad_(True)
-    outs = module(x)
-    if not isinstance(outs, tuple):
-        outs = (outs,)
-    assert len(outs) == len(g.outs)
-    loss = 0
-    for o, ref, cot in zip(outs, g.outs, g.cots):
-        assert tuple(o.shape) == tuple(ref.shape)
-        err = O.rel_err(o.detach().cpu(), ref)
-        assert err < tol, (g.name, "forward", err)
-        loss = loss + (o * cot.to(DEV)).sum()
-    loss.backward()
-    _compare_grads(g, module, tol)
-    err = O.rel_err(x.grad.cpu(), g.grad_inputs["x"])
-    assert err < tol, (g.name, "dx", err)
 
 
 @pytest.mark.parametrize("name", goldenio.names("conv_"))

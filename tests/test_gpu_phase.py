@@ -14,30 +14,12 @@ from tests import phase_cases as PC
 from tests import phase_ref as H
 from tests import pileup_cases as C
 from tests import pileup_ref as P
+from tests.gpu_calls import alignment as _alignment, assert_chain as _assert_chain, assert_counts as _assert_counts, assert_links as _assert_links
+from tests.gpu_calls import assert_tags as _assert_tags, host_rows as _rows, links_both as _both, sites_dev as _sites_dev, tags_both as _tags_both
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 T = 256
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _i32(v):
-    return _dev(np.asarray(v, dtype=np.int32))
-
-
-def _u8(v):
-    return _dev(np.asarray(v, dtype=np.uint8))
-
-
-def _alignment(ops_rows, ops_len):
-    return W.PairwiseAlignment(None, None, None, None, None, _dev(ops_rows), _i32(ops_len))
-
-
-def _sites_dev(sites):
-    return W.PhaseSites(_i32(sites.pos), _u8(np.asarray(sites.alleles, dtype=np.uint8).reshape(-1, 2)), _i32(sites.site_of))
 
 
 def _random_sites(rng, R, density=0.15, forced=()):
@@ -53,77 +35,20 @@ def _random_sites(rng, R, density=0.15, forced=()):
     return H.Sites(pos, alleles, site_of)
 
 
-def _rows(ops, query, qual, ops_len, query_len):
-    ops_rows, lens = C.rows(ops, dtype=np.uint8)
-    q_rows, q_len = C.rows(query)
-    qual_rows = None if qual is None else C.rows(qual, width=q_rows.shape[1], dtype=np.uint8)[0]
-    return (ops_rows, lens if ops_len is None else np.asarray(ops_len, dtype=np.int32), q_rows,
-            q_len if query_len is None else np.asarray(query_len, dtype=np.int32), qual_rows)
-
-
-def _assert_links(got, want):
-    S = len(want.observed)
-    assert got.links.dtype == torch.int64 and got.observed.dtype == torch.int32 and got.used.dtype == torch.int8
-    assert tuple(got.links.shape) == (S, len(want.links[0]) if S else got.links.shape[1], 2) and tuple(got.observed.shape) == (S, 3)
-    assert got.used.cpu().tolist() == want.used.tolist()
-    assert got.observed.cpu().tolist() == want.observed
-    assert got.links.cpu().tolist() == want.links
-
-
-def _both(sites, ops, lo, n_ref, strand, query, qual=None, keep=None, cap=None, ops_len=None, query_len=None, into=None, reach=4, pile=False, **kw):
-    """the same reads through the reference and the kernel; links, observed and `used` must agree exactly -> (PhaseLinks, reference
-    Links) and, with pile=True, the Pileup of the same batch beside them"""
-    ops_rows, ops_len, q_rows, q_len, qual_rows = _rows(ops, query, qual, ops_len, query_len)
-    want = H.links_ref(sites, ops_rows, ops_len, lo, n_ref, strand, q_rows, q_len, qual=qual_rows, keep=keep, cap=cap, reach=reach,
-                       into=None if into is None else into[1], **kw)
-    args = (_alignment(ops_rows, ops_len), _i32(lo), _i32(n_ref), _i32(strand), _dev(q_rows), _i32(q_len))
-    common = dict(qual=None if qual is None else _dev(qual_rows), keep=None if keep is None else torch.tensor(keep, device=DEV))
-    got = W.phase_links(*args, _sites_dev(sites), cap=None if cap is None else _u8(cap), reach=reach, into=None if into is None else into[0],
-                        **common, **kw)
-    _assert_links(got, want)
-    if pile:
-        return got, want, W.pileup(*args, len(sites.site_of), min_qual=kw.get("min_qual", 0), **common)
-    return got, want
-
-
-def _assert_counts(observed, sites, pile):
-    """observed[s] against the pileup's counts at pos[s] over both strands: label k is column k - 1, a deletion column 4"""
-    counts = pile.counts.sum(1).cpu().tolist()
-    for s, (p, (a0, a1)) in enumerate(zip(sites.pos, sites.alleles)):
-        col = lambda label: 4 if label == 0 else label - 1           # noqa: E731
-        assert observed[s][0] == counts[p][col(a0)] and observed[s][1] == counts[p][col(a1)], (s, p)
-        assert sum(observed[s]) == sum(counts[p][:5]), (s, p)
-
-
-def _read(ops, rng, odd=0.1):
-    """(ops, n_ref, query, qual) with random labels, a share `odd` of them outside 1..4, and random quals"""
-    n_query = sum(v != 3 for v in ops)
-    query = [int(v) if rng.random() >= odd else int(rng.choice([0, 5, 9])) for v in rng.integers(1, 5, size=n_query)]
-    return list(ops), sum(v != 4 for v in ops), query, [int(v) for v in rng.integers(0, 94, size=n_query)]
-
-
-def _random_ops(rng, n):
-    return [int(v) for v in rng.choice([1, 2, 3, 4], size=n, p=[0.6, 0.2, 0.1, 0.1])]
-
-
-def _cols(reads):
-    return [r[0] for r in reads], [r[1] for r in reads], [r[2] for r in reads], [r[3] for r in reads]
-
-
 # ---- phase_links ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("reach", [1, 8])
 def test_links_at_the_tile_edges_on_both_strands(reach):
     rng = np.random.default_rng(1)
-    strings = [_random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
+    strings = [C.random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
     strings += [[1] * (2 * T + 1),                                   # column c is position lo + c: sites in the first and last column, on the tile edges
                 [2] * (T - 6) + [3] * 12 + [2] * 9,                  # a deletion run of sites across the first tile edge
                 [3] * T + [1] * 20 + [4] * 3,                        # the first aligned column on a tile edge, end columns before it
                 [4] * 7 + [1] * (T - 8) + [1] + [3] * 30,            # the last aligned column at T - 1
                 [1] * T + [4, 4] + [3] + [4] + [1] * (T - 3)]
     strings += [s[::-1] for s in strings[5:]]                        # a reverse-strand read walks its columns back to front
-    reads = [_read(s, rng) for s in strings]
-    ops, n_ref, query, qual = _cols(reads)
+    reads = [C.read(s, rng) for s in strings]
+    ops, n_ref, query, qual = C.cols(reads)
     n = len(reads)
     R = 2 * T + 1
     lo = [0 if b % 2 == 0 else R - n_ref[b] for b in range(n)]       # windows at 0 and windows that end at R
@@ -170,7 +95,7 @@ def test_a_read_that_holds_reach_plus_3_sites(reach):
 
 def test_skipped_reads_are_not_looked_at():
     rng = np.random.default_rng(5)
-    good = _read([3, 1, 2, 4, 1, 3, 1, 4], rng, odd=0.0)
+    good = C.read([3, 1, 2, 4, 1, 3, 1, 4], rng, odd=0.0)
     ops = [good[0], good[0], good[0], [3] * 6, [3, 3, 3, 4, 4], good[0], [9] * 8]
     query = [good[2], good[2], good[2], [], [1, 2], good[2], good[2]]
     sites = _random_sites(rng, 8, 1.0)
@@ -234,14 +159,14 @@ def test_the_carry_of_a_true_64_bit_add():
 
 def test_contention_on_one_locus():
     rng = np.random.default_rng(8)
-    ops, n_ref, query, qual = _read([1] * 12 + [4, 4] + [1] * 10 + [3] + [2] * 17, rng, odd=0.05)
+    ops, n_ref, query, qual = C.read([1] * 12 + [4, 4] + [1] * 10 + [3] + [2] * 17, rng, odd=0.05)
     assert n_ref == 40
     sites = _random_sites(rng, 40, 0.0, forced=(2, 9, 17, 22, 30, 39))      # 6 sites; position 22 is the deletion column
     sites = sites._replace(alleles=[(1, 0) if p == 22 else a for p, a in zip(sites.pos, sites.alleles)])
     got, want = _both(sites, [ops] * 300, [0] * 300, [40] * 300, [0] * 300, [query] * 300, qual=[qual] * 300, gap_qual=2, reach=8)
     assert want.observed[3] == [0, 300, 0] and sum(sum(c) for c in want.links[5]) % 300 == 0 and sum(sum(c) for c in want.links[3]) > 0
-    reads = [r for r in (_read(_random_ops(rng, 42), rng) for _ in range(300)) if r[1] <= 40]
-    ops, n_ref, query, qual = _cols(reads)
+    reads = [r for r in (C.read(C.random_ops(rng, 42), rng) for _ in range(300)) if r[1] <= 40]
+    ops, n_ref, query, qual = C.cols(reads)
     n = len(reads)
     got, want = _both(sites, ops, [40 - r[1] if b % 3 else 0 for b, r in enumerate(reads)], n_ref, [int(v) for v in rng.integers(0, 2, size=n)], query,
                       qual=qual, cap=[int(v) for v in rng.integers(0, 94, size=n)], reach=5)
@@ -251,11 +176,11 @@ def test_contention_on_one_locus():
 
 def test_accumulation_over_batches_and_reproducibility():
     rng = np.random.default_rng(9)
-    reads = [_read(_random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
+    reads = [C.read(C.random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
     sites = _random_sites(rng, 400, 0.1)
-    args = lambda part, first=0: (_cols(part)[0], [2 * b for b in range(first, first + len(part))], _cols(part)[1],      # noqa: E731
-                                  [b & 1 for b in range(first, first + len(part))], _cols(part)[2])
-    kw = lambda part: dict(qual=_cols(part)[3], min_qual=9)          # noqa: E731
+    args = lambda part, first=0: (C.cols(part)[0], [2 * b for b in range(first, first + len(part))], C.cols(part)[1],      # noqa: E731
+                                  [b & 1 for b in range(first, first + len(part))], C.cols(part)[2])
+    kw = lambda part: dict(qual=C.cols(part)[3], min_qual=9)          # noqa: E731
     whole, _, pile = _both(sites, *args(reads), pile=True, **kw(reads))
     again, _ = _both(sites, *args(reads), **kw(reads))
     assert torch.equal(whole.links, again.links) and torch.equal(whole.observed, again.observed)    # bitwise: integer addition commutes
@@ -289,13 +214,6 @@ def test_no_site_at_all():
 
 
 # ---- phase_chain, on hand-given links ---------------------------------------------------------------------------------------------
-
-def _assert_chain(got, want):
-    assert got.flip.dtype == got.parity.dtype == torch.uint8
-    for name in ("parent", "flip", "margin", "root", "parity", "ps", "set_size"):
-        t = getattr(got, name)
-        assert (t.dtype == torch.uint8 if name in ("flip", "parity") else t.dtype == torch.int32) and t.cpu().tolist() == getattr(want, name), name
-
 
 def _chain_both(links, pos, **kw):
     want = H.chain_ref(links, pos, **kw)
@@ -346,27 +264,6 @@ def test_the_chain_at_every_tie_and_at_the_clamp():
 
 # ---- haplotag ---------------------------------------------------------------------------------------------------------------------
 
-def _chain_dev(chain):
-    dtypes = (torch.int32, torch.uint8, torch.int32, torch.int32, torch.uint8, torch.int32, torch.int32)
-    return W.Phasing(*[torch.tensor(v, dtype=d, device=DEV) for v, d in zip(chain, dtypes)])
-
-
-def _tags_both(sites, chain, host, qual=None, keep=None, cap=None, report=0, **kw):
-    """host: (ops rows, ops_len, lo, n_ref, strand, query rows, query_len) -> the reference Tags, equal to the kernel's exactly"""
-    want = H.haplotag_ref(sites, chain, *host, qual=qual, keep=keep, cap=cap, **kw)
-    got = W.haplotag(_alignment(host[0], host[1]), _i32(host[2]), _i32(host[3]), _i32(host[4]), _dev(np.asarray(host[5])), _i32(host[6]), _sites_dev(sites),
-                     _chain_dev(chain), qual=None if qual is None else _dev(qual), keep=None if keep is None else torch.tensor(keep, device=DEV),
-                     cap=None if cap is None else _u8(cap), **kw)
-    if report:
-        with pytest.raises(RuntimeError, match="wavenet_speech_amd.haplotag: %d pair\\(s\\) whose ops do not fit" % report):
-            W.check_device_flags()
-    W.check_device_flags()
-    assert got.hp.dtype == torch.uint8 and got.ps.dtype == got.weight.dtype == got.n_sites.dtype == torch.int32
-    assert got.hp.cpu().tolist() == want.hp and got.ps.cpu().tolist() == want.ps
-    assert got.weight.cpu().tolist() == want.weight and got.n_sites.cpu().tolist() == want.n_sites
-    return want
-
-
 def test_haplotags_by_hand():
     """the rows of tests/test_phase_ref.py::test_haplotags_by_hand, and a bad read beside them"""
     from tests.phase_cases import CHAIN_LINKS, SITES
@@ -397,9 +294,9 @@ def test_haplotags_of_random_reads_across_sets():
     S = len(sites.pos)
     chain = H.chain_ref(rng.integers(0, 3, size=(S, 2, 2)).tolist(), sites.pos)          # many small sets: every read spans several
     assert 10 < len(set(chain.root)) < S and 1 in chain.set_size
-    reads = [_read(_random_ops(rng, n), rng) for n in (T - 1, T, T + 1, 2 * T + 1, 60, 300, 17, 2 * T + 1)]
+    reads = [C.read(C.random_ops(rng, n), rng) for n in (T - 1, T, T + 1, 2 * T + 1, 60, 300, 17, 2 * T + 1)]
     reads = [r for r in reads if r[1] <= R]
-    ops, n_ref, query, qual = _cols(reads)
+    ops, n_ref, query, qual = C.cols(reads)
     n = len(reads)
     ops_rows, ops_len, q_rows, q_len, qual_rows = _rows(ops, query, qual, None, None)
     few = (rng.integers(0, 3, size=qual_rows.shape) * 10).astype(np.uint8)               # three weights only: the arg-max ties all the time
@@ -449,8 +346,7 @@ def test_closed_loop_on_the_planted_phased_runs(noisy):
     _assert_counts(links.observed.cpu().tolist(), want["sites"], pile)
     assert torch.equal(links.used, pile.used)
     _assert_chain(phasing, want["chain"])
-    for name in ("hp", "ps", "weight", "n_sites"):
-        assert getattr(tags, name).cpu().tolist() == getattr(want["tags"], name), name
+    _assert_tags(tags, want["tags"])
     assert [tuple(v) for v in records] == want["records"]
     # the five conditions, on the device's tables
     got = dict(sites=want["sites"]._replace(pos=sites.pos.cpu().tolist()), chain=H.Chain(*[t.cpu().tolist() for t in phasing]),

@@ -13,9 +13,10 @@ import wavenet_speech_amd as W
 from tests import call_limits_cases as K
 from tests import phase_ref as H
 from tests import pileup_limits_cases as L
-from tests.test_gpu_genotype_limits import _capture, _copy_reads, _pile_rules, _reads_dev, _rules_dev
-from tests.test_gpu_phase import DEV, _assert_chain, _assert_counts, _assert_links, _chain_dev, _dev, _i32, _sites_dev, _tags_both
-from tests.test_gpu_pileup import U
+from tests.gpu_calls import U, assert_chain as _assert_chain, assert_counts as _assert_counts, assert_links as _assert_links, assert_tags as _assert_tags
+from tests.gpu_calls import capture as _capture, chain_dev as _chain_dev, copy_reads as _copy_reads, pile_rules as _pile_rules
+from tests.gpu_calls import reads_dev as _reads_dev, rules_dev as _rules_dev, sites_dev as _sites_dev, tags_both as _tags_both
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
 
@@ -139,8 +140,7 @@ def test_strided_rows_and_int64_labels():
     assert torch.equal(links[0].links, links[1].links) and torch.equal(links[0].observed, links[1].observed) and torch.equal(links[0].used, links[1].used)
     tags = [W.haplotag(*a, sites_dev, chain_dev, **r) for a, r in ((plain, dev_rules), (strided, strided_rules))]
     for got in tags:
-        for name in ("hp", "ps", "weight", "n_sites"):
-            assert getattr(got, name).cpu().tolist() == getattr(want_tags, name), name
+        _assert_tags(got, want_tags)
     assert all(torch.equal(a, b) for a, b in zip(*tags))
     W.check_device_flags()
 
@@ -179,6 +179,5 @@ def test_links_chain_and_tags_captured_into_a_graph():
         torch.cuda.synchronize()
         _assert_links(links, want[seed][0])
         _assert_chain(phasing, want[seed][1])
-        for name in ("hp", "ps", "weight", "n_sites"):
-            assert getattr(tags, name).cpu().tolist() == getattr(want[seed][2], name), (seed, name)
+        _assert_tags(tags, want[seed][2], "seed %d " % seed)
     W.check_device_flags()

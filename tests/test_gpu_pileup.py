@@ -2,7 +2,7 @@
 of tests/pileup_ref.py.  Everything the kernels write is an integer, so every comparison is exact equality, ties included;
 tests/test_pileup_ref.py holds the reference itself on the CPU, and the planted runs are built once in tests/pileup_cases.py.
 Every shape is tiny: T = 256 op columns is the pileup kernel's tile, S = 256 positions the tile of the call and emit kernels."""
-import sys
+import functools
 
 import numpy as np
 import pytest
@@ -11,64 +11,19 @@ import torch
 import wavenet_speech_amd as W
 from tests import pileup_cases as C
 from tests import pileup_ref as P
+from tests.gpu_calls import U, alignment as _alignment, assert_consensus as _assert_calls, assert_pile as _assert_pile, pile_both as _both
+from tests.gpu_calls import pile_dev as _to_device
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-U = sys.modules["wavenet_speech_amd.pileup"]      # the module: the package exports the function under the same name
 T, S = U.TILE, U.SCAN_TILE
+_read = functools.partial(C.read, quals=False)      # pileup takes no qualities: none are drawn
 CALLED = P.SUBSTITUTION | P.DELETION | P.INSERTION
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _i32(v):
-    return _dev(np.asarray(v, dtype=np.int32))
-
-
-def _alignment(ops_rows, ops_len):
-    return W.PairwiseAlignment(None, None, None, None, None, _dev(ops_rows), _i32(ops_len))
-
-
-def _assert_pile(got, want):
-    assert got.counts.dtype == got.ins_lengths.dtype == got.ins_bases.dtype == torch.int32 and got.used.dtype == torch.int8
-    assert tuple(got.counts.shape) == want.counts.shape and tuple(got.ins_lengths.shape) == want.ins_lengths.shape
-    assert tuple(got.ins_bases.shape) == want.ins_bases.shape
-    assert got.used.cpu().tolist() == want.used.tolist()
-    for name in ("counts", "ins_lengths", "ins_bases"):
-        assert np.array_equal(getattr(got, name).cpu().numpy().astype(np.int64), getattr(want, name)), name
-
-
-def _both(ops, lo, n_ref, strand, query, R, qual=None, keep=None, ops_len=None, query_len=None, into=None, **kw):
-    """the same reads through the reference and the kernel; the tables and `used` must agree exactly -> (Pileup, Pile)"""
-    ops_rows, lens = C.rows(ops, dtype=np.uint8)
-    ops_len = lens if ops_len is None else np.asarray(ops_len, dtype=np.int32)
-    q_rows, q_len = C.rows(query)
-    q_len = q_len if query_len is None else np.asarray(query_len, dtype=np.int32)
-    qual_rows = None if qual is None else C.rows(qual, width=q_rows.shape[1], dtype=np.uint8)[0]
-    want = P.pileup_ref(ops_rows, ops_len, lo, n_ref, strand, q_rows, q_len, R, qual=qual_rows, keep=keep, into=None if into is None else into[1], **kw)
-    got = W.pileup(_alignment(ops_rows, ops_len), _i32(lo), _i32(n_ref), _i32(strand), _dev(q_rows), _i32(q_len), R,
-                   qual=None if qual is None else _dev(qual_rows), keep=None if keep is None else torch.tensor(keep, device=DEV),
-                   into=None if into is None else into[0], **kw)
-    _assert_pile(got, want)
-    return got, want
-
-
-def _read(ops, rng, odd=0.1):
-    """(ops, n_ref, query) with random labels, a share `odd` of them outside 1..4"""
-    n_query = sum(v != 3 for v in ops)
-    query = [int(v) if rng.random() >= odd else int(rng.choice([0, 5, 9])) for v in rng.integers(1, 5, size=n_query)]
-    return list(ops), sum(v != 4 for v in ops), query
-
-
-def _random_ops(rng, n):
-    return [int(v) for v in rng.choice([1, 2, 3, 4], size=n, p=[0.6, 0.2, 0.1, 0.1])]
 
 
 def test_tile_edges_on_both_strands():
     rng = np.random.default_rng(1)
-    strings = [_random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
+    strings = [C.random_ops(rng, n) for n in (T - 1, T, T + 1, 2 * T + 1)]
     strings += [[1] * (T - 6) + [4] * 12 + [1] * 9,                  # an insertion run and a deletion run across the first tile edge
                 [2] * (T - 6) + [3] * 12 + [2] * 9,
                 [1] * 5 + [4] * (T + 40) + [1] * 5,                  # an insertion longer than a tile
@@ -92,7 +47,7 @@ def test_tile_edges_on_both_strands():
 
 def test_windows_clamped_at_both_ends_and_a_reference_of_one():
     rng = np.random.default_rng(2)
-    reads = [_read(_random_ops(rng, 70), rng, odd=0.0) for _ in range(6)] + [_read([1] * 40, rng, odd=0.0)] * 2
+    reads = [_read(C.random_ops(rng, 70), rng, odd=0.0) for _ in range(6)] + [_read([1] * 40, rng, odd=0.0)] * 2
     R = max(r[1] for r in reads)
     lo = [0 if b & 1 else R - r[1] for b, r in enumerate(reads[:6])] + [0, R - 40]          # a window at 0, a window that ends at R
     for strands in ([0] * 8, [1] * 8, [0, 1, 1, 0, 0, 1, 1, 0]):
@@ -198,7 +153,7 @@ def test_contention_on_one_locus():
     assert n_ref == 40
     got, want = _both([ops] * 300, [0] * 300, [40] * 300, [0] * 300, [query] * 300, 40)
     assert want.counts.max() == 300 and want.ins_lengths[11, 1] == 300
-    reads = [_read(_random_ops(rng, 42), rng) for _ in range(300)]
+    reads = [_read(C.random_ops(rng, 42), rng) for _ in range(300)]
     reads = [r for r in reads if r[1] <= 40]
     n = len(reads)
     got, want = _both([r[0] for r in reads], [40 - r[1] if b % 3 else 0 for b, r in enumerate(reads)], [r[1] for r in reads],
@@ -209,7 +164,7 @@ def test_contention_on_one_locus():
 
 def test_accumulation_over_batches_and_reproducibility():
     rng = np.random.default_rng(9)
-    reads = [_read(_random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
+    reads = [_read(C.random_ops(rng, int(rng.integers(40, 300))), rng) for _ in range(24)]
     args = lambda part: ([r[0] for r in part], [2 * b for b in range(len(part))], [r[1] for r in part], [b & 1 for b in range(len(part))],      # noqa: E731
                          [r[2] for r in part], 400)
     whole, _ = _both(*args(reads))
@@ -230,7 +185,7 @@ def test_accumulation_over_batches_and_reproducibility():
 
 def test_strided_rows_and_int64_labels():
     rng = np.random.default_rng(10)
-    reads = [_read(_random_ops(rng, 90), rng) for _ in range(5)]
+    reads = [_read(C.random_ops(rng, 90), rng) for _ in range(5)]
     ops_rows, ops_len = C.rows([r[0] for r in reads], dtype=np.uint8)
     q_rows, q_len = C.rows([r[2] for r in reads])
     qual_rows = rng.integers(0, 40, size=q_rows.shape).astype(np.uint8)
@@ -248,31 +203,12 @@ def test_strided_rows_and_int64_labels():
 
 # ---- call_consensus -------------------------------------------------------------------------------------------------------------
 
-def _assert_calls(got, want):
-    assert got.call.dtype == got.ins_len.dtype == got.ins_bases.dtype == got.flags.dtype == torch.uint8
-    assert got.alt_count.dtype == got.offsets.dtype == got.consensus.dtype == torch.int32
-    for name in ("call", "ins_len", "ins_bases", "flags", "alt_count", "offsets", "consensus"):
-        g, w = getattr(got, name).cpu().numpy(), getattr(want, name)
-        assert g.shape == w.shape and np.array_equal(g.astype(np.int64), w.astype(np.int64)), name
-
-
-def _random_pile(rng, R, max_ins, top=4):
-    counts = rng.integers(0, top, size=(R, 2, 6))
-    ins_lengths = rng.integers(0, top, size=(R, max_ins + 1)) * (rng.random((R, 1)) < 0.5)
-    ins_bases = rng.integers(0, 3, size=(R, max_ins, 4)) * (rng.random((R, max_ins, 1)) < 0.7)
-    return P.Pile(counts.astype(np.int64), ins_lengths.astype(np.int64), ins_bases.astype(np.int64), None, 0)
-
-
-def _to_device(pile):
-    return W.Pileup(_dev(pile.counts.astype(np.int32)), _dev(pile.ins_lengths.astype(np.int32)), _dev(pile.ins_bases.astype(np.int32)), None)
-
-
 @pytest.mark.parametrize("R", [1, S - 1, S, S + 1, 3 * S + 2])
 def test_call_consensus_at_the_scan_tile_edges(R):
     rng = np.random.default_rng(R)
     ref = rng.integers(0, 6, size=R)
     for max_ins, min_depth, frac in ((2, 3, (1, 2)), (0, 1, (0, 1)), (8, 6, (2, 3)), (3, 4, (1, 1)), (1, 2, (1, 3))):
-        pile = _random_pile(rng, R, max_ins)
+        pile = C.random_pile(rng, R, max_ins)
         want = P.call_consensus_ref(pile, ref, min_depth, *frac)
         got = W.call_consensus(_to_device(pile), _dev(ref), min_depth=min_depth, min_fraction=frac)
         _assert_calls(got, want)

@@ -10,7 +10,8 @@ import torch
 import wavenet_speech_amd as W
 from tests import pileup_limits_cases as L
 from tests import pileup_ref as P
-from tests.test_gpu_pileup import DEV, U, _alignment, _assert_calls, _assert_pile, _dev, _i32, _to_device
+from tests.gpu_calls import U, alignment as _alignment, assert_consensus as _assert_calls, assert_pile as _assert_pile, pile_dev as _to_device
+from tests.gpu_util import DEV, dev as _dev, i32 as _i32
 
 pytestmark = pytest.mark.gpu
 TOP = 2 ** 31 - 1

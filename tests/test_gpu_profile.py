@@ -10,15 +10,10 @@ import torch
 import wavenet_speech_amd as W
 from tests import quality_profile_cases as PC
 from tests import quality_profile_ref as PR
+from tests.gpu_labels import PROFILE_TABLES as TABLES, assert_profile as _equal
+from tests.gpu_util import DEV, basecall_model as _model, dev as _dev, same as _same
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-TABLES = ("q_counts", "dwell_counts", "confusion")
-FIELDS = TABLES + ("read_counts", "outcome", "ref_index")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _alignment(batch):
@@ -34,21 +29,6 @@ def _run(batch, count_ends, qual=True, dwell=True, into=None, views=None):
     args.update(views or {})
     return W.quality_profile(_alignment(batch), args["ref"], _dev(batch.ref_len), args["query"], _dev(batch.query_len),
                              qual=args["qual"], dwell=args["dwell"], classes=batch.classes, count_ends=count_ends, into=into)
-
-
-def _equal(got, want, what):
-    assert isinstance(got, W.QualityProfile)
-    for name, dtype in zip(FIELDS, (torch.int64,) * 3 + (torch.int32, torch.uint8, torch.int32)):
-        t = getattr(got, name)
-        if want[name] is None:
-            assert t is None, (what, name)
-            continue
-        assert t.is_cuda and t.dtype == dtype, (what, name)
-        assert np.array_equal(t.cpu().numpy(), want[name]), (what, name)
-
-
-def _same(a, b):
-    return all((u is None and v is None) or torch.equal(u, v) for u, v in zip(a, b))
 
 
 @pytest.mark.parametrize("count_ends", [False, True])
@@ -183,12 +163,6 @@ def test_a_poisoned_pair_of_the_aligner_is_a_bad_read():
                            calls[keep], calls_len[keep])
     assert torch.equal(p.confusion, ok.confusion) and torch.equal(p.read_counts[keep], ok.read_counts)
     W.check_device_flags()
-
-
-def _model():
-    from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
-    torch.manual_seed(21)                                            # the 16-channel model of tests/test_gpu_basecall.py
-    return RawCTCNet(16, 3, 5, [(16, 16, 2, d) for d in (1, 2, 4, 3)], 16, softmax=False, causal=False).to(DEV)
 
 
 @pytest.mark.parametrize("decode", ["greedy", "beam"])

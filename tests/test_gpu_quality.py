@@ -14,18 +14,9 @@ import wavenet_speech_amd as W
 from tests import ctc_decode_ref as DR
 from tests import ctc_quality_cases as QC
 from tests import ctc_quality_ref as QR
+from tests.gpu_util import DEV, basecall_model as _model, bits as _bits, same_bits as _same
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same(a, b):
-    """bitwise equality of two BaseQualities (NaN payloads included)"""
-    return all(torch.equal(_bits(u), _bits(v)) for u, v in zip(a, b))
 
 
 def _check(got, ref, valid, near, bound, what):
@@ -142,12 +133,6 @@ def test_bad_rows_are_poisoned_and_counted_and_their_neighbours_are_right():
         assert bool((got.dwell[b, :int(lengths[b])] > 0).sum() == int(lengths[b]) - 1)       # every other base of the row is served
     assert bool(torch.isnan(got.error[5]).all()) and not bool(got.qual[5].any()) and not bool(got.dwell[5].any())
     W.check_device_flags()                                           # the flag was consumed: nothing is left over
-
-
-def _model(softmax=False):
-    from wavenet_speech_amd.modules.raw_ctcnet import RawCTCNet
-    torch.manual_seed(21)                                            # the 16-channel model of tests/test_gpu_basecall.py
-    return RawCTCNet(16, 3, 5, [(16, 16, 2, d) for d in (1, 2, 4, 3)], 16, softmax=softmax, causal=False).to(DEV)
 
 
 @pytest.mark.parametrize("softmax", [False, True])

@@ -9,15 +9,10 @@ import torch
 import wavenet_speech_amd as W
 from tests import readmap_cases as C
 from tests import readmap_ref as R
+from tests.gpu_labels import INT_MIN, PAD, assert_index as _assert_index, assert_seeds as _assert_seeds
+from tests.gpu_util import DEV, dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-INT_MIN = -2 ** 31
-PAD = 2 ** 63 - 1
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ---- sketch -------------------------------------------------------------------------------------------------------------------
@@ -117,30 +112,6 @@ def test_sketch_seams():
 
 
 # ---- seeds --------------------------------------------------------------------------------------------------------------------
-
-def _assert_index(index, ref, k, w):
-    want = [(c << 28) | (p << 1) | s for c, p, s in R.index_ref(ref, k, w)]
-    assert index.n_entries == len(want) and index.entries[:index.n_entries].tolist() == want
-    assert (index.R, index.k, index.w) == (len(ref), k, w) and index.bases.tolist() == list(ref)
-
-
-def _assert_seeds(ref, reads, k, w, max_occ, cap, width=None):
-    index = W.read_index(ref, k=k, w=w, device=DEV)
-    _assert_index(index, ref, k, w)
-    labels, lengths = C.rows(reads, width)
-    got = W.seed_anchors(_dev(labels), _dev(lengths), index, max_occ=max_occ, anchors_per_read=cap)
-    host = R.index_ref(ref, k, w)
-    keys = np.full((len(reads), cap), PAD, dtype=np.int64)
-    want = []
-    for b, read in enumerate(reads):
-        anchors, n_min, trunc = R.anchors_ref(read, host, k, w, max_occ, cap)
-        keys[b, :len(anchors)] = sorted(R.pack(a) for a in anchors)
-        want.append((len(anchors), n_min, trunc))
-    assert got.keys.dtype == torch.int64 and np.array_equal(got.keys.cpu().numpy(), keys)
-    assert [got.n_anchors.tolist(), got.n_minimizers.tolist(), got.truncated.tolist()] == [list(c) for c in zip(*want)]
-    assert all(t.dtype == torch.int32 for t in (got.n_anchors, got.n_minimizers, got.truncated))
-    return got, want
-
 
 def test_seeds_max_occ_on_both_sides():
     """a k-mer with exactly max_occ entries in the index is kept, one with max_occ + 1 is dropped whole (w = 1: every valid k-mer is a

@@ -6,51 +6,22 @@ tests/test_ragged_reads.py).  All shapes are tiny.
 Tolerances: integers (lengths, starts, the k-mer of every sample) are exact.  The signal is (float)(mean + stdv * z) with the sum
 in float64: a fused multiply-add may move the float64 sum by one of ITS ulps before the single rounding to float32, so the
 float32 result may differ from the two-rounding form by at most one float32 ulp (and almost never does)."""
-import os
-
-import numpy as np
 import pytest
 import torch
 
 import wavenet_speech_amd as W
 from wavenet_speech_amd import synthetic as S
 from tests import dwell_stats as D
+from tests.cpu_util import gold, ragged_table as _table  # noqa: F401
+from tests.gpu_labels import plan_given as _plan_given
+from tests.gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ragged_00.npz")
-
-
-@pytest.fixture(scope="module")
-def gold():
-    z = np.load(FIXTURE, allow_pickle=False)
-    return {k: z[k] for k in z.files}
-
-
-def _table(gold):
-    return torch.from_numpy(gold["table.means"]), torch.from_numpy(gold["table.stdvs"])
 
 
 def _ulps(a, b):
     """largest distance in float32 ulps between two float32 tensors of one sign"""
     return int((a.cpu().contiguous().view(torch.int32).long() - b.cpu().contiguous().view(torch.int32).long()).abs().max())
-
-
-def _rows(x, width):
-    out = torch.zeros(x.shape[0], width, dtype=torch.int32, device=DEV)
-    out[:, :x.shape[1]] = x.to(DEV)
-    return out
-
-
-def _plan_given(bases, base_lengths, dwell, window, max_dwell=1 << 14, dwell_model=("fixed", 1)):
-    """wn_reads_plan on given bases / lengths / dwell (CPU tensors, [B, n] / [B] / [B, K]); any of them may be None"""
-    B = (bases if bases is not None else dwell if dwell is not None else base_lengths).shape[0]
-    nmax = bases.shape[1] if bases is not None else int(base_lengths.max())
-    mb = nmax + 1
-    return S.hip_reads_plan(B, 5 + 2 * window, mb, window, dwell_model, max_dwell, 17, DEV,
-                            None if bases is None else _rows(bases, mb),
-                            None if base_lengths is None else base_lengths.to(device=DEV, dtype=torch.int32),
-                            None if dwell is None else _rows(dwell, mb))
 
 
 @pytest.mark.parametrize("case", ["case0", "case1", "case2"])

@@ -9,31 +9,11 @@ import torch
 import wavenet_speech_amd as W
 from tests import signal_align_cases as C
 from tests import signal_align_ref as R
+from tests.gpu_signal import assert_signal_alignment as _assert_equal, model_of as _model
+from tests.gpu_util import dev as _dev, strided as _strided
 from wavenet_speech_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _strided(a, channel):
-    """the rows of `a` as a view into a wider device buffer (row stride L + 5, one element in); [B, 1, L] with channel"""
-    B, L = a.shape
-    wide = torch.zeros(B, L + 5, dtype=torch.from_numpy(a[:1, :1]).dtype, device=DEV)
-    wide[:, 1:1 + L] = _dev(a)
-    view = wide[:, 1:1 + L]
-    return view.unsqueeze(1) if channel else view
-
-
-def _model(case):
-    table = torch.from_numpy(case.model)
-    model = W.SignalModel(table.clamp(min=1) if bool((table[:, 1] < 1).any()) else table, case.kw["weight_shift"], case.kw["frac_bits"],
-                          C.COST_BITS)
-    model.table.copy_(table)                                         # the constructor refuses a weight of 0: the device must too
-    return model
 
 
 def _call(case, signal=None, scale_shift=None, want_states=True, band=None, labels=None):
@@ -42,16 +22,6 @@ def _call(case, signal=None, scale_shift=None, want_states=True, band=None, labe
     return W.signal_align(signal, _dev(case.signal_lengths), _dev(case.labels) if labels is None else labels, _dev(case.label_lengths),
                           _model(case), first=kw["first"], band=band or kw["band"], max_cost=kw["max_cost"],
                           scale_shift=None if scale_shift is None else _dev(scale_shift), want_states=want_states)
-
-
-def _assert_equal(got, ref, states=True):
-    assert got.starts.dtype == torch.int32 and np.array_equal(got.starts.cpu().numpy(), ref["starts"])
-    assert got.score.dtype == torch.int64 and got.score.cpu().tolist() == ref["score"].tolist()
-    assert got.band_hits.dtype == torch.int32 and np.array_equal(got.band_hits.cpu().numpy(), ref["band_hits"])
-    if states:
-        assert got.states.dtype == torch.int32 and np.array_equal(got.states.cpu().numpy(), ref["states"])
-    else:
-        assert got.states is None
 
 
 SMALL = ["hand", "small", "band_never_moves", "moving_band", "sample_chunk_edges", "homopolymer", "dyadic", "cost_clamp",

@@ -11,60 +11,18 @@ import wavenet_speech_amd as W
 from tests import signal_align_ref as AR
 from tests import signal_limits_cases as C
 from tests import signal_map_ref as MR
+from tests.gpu_signal import assert_kmer_events as _assert_events_equal, assert_signal_alignment as _assert_align_equal
+from tests.gpu_signal import assert_signal_mapping as _assert_map_equal
+from tests.gpu_util import DEV, dev as _dev, no_stale_flags  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
+
+
 I64_MIN = np.iinfo(np.int64).min
-EVENT_FIELDS = ("kmer", "start", "length", "sum", "sumsq")
-
-
-@pytest.fixture(autouse=True)
-def _no_flags_left_by_another_test():
-    """a test that failed between a call with bad reads and its check leaves their flag behind: it is not this test's"""
-    try:
-        W.check_device_flags()
-    except RuntimeError:
-        pass
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _model(table, weight_shift, frac_bits):
     return W.SignalModel(torch.from_numpy(np.asarray(table, dtype=np.int64)), weight_shift, frac_bits, C.COST_BITS)
-
-
-def _i64(a):
-    return np.array(a.tolist(), dtype=np.int64).reshape(a.shape)
-
-
-def _assert_map_equal(got, ref):
-    for name in ("score", "runner_up", "block_cost", "end_cost"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int64 and np.array_equal(t.cpu().numpy(), _i64(ref[name])), name
-    for name in ("end", "start", "block_end"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int32 and np.array_equal(t.cpu().numpy(), ref[name]), name
-
-
-def _assert_align_equal(got, ref):
-    assert got.starts.dtype == torch.int32 and np.array_equal(got.starts.cpu().numpy(), ref["starts"])
-    assert got.score.dtype == torch.int64 and got.score.cpu().tolist() == ref["score"].tolist()
-    assert got.band_hits.dtype == torch.int32 and np.array_equal(got.band_hits.cpu().numpy(), ref["band_hits"])
-    assert got.states.dtype == torch.int32 and np.array_equal(got.states.cpu().numpy(), ref["states"])
-
-
-def _assert_events_equal(got, ref, events=True):
-    if events:
-        for name, field in zip(EVENT_FIELDS, got[:5]):
-            assert field.dtype == (torch.int64 if name in ("sum", "sumsq") else torch.int32), name
-            assert np.array_equal(field.cpu().numpy(), ref[name]), name
-    else:
-        assert all(f is None for f in got[:5])
-    assert got.read_counts.dtype == torch.int32 and np.array_equal(got.read_counts.cpu().numpy(), ref["read_counts"])
-    assert got.kmer_stats.dtype == torch.int64 and np.array_equal(got.kmer_stats.cpu().numpy(), ref["kmer_stats"])
-    assert got.dwell_hist.dtype == torch.int64 and np.array_equal(got.dwell_hist.cpu().numpy(), ref["dwell_hist"])
 
 
 def _events(case, k=1, first=0, **more):

@@ -10,31 +10,13 @@ import wavenet_speech_amd as W
 from tests import signal_align_ref as AR
 from tests import signal_map_cases as C
 from tests import signal_map_ref as R
+from tests.gpu_signal import assert_signal_mapping as _assert_equal, model_of as _model
+from tests.gpu_util import DEV, dev as _dev, strided as _strided
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
+
+
 I64_MIN = np.iinfo(np.int64).min
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _strided(a, channel):
-    """the rows of `a` as a view into a wider device buffer (row stride L + 5, one element in); [B, 1, L] with channel"""
-    B, L = a.shape
-    wide = torch.zeros(B, L + 5, dtype=torch.from_numpy(a[:1, :1]).dtype, device=DEV)
-    wide[:, 1:1 + L] = _dev(a)
-    view = wide[:, 1:1 + L]
-    return view.unsqueeze(1) if channel else view
-
-
-def _model(case):
-    table = torch.from_numpy(case.model)
-    model = W.SignalModel(table.clamp(min=1) if bool((table[:, 1] < 1).any()) else table, case.kw["weight_shift"], case.kw["frac_bits"],
-                          C.COST_BITS)
-    model.table.copy_(table)                                         # the constructor refuses a weight of 0: the device must too
-    return model
 
 
 _REFERENCES = {}
@@ -51,23 +33,6 @@ def _call(name, case, signal=None, scale_shift=None, strip=None, want_end_cost=T
     signal = _dev(case.signal) if signal is None else signal
     return W.signal_map(signal, _dev(case.signal_lengths), _reference(name, case), max_cost=case.kw["max_cost"], strip=strip,
                         scale_shift=None if scale_shift is None else _dev(scale_shift), want_end_cost=want_end_cost)
-
-
-def _i64(a):
-    return np.array(a.tolist(), dtype=np.int64).reshape(a.shape)
-
-
-def _assert_equal(got, ref, end_cost=True):
-    for name, dtype in (("score", torch.int64), ("runner_up", torch.int64), ("block_cost", torch.int64)):
-        t = getattr(got, name)
-        assert t.dtype == dtype and np.array_equal(t.cpu().numpy(), _i64(ref[name])), name
-    for name in ("end", "start", "block_end"):
-        t = getattr(got, name)
-        assert t.dtype == torch.int32 and np.array_equal(t.cpu().numpy(), ref[name]), name
-    if end_cost:
-        assert got.end_cost.dtype == torch.int64 and np.array_equal(got.end_cost.cpu().numpy(), _i64(ref["end_cost"]))
-    else:
-        assert got.end_cost is None
 
 
 @pytest.mark.parametrize("M", C.SWEEP_M)

@@ -15,27 +15,12 @@ from tests import event_detect_cases as ED
 from tests import readmap_cases as RC
 from tests import readmap_ref as RR
 from tests import tool_limits_cases as C
-from tests.test_gpu_demux import _assert_pick, _assert_scores, _kit, _kw
-from tests.test_gpu_event_align import _assert_counts, _assert_equal as _assert_alignment, _call as _align
-from tests.test_gpu_event_detect import _assert_equal as _assert_events, _call as _detect
+from tests.gpu_labels import INT_MIN, PAD, assert_pick as _assert_pick, assert_scores as _assert_scores, kit as _kit, kw as _kw
+from tests.gpu_signal import assert_detected as _assert_events, assert_event_alignment as _assert_alignment, assert_move_counts as _assert_counts
+from tests.gpu_signal import detect_events as _detect, event_align as _align
+from tests.gpu_util import DEV, dev as _dev, no_stale_flags  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-INT_MIN = -2 ** 31
-PAD = 2 ** 63 - 1
-
-
-@pytest.fixture(autouse=True)
-def _no_flags_left_by_another_test():
-    """a test that failed between a call with bad rows and its check leaves their flag behind: it is not this test's"""
-    try:
-        W.check_device_flags()
-    except RuntimeError:
-        pass
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ================================================================================================================ event alignment

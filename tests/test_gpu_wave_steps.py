@@ -13,22 +13,18 @@ from tests import event_detect_cases as EC
 from tests import kmer_events_cases as KC
 from tests import kmer_events_ref as KR
 from tests import pairwise_align_ref as PR
+from tests import pileup_cases as PC
 from tests import pileup_ref as P
 from tests import read_stats_ref as SR
 from tests import readmap_cases as RC
 from tests import readmap_ref as RR
-from tests import test_gpu_align as TA
-from tests import test_gpu_demux as TD
-from tests import test_gpu_event_detect as TE
-from tests import test_gpu_events as TK
-from tests import test_gpu_pairalign as TP
-from tests import test_gpu_pileup as TU
-from tests import test_gpu_reads as TR
-from tests import test_gpu_readmap as TM
+from tests.gpu_calls import assert_consensus, pile_both
+from tests.gpu_labels import assert_pick, assert_scores, assert_seeds, check_forced_batch, check_pair_batch, forced_align, kit, kw, pair_align, plan_given
+from tests.gpu_signal import assert_detected, assert_kmer_events, detect_events, kmer_events
+from tests.gpu_util import DEV, dev
 from wavenet_speech_amd import normalise as N
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 # ---- scans ----------------------------------------------------------------------------------------------------------------------
@@ -36,14 +32,14 @@ DEV = torch.device("cuda:0")
 def test_pileup_op_strings_at_the_wave_and_tile_seams():
     """tile_scan (two ballots, wave_offsets) in the walk; block_scan in the call, the scan of the tile totals and the emit"""
     rng = np.random.default_rng(11)
-    reads = [TU._read(TU._random_ops(rng, n), rng) for n in (63, 64, 65, 255, 256, 257)]
+    reads = [PC.read(PC.random_ops(rng, n), rng, quals=False) for n in (63, 64, 65, 255, 256, 257)]
     n, R = len(reads), 300
     for strand in (0, 1):
-        got, want = TU._both([r[0] for r in reads], [7 * b for b in range(n)], [r[1] for r in reads], [strand] * n, [r[2] for r in reads], R,
-                             max_ins=2)
+        got, want = pile_both([r[0] for r in reads], [7 * b for b in range(n)], [r[1] for r in reads], [strand] * n, [r[2] for r in reads], R,
+                              max_ins=2)
         assert want.used.tolist() == [1] * n
     ref = rng.integers(1, 5, size=R).astype(np.int32)
-    TU._assert_calls(W.call_consensus(got, TU._dev(ref), min_depth=1, min_fraction=(1, 2)), P.call_consensus_ref(want, ref, 1, 1, 2))
+    assert_consensus(W.call_consensus(got, dev(ref), min_depth=1, min_fraction=(1, 2)), P.call_consensus_ref(want, ref, 1, 1, 2))
     W.check_device_flags()
 
 
@@ -55,7 +51,7 @@ def test_event_ranks_with_boundaries_in_the_first_and_the_last_word(words):
     case = EC.batch_of([x], EC.kw_of(windows=(3, 0)))
     ref = EC.call_ref(case)
     assert {p >> 6 for p, _ in EC.boundaries(ref, 0) if _ != 3} == {0, words - 1}
-    TE._assert_equal(TE._call(case, chunk=None), ref)
+    assert_detected(detect_events(case, chunk=None), ref)
     W.check_device_flags()
 
 
@@ -64,7 +60,7 @@ def test_seed_anchors_with_hits_at_both_ends_of_reads_around_a_tile():
     k = 6
     ref = RC.random_bases(np.random.default_rng(12), 700)
     reads = [ref[100:100 + n] for n in (255, 256, 257, 255 + k - 1, 256 + k - 1, 257 + k - 1)]
-    got, want = TM._assert_seeds(ref, reads, k, 1, 8, 2048)
+    got, want = assert_seeds(ref, reads, k, 1, 8, 2048)
     host = RR.index_ref(ref, k, 1)
     for read in reads:
         q = {a[2] for a in RR.anchors_ref(read, host, k, 1, 8, 2048)[0] if a[0] == 0}
@@ -74,7 +70,7 @@ def test_seed_anchors_with_hits_at_both_ends_of_reads_around_a_tile():
 
 def test_reads_plan_with_fixed_dwell_1_gives_arange():
     sizes = (255, 256, 257)
-    plan = TR._plan_given(None, torch.tensor(sizes) + 4, None, 0)                    # window 0: K = n - 4
+    plan = plan_given(None, torch.tensor(sizes) + 4, None, 0)                    # window 0: K = n - 4
     assert int(plan["bad"]) == 0
     for b, K in enumerate(sizes):
         assert torch.equal(plan["starts"][b, :K + 1].cpu().long(), torch.arange(K + 1)) and int(plan["signal_lengths"][b]) == K
@@ -106,9 +102,9 @@ def test_demux_with_the_best_and_longest_pattern_at_either_end_of_the_waves(K, a
     ref = DR.demux_scores_ref(case.labels, case.lengths, case.patterns, case.pattern_lengths, case.n_front, case.window, *case.costs)
     want = DR.demux_pick_ref(ref["score"], ref["start"], ref["end"], case.lengths, case.group, DC.min_scores(case, 0, 1), case.n_front, 0, False)
     assert want["hits"][0, 0, 0] == (0 if at == "first" else K - 1) and want["hits"][0, 0, 1] == 24 * case.costs[0]
-    got = W.demultiplex(TD._dev(case.labels), TD._dev(case.lengths), TD._kit(case), min_fraction=0.0, min_margin=0.0, **TD._kw(case))
-    TD._assert_scores(got.scores, ref)
-    TD._assert_pick(got, want)
+    got = W.demultiplex(dev(case.labels), dev(case.lengths), kit(case), min_fraction=0.0, min_margin=0.0, **kw(case))
+    assert_scores(got.scores, ref)
+    assert_pick(got, want)
     W.check_device_flags()
 
 
@@ -119,7 +115,7 @@ def test_kmer_events_of_64_and_65_samples():
     ref = KR.kmer_events_ref(case.signal, case.signal_lengths, case.labels, case.label_lengths, begin, end, events, scale_shift=None,
                              frac_bits=12, max_dwell=255, **case.kw)
     assert ref["length"][0, 2:7].tolist() == [64, 2, 65, 4, 33] and (ref["kmer"][0, 2:7] >= 0).all()
-    TK._assert_equal(TK._call(case, "starts", "f32", 12), ref)
+    assert_kmer_events(kmer_events(case, "starts", "f32", 12), ref)
     W.check_device_flags()
 
 
@@ -133,8 +129,8 @@ def test_pairwise_align_across_the_first_wave_seam(M, free):
     refs = [rng.integers(1, 5, size=3).tolist(), rng.integers(1, 5, size=3).tolist()]
     queries = [rng.integers(1, 5, size=M).tolist(), rng.integers(1, 5, size=M - 1).tolist()[:505] + refs[1] + [1] * (M - 508)]
     assert len(queries[1]) == M
-    got = TP._align(refs, queries, PR.EMBOSS, free)
-    TP._check_batch(refs, queries, PR.EMBOSS, free, got, "M%d" % M)
+    got = pair_align(refs, queries, PR.EMBOSS, free)
+    check_pair_batch(refs, queries, PR.EMBOSS, free, got, "M%d" % M)
 
 
 @pytest.mark.parametrize("frames", [1, -1])
@@ -148,7 +144,7 @@ def test_forced_align_where_every_frame_advances_one_state(L, frames):
     T = 2 * L + frames
     x = torch.tensor(rng.integers(-24, 1, size=(1, 5, T)) / 4.0, dtype=torch.float32)
     labels = [[2] * L]
-    got = TA._run(x, labels, None, input="log_probs")
-    TA._check_batch(x, labels, None, got, kind="log_probs", exact=True, tag="L%d" % L)
+    got = forced_align(x, labels, None, input="log_probs")
+    check_forced_batch(x, labels, None, got, kind="log_probs", exact=True, tag="L%d" % L)
     states, _, _ = A.viterbi_align(x[0].double().numpy(), labels[0])
     assert frames == 1 or list(states) == list(range(1, T + 1))

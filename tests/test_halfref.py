@@ -98,7 +98,7 @@ def test_exact_classifier_is_the_oracle(pool, L, kw, dil):
 def test_exact_classifier_reproduces_the_golden(name):
     """forward and every gradient, x included, of the reference's own classifier run, at test_oracle_golden.py's tolerances"""
     from tests import goldenio
-    from tests.test_oracle_golden import TOL
+    from tests.goldenio import ORACLE_TOL as TOL
     g = goldenio.load(name)
     m = g.meta
     assert not m["softmax"]

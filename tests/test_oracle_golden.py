@@ -10,7 +10,7 @@ import torch
 from oracle import wavenet_oracle as O
 from tests import goldenio
 
-TOL = 2e-5
+TOL = goldenio.ORACLE_TOL
 
 
 def _leafify(sd):

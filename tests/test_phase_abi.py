@@ -8,7 +8,7 @@ import torch
 
 from tests.abi_util import FAKE, READ_ACCEPTED, READ_BATCH, READ_REQUIRED, READ_SHAPE, READ_UNSUPPORTED, WN_ERR_BAD_SHAPE, WN_ERR_UNSUPPORTED, \
     Entry, header_names, host_alignment
-from tests.abi_util import lib  # noqa: F401
+from tests.abi_util import hand_made_genotypes, lib  # noqa: F401
 
 READS = dict(READ_BATCH, cap=None, flat_qual=20, gap_qual=20, min_qual=0, site_of=FAKE, alleles=FAKE, n_sites=40)
 LINKS = Entry("wn_phase_links", dict(READS, reach=4, links=FAKE, observed=FAKE, used=FAKE, bad=None, stream=None))
@@ -108,9 +108,8 @@ def test_python_surface_refusals():
 def _hand_made():
     """the case of tests/test_phase_ref.py::test_phased_records_by_hand as tensors"""
     import wavenet_speech_amd as W
-    from tests.test_genotype_abi import _hand_made as genotypes
     from tests.phase_cases import HAND_CHAIN
-    ref, g, pile = genotypes()
+    ref, g, pile = hand_made_genotypes()
     site_of = torch.tensor([-1, 0, 1, 2, -1, 3, -1, 4], dtype=torch.int32)
     sites = W.PhaseSites(torch.tensor([1, 2, 3, 5, 7], dtype=torch.int32), g.alleles[[1, 2, 3, 5, 7]], site_of)
     dtypes = (torch.int32, torch.uint8, torch.int32, torch.int32, torch.uint8, torch.int32, torch.int32)

@@ -11,18 +11,7 @@ import torch
 import wavenet_speech_amd as W
 from wavenet_speech_amd import synthetic as S
 from tests import dwell_stats as D
-
-FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ragged_00.npz")
-
-
-@pytest.fixture(scope="module")
-def gold():
-    z = np.load(FIXTURE, allow_pickle=False)
-    return {k: z[k] for k in z.files}
-
-
-def _table(gold):
-    return torch.from_numpy(gold["table.means"]), torch.from_numpy(gold["table.stdvs"])
+from tests.cpu_util import gold, ragged_table as _table  # noqa: F401
 
 
 @pytest.mark.parametrize("case", ["case0", "case1", "case2"])
