@@ -1,6 +1,9 @@
 """CPU: libwavenet_amd.so loads without a GPU and exports every symbol include/wavenet_amd.h declares
 (no compute calls here -- those need a GPU)."""
 import ctypes
+import os
+import shutil
+import subprocess
 
 import pytest
 
@@ -21,6 +24,25 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "libwavenet_amd.so does not export %s" % name
     # and the ctypes table covers the header one-to-one
     assert sorted(_lib.SIGNATURES) == declared_functions()
+
+
+def _exported_wn_symbols(path):
+    """the defined dynamic symbols of a shared library that begin with wn_, or None where no tool that lists them is installed"""
+    for tool in (shutil.which("nm"), shutil.which("llvm-nm"), "/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/bin/llvm-nm"):
+        if tool and os.path.exists(tool):
+            out = subprocess.run([tool, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+            return sorted({line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("wn_")})
+    return None
+
+
+def test_library_exports_nothing_the_header_does_not_declare():
+    """the other side: a wn_* symbol of the product library that the header does not declare is a hook nobody documented (the
+    measurement hooks live in the builds of `make measure`, `make stamps` and `make l2operands`)"""
+    from wavenet_speech_amd import _lib
+    exported = _exported_wn_symbols(_lib.LIB_PATH)
+    if exported is None:
+        pytest.skip("neither nm nor llvm-nm is installed")
+    assert exported == declared_functions(), sorted(set(exported) ^ set(declared_functions()))
 
 
 def test_every_signature_row_matches_the_header():

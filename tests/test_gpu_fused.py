@@ -6,12 +6,18 @@ The stack is evaluated WITHOUT an output block (run_stack returns skips_sum), so
 decision can flip between two evaluations and the comparison measures rounding only."""
 import copy
 import ctypes
+import hashlib
+import json
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
 import torch.nn as nn
 
 from oracle import wavenet_oracle as O
+from tests import gpu_stack as S
 from tests import halfref as R
 from wavenet_speech_amd import _lib
 from wavenet_speech_amd import functional as HF
@@ -320,3 +326,42 @@ def test_run_stack_on_data_without_gradient(precision, pair, monkeypatch):
     hip.update({k: p.grad.cpu() for k, p in net.named_parameters() if p.grad is not None})
     _check_vs_rounding_reference("%s no input gradient pair=%s" % (precision, pair), hip, x, cot, sd, net.layers, causal, precision,
                                  input_grad=False)
+
+
+MEASUREMENT_KNOBS = {"WN_FUSED_DBG": "1", "WN_COL_DBG": "1", "WN_HGEMM_DBG": "1", "WN_HWGRAD_DBG": "1", "WN_FUSED_STAMPS": "1"}
+
+
+def _small_step_digests():
+    """SHA-1 of the output, dx and every gradient of one bf16 step of a two-block stack (32 channels, dilations 1 and 2, B = 1,
+    L = 128: the smallest that takes hfused_fwd_kernel, hcol_kernel / hcol2_kernel, hwgrad_kernel and hgemm_kernel for skips_sum),
+    and what it launched.  Run here and, by name, in the child process of the test below"""
+    net = _Stack(32, (1, 2), 32, True, seed=5).to(DEV)
+    net.stack_state.precision = "bf16"
+    torch.manual_seed(6)
+    x = torch.randn(1, 32, 128, device=DEV)
+    cot = torch.randn(1, 32, 128, device=DEV)
+    (s, dx, grads), launched = S.launches(lambda: _eval(net, x, cot))
+    out = {"forward": s, "dx": dx}
+    out.update({k: g for k, g in grads.items() if g is not None})
+    return {k: hashlib.sha1(v.detach().cpu().contiguous().numpy().tobytes()).hexdigest() for k, v in out.items()}, launched
+
+
+def test_measurement_knobs_do_nothing_to_the_product_library(monkeypatch):
+    """the variables that switch stores, K loops and split ranges off for A/B timing (csrc/wn_knobs.h: read by the measurement
+    build only) set in a child process that runs the same step from the same seed on the product library: the output and every
+    gradient have the bits of this process, which has none of them set"""
+    for name in MEASUREMENT_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    for name in ("WN_FUSED_FWD", "WN_COL_BWD", "WN_COL_PAIR"):
+        monkeypatch.setenv(name, "1")
+    here, launched = _small_step_digests()
+    assert {"hfused_fwd_kernel", "hcol_kernel<dz,dgate>", "hcol2_kernel<dx+dz>", "hwgrad_kernel", "hgemm_kernel<skips_sum>"} <= set(launched), launched
+    assert {"forward", "dx"} < set(here), sorted(here)     # and the parameters' gradients
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", "import json; from tests.test_gpu_fused import _small_step_digests as f; print(json.dumps(f()))"],
+                       env=dict(os.environ, **MEASUREMENT_KNOBS), cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
+    there, launched_there = json.loads(r.stdout.strip().splitlines()[-1])
+    assert launched_there == launched, (launched_there, launched)
+    differ = sorted(k for k in here if there.get(k) != here[k])
+    assert set(there) == set(here) and not differ, differ

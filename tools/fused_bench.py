@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Time wn_hblock_forward (training form: z, sg, r stored) at BASELINE configs[1]'s block shape, fused vs two launches.
-usage: fused_bench.py [C] [L] [B] [d]   (env WN_FUSED_FWD=0 for the two-launch path, WN_FUSED_DBG=bits for ablations)"""
+usage: fused_bench.py [C] [L] [B] [d]   (env WN_FUSED_FWD=0 for the two-launch path)
+WN_LIB=libwavenet_amd_measure.so (`make -C wavenet_speech_amd/csrc measure`; as tools/run_bench_with_lib.py takes it) loads the
+measurement build, which WN_FUSED_DBG=bits (ablations) and WN_FUSED_STAMPS=1 (phase stamps of wave 0 of every workgroup) need: the
+product library does not read them."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from wavenet_speech_amd import _lib
+if os.environ.get("WN_LIB"):
+    _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.__file__), os.environ["WN_LIB"])
 from wavenet_speech_amd import functional as HF
 from wavenet_speech_amd import functional_half as FH
 from gputime import timed
@@ -33,6 +38,14 @@ x = FH._hlease(mode, B, C, layout, dev)
 FH._load(lib, mode, torch.randn(B, C, L, device=dev), x, layout, float(lib.wn_hseries_residual_scale()), None, None)
 r, sg, z = (FH._hlease(mode, B, C, layout, dev) for _ in range(3))
 
+stamps = None
+if os.environ.get("WN_FUSED_STAMPS"):
+    # 8 words per workgroup of the launch (csrc/wn_fused.hip: units of 32 columns, four per workgroup, the grid a multiple of 8);
+    # the library writes into the caller's buffer and copies nothing back
+    nwg = (-(-(B * -(-L // 32)) // 4) + 7) // 8 * 8
+    stamps = torch.zeros(nwg, 8, dtype=torch.int64, device=dev)
+    ctypes.CDLL(_lib.LIB_PATH).wn_debug_set_fused_stamp_buffer(ctypes.c_void_p(stamps.data_ptr()))
+
 def run():
     _lib.check(lib.wn_hblock_forward(ctypes.byref(shape), mode.code, HF._p(packed), HF._p(x), HF._p(r), None, 0, HF._p(sg), HF._p(z),
                                      None, HF._stream()), "fwd")
@@ -40,11 +53,10 @@ us = timed(run, calls=200, warmup=20).median * 1e3
 mb = B * L * C * 2 * 4 / 1e6
 print("C %d L %d B %d d %d %s fused=%s dbg=%s: %.1f us per block forward  (%.0f MB algorithmic -> %.2f TB/s)" % (
     C, L, B, d, prec, os.environ.get("WN_FUSED_FWD", "1"), os.environ.get("WN_FUSED_DBG", "0"), us, mb, mb / us * 1e-6 * 1e6 / 1e6))
-if os.environ.get("WN_FUSED_STAMPS"):
+if stamps is not None:
     import numpy as np
-    buf = (ctypes.c_ulonglong * (8 * 4096))()
-    n = ctypes.CDLL(_lib.LIB_PATH).wn_debug_fused_stamps(buf, 4096)
-    a = np.frombuffer(buf, dtype=np.uint64)[:8 * n].reshape(n, 8).astype(np.int64)
+    torch.cuda.synchronize()
+    a = stamps.cpu().numpy()
     a = a[a[:, 7] > 0]
     d = np.diff(a, axis=1)
     names = ["gate half 0 K loop", "gate 0 epilogue", "gate 1 (K loop + epilogue)", "res K loop", "res epilogue", "-", "drain"]

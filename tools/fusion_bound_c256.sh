@@ -8,7 +8,7 @@ OUT=${WN_OUT_DIR:-bench_out}
 mkdir -p $OUT
 for i in 1 2; do
   WN_LIB=libwavenet_amd_l2ops.so python tools/run_bench_with_lib.py --precision f16x3 --full --steps 6 --warmup 2 --no-cpu-baseline --no-breakdown > $OUT/fb_base.$i.json 2>/dev/null
-  WN_HGEMM_DBG=8 WN_HGEMM_DBG_EPI=0 WN_FLAG_CHECK=off WN_LIB=libwavenet_amd_l2ops.so python tools/run_bench_with_lib.py --precision f16x3 --full --steps 6 --warmup 2 --no-cpu-baseline --no-breakdown > $OUT/fb_l2.$i.json 2>$OUT/fb_l2.$i.err
+  WN_HGEMM_DBG=8 WN_HGEMM_DBG_EPI=0 WN_LIB=libwavenet_amd_l2ops.so python tools/run_bench_with_lib.py --precision f16x3 --full --steps 6 --warmup 2 --no-cpu-baseline --no-breakdown > $OUT/fb_l2.$i.json 2>$OUT/fb_l2.$i.err
   for f in fb_base fb_l2; do python -c "
 import json; b=json.loads(open('$OUT/$f.$i.json').read().strip().splitlines()[-1]); k=b['kernels']; print('$f', b['ms_per_step'], {n: round(1e3*v['avg_ms'],1) for n,v in k.items() if n in ('hgemm_kernel<gate>','hgemm_kernel<res>','hgemm_kernel<dx>')})"; done
 done

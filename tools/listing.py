@@ -15,17 +15,17 @@ compiles = 0                                    # runs of the compiler by this p
 _DONE = {}
 
 
-def _make(target, src, csrc, suffix):
+def _make(target, src, csrc, suffix, defs=""):
     """the path of what `target` makes of `csrc/src`, made at most once per process.  Another tree's files are compiled by
-    this tree's Makefile, so both get the same flags"""
+    this tree's Makefile, so both get the same flags; `defs` ("-DWN_MEASURE": the measurement build) is the Makefile's DEFS"""
     global compiles
     csrc = os.path.abspath(csrc or CSRC)
-    key = (target, csrc, src)
+    key = (target, csrc, src) + ((defs,) if defs else ())
     if key in _DONE and os.path.exists(_DONE[key]):
         return _DONE[key]
     out = os.path.join(tempfile.mkdtemp(prefix="wn_%s_" % target), src + suffix)
     compiles += 1
-    r = subprocess.run(["make", "-s", "-C", csrc, "-f", os.path.join(CSRC, "Makefile"), target, "SRC=" + src, "OUT=" + out, "HIPCC=" + HIPCC],
+    r = subprocess.run(["make", "-s", "-C", csrc, "-f", os.path.join(CSRC, "Makefile"), target, "SRC=" + src, "OUT=" + out, "HIPCC=" + HIPCC, "DEFS=" + defs],
                        capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError((r.stderr + (open(out).read() if target == "remarks" and os.path.exists(out) else ""))[-2000:])
@@ -33,9 +33,9 @@ def _make(target, src, csrc, suffix):
     return out
 
 
-def listing(src, csrc=None):
+def listing(src, csrc=None, defs=""):
     """the path of the gfx950 assembly listing of csrc/<src>"""
-    return _make("listing", src, csrc, ".s")
+    return _make("listing", src, csrc, ".s", defs)
 
 
 def kernels(text):
@@ -47,11 +47,11 @@ def kernels(text):
     return out
 
 
-def resources(src, csrc=None):
+def resources(src, csrc=None, defs=""):
     """one dict per kernel of csrc/<src> from hipcc's kernel-resource-usage remarks: "Function Name" and every remark row
     ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]", ...) as strings"""
     rows, cur = [], None
-    for line in open(_make("remarks", src, csrc, ".txt")):
+    for line in open(_make("remarks", src, csrc, ".txt", defs)):
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = {"Function Name": m.group(1)}

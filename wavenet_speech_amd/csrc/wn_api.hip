@@ -14,6 +14,7 @@
 
 #include "wn_host.h"
 #include "wn_kernels.h"
+#include "wn_knobs.h"
 
 using namespace wn;
 
@@ -132,7 +133,7 @@ struct BlockPlan {
 
 BlockPlan plan_block(const wn_block_shape* s) {
     BlockPlan p;
-    static const int mt2 = getenv("WN_MT2_MASK") ? atoi(getenv("WN_MT2_MASK")) : 0;   // measurement knob: 1 gate, 2 res/skip, 4 dx
+    const int mt2 = measure_knob(Knob::WN_MT2_MASK, 0);   // measure build: 64-row slabs for 1 gate, 2 res/skip, 4 dx
     const int Ci = s->in_channels, Co = s->out_channels, Ms = s->skip_rows, k = s->kernel_width;
     // FA: [a;g] interleaved by 32-channel tile pairs;  K = k taps of x
     {
@@ -164,8 +165,8 @@ BlockPlan plan_block(const wn_block_shape* s) {
         g.MT = pick_mt(zt);
         // dz has the shortest K loop (2C) and the heaviest epilogue (reads z, sg, writes da, dg): 64-row slabs at two waves
         // per SIMD let one wave's epilogue overlap the other's MFMAs: 0.616 -> 0.589 ms per launch at 256 ch x 16 x 16000
-        // (WN_DZ_MT=4 restores the 128-row slabs for A/B runs)
-        static const int dz_mt = getenv("WN_DZ_MT") ? atoi(getenv("WN_DZ_MT")) : 2;
+        // (WN_DZ_MT=4 in the measure build restores the 128-row slabs for A/B runs)
+        const int dz_mt = measure_knob(Knob::WN_DZ_MT, 2);
         if (dz_mt == 2 && zt >= 2) g.MT = 2;
         g.nseg = 2;
         g.seg_nkb[0] = cp8(Ms) / 8;

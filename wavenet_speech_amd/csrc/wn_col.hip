@@ -1,6 +1,7 @@
 // Launchers of the column-owner backward-data kernels of a residual block (dz, dx, dx masked by the LeakyReLU in front of the stack).
 // The kernel and its design notes: wn_col_dev.h.
 #include "wn_col_dev.h"
+#include "wn_knobs.h"
 
 namespace wn {
 
@@ -8,8 +9,7 @@ hipError_t launch_hcol(int prec, int epi, const HColArgs& a_in, hipStream_t st) 
     if (a_in.nunit <= 0 || a_in.nks <= 0) return hipSuccess;
     if (prec != HP_BF16 && prec != HP_F16) return hipErrorInvalidValue;
     HColArgs a = a_in;
-    static const int dbg = getenv("WN_COL_DBG") ? atoi(getenv("WN_COL_DBG")) : 0;   // measurement: 1 = no stores
-    a.dbg = dbg;
+    a.dbg = measure_knob(Knob::WN_COL_DBG, 0);   // measure build: 1 = no stores
     a.nwg = (a.nunit + 3) / 4;
     const int nwg = a.nwg;
     const unsigned grid = (unsigned)(((nwg + 7) / 8) * 8);

@@ -30,6 +30,7 @@
 
 #include "wn_half.h"
 #include "wn_half_dev.h"
+#include "wn_knobs.h"
 
 namespace wn {
 
@@ -318,22 +319,21 @@ __global__ __launch_bounds__(256, 2) void hfused_fwd_kernel(const HFusedArgs a) 
     #undef WN_EXTRA
 }
 
-unsigned long long* g_fused_stamps = nullptr;
-int g_fused_stamp_wgs = 0;
+#ifdef WN_MEASURE
+// measure build (tools/fused_bench.py; not in include/wavenet_amd.h): the caller's device buffer of 8 words per workgroup of the
+// largest fused launch it will make, grid = round_up(ceil(units / 4), 8).  Written under WN_FUSED_STAMPS=1 while it is set.
+static unsigned long long* g_fused_stamp_buf = nullptr;
+extern "C" void wn_debug_set_fused_stamp_buffer(void* p) { g_fused_stamp_buf = (unsigned long long*)p; }
+#endif
 
 hipError_t launch_hfused_fwd(int prec, const HFusedArgs& a_in, hipStream_t st) {
     if (a_in.nunit <= 0 || a_in.nstage <= 0) return hipSuccess;
     HFusedArgs a = a_in;
-    static const int dbg = getenv("WN_FUSED_DBG") ? atoi(getenv("WN_FUSED_DBG")) : 0;   // measurement: 1 no stores, 2 no tanh/sigmoid, 4 no MFMA
-    a.dbg = dbg;
-    static unsigned long long* stamps = nullptr;   // measurement (WN_FUSED_STAMPS=1): per-workgroup phase stamps, read back by wn_debug_fused_stamps
-    static const bool want = getenv("WN_FUSED_STAMPS") != nullptr;
-    if (want) {
-        if (!stamps) (void)hipMalloc(&stamps, sizeof(unsigned long long) * 8 * 65536);
-        a.stamps = stamps;
-        g_fused_stamps = stamps;
-        g_fused_stamp_wgs = ((a.nunit + 3) / 4 + 7) / 8 * 8;
-    }
+    a.dbg = measure_knob(Knob::WN_FUSED_DBG, 0);   // measure build: 1 no stores, 2 no tanh/sigmoid, 4 no MFMA
+    a.stamps = nullptr;
+#ifdef WN_MEASURE
+    if (measure_knob(Knob::WN_FUSED_STAMPS, 0)) a.stamps = g_fused_stamp_buf;
+#endif
     const int nwg = (a.nunit + 3) / 4;
     const unsigned grid = (unsigned)(((nwg + 7) / 8) * 8);
     const bool bf = prec == HP_BF16;
@@ -360,10 +360,3 @@ hipError_t launch_hfused_fwd(int prec, const HFusedArgs& a_in, hipStream_t st) {
 }
 
 }  // namespace wn
-// measurement only (tools/fused_stamps.py; not in include/wavenet_amd.h): copy the phase stamps of the last fused launch
-extern "C" int wn_debug_fused_stamps(unsigned long long* host, int max_wgs) {
-    if (!wn::g_fused_stamps) return 0;
-    const int n = wn::g_fused_stamp_wgs < max_wgs ? wn::g_fused_stamp_wgs : max_wgs;
-    if (hipMemcpy(host, wn::g_fused_stamps, sizeof(unsigned long long) * 8 * n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return n;
-}

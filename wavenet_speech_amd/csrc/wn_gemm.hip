@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "wn_kernels.h"
+#include "wn_knobs.h"
 
 namespace wn {
 
@@ -467,24 +468,16 @@ static hipError_t launch_one(GemmArgs a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// Variant 0 (default): MT x 4 tiles, B prefetched 3 k-blocks ahead, one wave per SIMD.
-// WN_GEMM_VARIANT=1 selects prefetch depth 1 for A/B measurements (tools/gemm_sweep.py).
-static int gemm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("WN_GEMM_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
+// MT x 4 tiles, B prefetched 3 k-blocks ahead, one wave per SIMD.
+// The measure build also holds prefetch depth 1 and runs it under WN_GEMM_VARIANT=1 (tools/gemm_sweep.py).
 template <int EPI>
 static hipError_t launch_epi(int MT, const GemmArgs& a, hipStream_t st) {
-    const int v = gemm_variant();
     if (MT == 4) {
         // measured on MI355X (tools/gemm_sweep.py, profiles/r01/gemm_variants.txt): prefetch depth 1 vs 3 is a
         // tie; 64-column tiles at two waves per SIMD (NT=2) were 20-30 % slower and are not instantiated.
-        if (v == 1) return launch_one<4, 4, EPI, 1, 1>(a, st);
+        if constexpr (kMeasureBuild) {
+            if (measure_knob(Knob::WN_GEMM_VARIANT, 0) == 1) return launch_one<4, 4, EPI, 1, 1>(a, st);
+        }
         return launch_one<4, 4, EPI, 3, 1>(a, st);
     }
     if (MT == 2) return launch_one<2, 4, EPI, 3, 2>(a, st);

@@ -26,6 +26,7 @@
 
 #include "wn_half.h"
 #include "wn_half_dev.h"
+#include "wn_knobs.h"
 
 namespace wn {
 
@@ -1111,8 +1112,7 @@ static hipError_t launch_h8(int epi, const HGemmArgs& a, unsigned grid, hipStrea
 
 template <int MT, int P, bool BF>
 static hipError_t launch_h(int epi, const HGemmArgs& a, unsigned grid, hipStream_t st) {
-    static const bool report = getenv("WN_HGEMM_OCCUPANCY") != nullptr;   // measurement: print the occupancy API's answer once
-    if (report) {
+    if (measure_knob(Knob::WN_HGEMM_OCCUPANCY, 0)) {   // measure build: print the occupancy API's answer once
         static bool done = false;
         if (!done) {
             done = true;
@@ -1143,8 +1143,8 @@ static hipError_t launch_h(int epi, const HGemmArgs& a, unsigned grid, hipStream
 hipError_t launch_hgemm(int prec, int MT, int epi, const HGemmArgs& a_in, hipStream_t st) {
     if (a_in.nslab <= 0 || a_in.B <= 0 || a_in.L <= 0) return hipSuccess;
     HGemmArgs a = a_in;
-    static const int dbg = getenv("WN_HGEMM_DBG") ? atoi(getenv("WN_HGEMM_DBG")) : 0;
-    static const int dbg_epi = getenv("WN_HGEMM_DBG_EPI") ? atoi(getenv("WN_HGEMM_DBG_EPI")) : -1;   // restrict the knob to one epilogue class
+    const int dbg = measure_knob(Knob::WN_HGEMM_DBG, 0);
+    const int dbg_epi = measure_knob(Knob::WN_HGEMM_DBG_EPI, -1);   // restrict the knob to one epilogue class
     a.dbg = (dbg_epi < 0 || dbg_epi == epi) ? dbg : 0;
     if (MT == 10) {  // hgemm8_kernel, four waves on 128 x 256 tiles, two workgroups per CU (one-plane modes)
         if (a.L % 16 != 0 || prec == HP_F16X3) return hipErrorInvalidValue;

@@ -18,6 +18,7 @@
 
 #include "wn_half.h"
 #include "wn_host.h"
+#include "wn_knobs.h"
 
 using namespace wn;
 
@@ -70,13 +71,13 @@ struct HPlan {
     //            against hgemm_kernel at cfg3 (alternating runs on one device, ms per launch): gate 0.363 vs 0.386, skips_sum
     //            2.03 vs 2.24, dx 0.381 vs 0.380, res 0.201 vs 0.199, dz 0.317 vs 0.300; step 65.5 vs 66.7 ms -> `prefer` is set
     //            for the gate and skips_sum GEMMs.  The one-plane modes lose with it (cfg5 f16 89.1 vs 84.7 ms/step).
-    //            WN_HGEMM16=0: never; =2: wherever the shape allows, every mode (tests); WN_HGEMM16_COLS=128: narrow form.
+    //            WN_HGEMM16=0: never; =2: wherever the shape allows, every mode (tests); WN_HGEMM16_COLS=128 (measure build): narrow form.
     //            One-plane modes: the same code as FOUR waves on 128 x 256 tiles, two workgroups per CU (`quad`; a 32-channel
     //            stage is only 24 KiB there): every block GEMM whose row count is a multiple of 128 (`allow_quad`).
     int wide = 0, quad = 0;
     void init(int out_rows, int planes_, bool long_k = false, int length = 0, bool prefer_k32 = false, bool allow_quad = false) {
-        static const int knob = getenv("WN_HGEMM16") ? atoi(getenv("WN_HGEMM16")) : 1;
-        static const bool narrow_only = getenv("WN_HGEMM16_COLS") && atoi(getenv("WN_HGEMM16_COLS")) == 128;
+        const int knob = hgemm16_form();
+        const bool narrow_only = measure_knob(Knob::WN_HGEMM16_COLS, 0) == 128;
         const bool rows_ok = out_rows % 256 == 0 && length > 0;
         const bool fits_wide = rows_ok && planes_ == 2 && length % 16 == 0 && !narrow_only;
         const bool fits_narrow = rows_ok && length % 128 == 0;
@@ -119,16 +120,10 @@ struct HFusedPlan {
     size_t bytes() const { return on ? align256((size_t)stages() * kFStageBytes) + bias_bytes() + 1024 : 0; }
 };
 
-bool fused_forward_enabled() {
-    const char* e = getenv("WN_FUSED_FWD");      // read per call: the parity tests compare both forms in one process
-    return !(e && atoi(e) == 0);
-}
+bool fused_forward_enabled() { return switch_on(Switch::WN_FUSED_FWD); }
 
 // column-owner dz / dx (wn_col.hip): the blocks the fused forward takes, when the skip path is as wide as the block
-bool col_backward_enabled() {
-    const char* e = getenv("WN_COL_BWD");        // read per call: the parity tests compare both forms in one process
-    return !(e && atoi(e) == 0);
-}
+bool col_backward_enabled() { return switch_on(Switch::WN_COL_BWD); }
 
 struct HBlockPlan {
     HPlan fa, fr, fs, ka, kb;
@@ -657,8 +652,7 @@ int wn_hblock_backward_input(const wn_block_shape* s, int precision, const void*
 // ---- dx of `upper` and dz of `lower` (the block below it in the stack) in one launch ---------------------------------------------
 namespace {
 bool pair_fusable(const wn_block_shape* u, const wn_block_shape* l, int precision, const HBlockPlan& pu, const HBlockPlan& pl) {
-    const char* e = getenv("WN_COL_PAIR");       // read per call (tests compare both forms)
-    return !(e && atoi(e) == 0) && pu.col && pl.col && cp32(u->in_channels) == cp32(l->out_channels) && u->in_channels == l->out_channels &&
+    return switch_on(Switch::WN_COL_PAIR) && pu.col && pl.col && cp32(u->in_channels) == cp32(l->out_channels) && u->in_channels == l->out_channels &&
            u->batch == l->batch && u->length == l->length && u->ld == l->ld && u->halo == l->halo && u->skip_rows == l->skip_rows &&
            pu.kb.nslab == 1 && pl.ka.nslab == 1 && !pu.kb.k32 && !pl.ka.k32 && hp_planes(precision) == 1;
 }
@@ -1025,8 +1019,7 @@ struct HWPlan {
 };
 
 bool composite_wgrad(int ci, int co, int ms) {
-    const char* e = getenv("WN_HWGRAD_COMPOSITE");   // read per call (tests compare both forms)
-    return !(e && atoi(e) == 0) && cp32(ci) <= 128 && cp32(co) <= 128 && cp32(ms) <= 128;
+    return switch_on(Switch::WN_HWGRAD_COMPOSITE) && cp32(ci) <= 128 && cp32(co) <= 128 && cp32(ms) <= 128;
 }
 
 // the destinations a block's weight gradients need: the residual path's four only when the block has a residual consumer

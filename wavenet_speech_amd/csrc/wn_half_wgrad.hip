@@ -26,6 +26,7 @@
 #include <utility>
 
 #include "wn_half.h"
+#include "wn_knobs.h"
 
 namespace wn {
 
@@ -295,8 +296,7 @@ static hipError_t launch_hw(int prec, const HWgradArgs& a, hipStream_t st) {
 
 hipError_t launch_hwgrad(int prec, const HWgradArgs& a, hipStream_t st) {
     if (a.ntile_total <= 0 || a.nsplit <= 0) return hipSuccess;
-    static const int dbg = getenv("WN_HWGRAD_DBG") ? atoi(getenv("WN_HWGRAD_DBG")) : 0;
-    if (dbg) {
+    if (const int dbg = measure_knob(Knob::WN_HWGRAD_DBG, 0)) {   // measure build: 1 every split re-reads the first, 2 no DMA in the K loop
         HWgradArgs b = a;
         b.xcd_map |= 2 * dbg;
         return launch_hw(prec, b, st);
