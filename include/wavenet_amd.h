@@ -1080,6 +1080,64 @@ int wn_haplotag(const unsigned char* ops, long long ops_stride, const int* ops_l
                 const int* pos, const int* root, const unsigned char* parity, const int* set_size, unsigned char* hp, int* ps,
                 int* weight, int* n_observed, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Realignment of reads against the called haplotypes (wavenet_speech_amd/realign.py): what GATK's indel
+ * realigner and HaplotypeCaller, longshot and margin do after the calls -- a read is aligned against the two haplotypes the calls
+ * and their phasing spell, the better score says which one it lies on, and that alignment is carried back to reference
+ * coordinates.  The DP is wn_pair_align's, run by the caller once per haplotype; these are the two steps around it.  Integer
+ * arithmetic only; all pointers are DEVICE pointers.  tests/realign_ref.py holds the same definitions as plain loops.
+ *   A HAPLOTYPE h (0 <= h < haplotypes) over a reference of reference_len positions: call [haplotypes][R] bytes, the label it
+ *   carries at forward position p (0: deleted); ins_len [haplotypes][R] bytes and ins_bases [haplotypes][R][max_ins] bytes, the
+ *   insertion it carries after p.  reference [R] int32: the reference's labels.
+ *   wn_haplotype_windows: for read b with the window [lo[b], lo[b] + n), n = ref_lengths[b], and haplotype h, two rows IN READ
+ *   ORIENTATION.  In forward order position p gives, with v = call[h][p]: v == 0: op 3 and no label; else the label v and op 1 if
+ *   v == reference[p], else op 2; then, only for p < lo + n - 1, ins_len[h][p] labels with op 4 (the insertion after the window's
+ *   last position is outside the window, as in wn_pileup).  On strand[b] == 1 both rows are reversed and labels 1..4 complemented
+ *   (5 - v), other labels kept: wn_pileup's orientation, so the label row is wn_pair_align's `ref`.
+ *     labels  [haplotypes][B][max_hap_ops] int32, lengths [haplotypes][B] int32: the haplotype's labels over the window
+ *     ops     [haplotypes][B][max_hap_ops] bytes, ops_len [haplotypes][B] int32: haplotype against reference: 1 / 2 both, 3 a
+ *             reference label the haplotype lacks, 4 a haplotype label the reference lacks
+ *     used    [B] int8: 1 written, 0 skipped, -1 bad
+ *   Both rows are zero behind their lengths.  A read with strand < 0 or ref_lengths == 0 is SKIPPED: lengths 0, used 0.  A read that
+ *   is not skipped is BAD when strand > 1, lo < 0, ref_lengths < 0, lo + n > R, an ins_len of its window is above max_ins, or a row
+ *   of ANY of its haplotypes needs more than max_hap_ops ops: lengths 0 on every haplotype, used -1, counted once in *bad (DEVICE
+ *   int, caller-zeroed, may be NULL).  No bad value is used as an index; a row is never truncated.  One launch, one workgroup per
+ *   (read, haplotype), two passes over the window; no workspace, nothing is read back.
+ *   wn_lift_ops: row b of a_ops[pick[b]] is A, the read against the haplotype as wn_pair_align wrote it (1 / 2 both, 3 a haplotype
+ *   label only, 4 a read label only); row b of hap_ops[pick[b]] is Hh, wn_haplotype_windows' row.  Row (h, b) of a_ops is at a_ops +
+ *   h * a_hap_stride + b * a_stride with a_ops_len [haplotypes][B]; hap_ops likewise, with hap_lengths [haplotypes][B] the
+ *   haplotype's labels.  Their composition, the read against its reference window, is the sequential loop
+ *     loop: while Hh's next op is 3: emit 3, take it;  while A's next op is 4: emit 4, take it;  if both rows are used up: stop;
+ *           a = A's next op is 1 or 2 (else 3), g = Hh's next op is 1 or 2 (else 4), take both (they share one haplotype label);
+ *           a and g: emit 1 if ref[i] == query[j] else 2 (i, j the reference and read labels emitted so far: compared afresh);
+ *           a only: emit 4;  g only: emit 3;  neither: emit nothing
+ *   written to row b of ops (ops_stride bytes, zero behind ops_len[b]) with stats [B][4] int32 = matches, mismatches, gap columns,
+ *   length and score [B] int32 in half units under the affine costs with wn_pair_align's end-gap rule: a run of one gap op costs
+ *   gap_open + (n - 1) gap_extend, and with end_gaps_free the runs that touch either end of the row cost nothing.  The result
+ *   consumes exactly ref_lengths[b] and query_lengths[b] labels: it is an op row as wn_pair_align writes one.
+ *   used[b] == 0 (a skipped window) passes through: ops_len 0, stats and score 0.  Otherwise a row is BAD when used[b] < 0, pick[b]
+ *   outside [0, haplotypes), ref_lengths outside [1, max_ref_len], query_lengths outside [0, max_query_len], a length of A or Hh
+ *   outside its row, hap_lengths outside [0, max_hap_len], an op outside 1..4, A does not consume exactly hap_lengths and
+ *   query_lengths labels, Hh not exactly ref_lengths and hap_lengths, or the result would pass max_ops: ops_len 0, stats -1, score
+ *   -2^31 (wn_pair_align's poison), counted once in *bad.  One launch, one workgroup per read.  workspace: wn_lift_ops_workspace_bytes (three int32 per
+ *   haplotype index and read; 0 for a bad or unsupported shape), 4-byte aligned.
+ * Checked before the launch, in this order.  WN_ERR_BAD_SHAPE: haplotypes, batch, reference_len, max_hap_ops, max_hap_len,
+ * a_max_ops, max_ref_len, max_query_len or max_ops < 1, max_ins < 0, a negative stride, end_gaps_free not 0 or 1.
+ * WN_ERR_UNSUPPORTED: haplotypes > 2, batch > 65535, reference_len > 2^26, max_ins > 8, max_hap_ops, max_hap_len or max_ref_len >
+ * 65535, max_query_len > 8192, a_max_ops or max_ops > 65535 + 8192, the costs outside wn_pair_align's limits.  WN_ERR_NULL: any
+ * pointer but bad; ins_bases only with max_ins > 0.  WN_ERR_WORKSPACE: workspace_bytes too small or workspace misaligned. */
+int wn_haplotype_windows(const unsigned char* call, const unsigned char* ins_len, const unsigned char* ins_bases /* with max_ins > 0 */,
+                         const int* reference, const int* lo, const int* ref_lengths, const int* strand, int haplotypes, int batch,
+                         int reference_len, int max_ins, int max_hap_ops, int* labels, int* lengths, unsigned char* ops, int* ops_len,
+                         signed char* used, int* bad /* may be NULL */, wn_stream_t stream);
+size_t wn_lift_ops_workspace_bytes(int batch, int max_hap_len);
+int wn_lift_ops(const unsigned char* a_ops, long long a_hap_stride, long long a_stride, const int* a_ops_len, int a_max_ops,
+                const unsigned char* hap_ops, long long hap_hap_stride, long long hap_stride, const int* hap_ops_len,
+                const int* hap_lengths, int max_hap_ops, int max_hap_len, const signed char* used, const int* pick, const int* ref,
+                long long ref_stride, const int* ref_lengths, const int* query, long long query_stride, const int* query_lengths,
+                int haplotypes, int batch, int max_ref_len, int max_query_len, int max_ops, int match, int mismatch, int gap_open,
+                int gap_extend, int end_gaps_free, unsigned char* ops, long long ops_stride, int* ops_len, int* score, int* stats,
+                void* workspace, size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -35,6 +35,8 @@ from .genotype import (Evidence, GenotypeRecord, Genotypes, GenotypeWeights, cal
                        pileup_evidence, vcf_genotype_records)
 from .phase import (Haplotags, PhasedRecord, PhaseLinks, PhaseSites, Phasing, haplotag, phase_chain, phase_links, phase_sites,  # noqa: F401
                     phased_records, vcf_phased_records)
+from .realign import (HaplotypeCalls, HaplotypeWindows, Realignment, haplotype_calls, haplotype_windows, lift_alignment,  # noqa: F401
+                      realign)
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

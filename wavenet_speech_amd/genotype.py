@@ -18,8 +18,8 @@ Everything the kernels add or compare is an integer, so results equal the host r
 runs are bitwise identical.  Neither function synchronises with the host.  There is no CPU fallback: CPU tensors raise (the host
 helpers genotype_records / vcf_genotype_records take tensors on any device).
 Read-backed phasing of the heterozygous calls and a haplotype tag per read are phase.py's.
-Not built: realignment against candidate haplotypes, more than one insertion allele per site, strand bias, a gap_qual
-derived from quality_profile.
+Realignment of the reads against the called haplotypes is realign.py's.
+Not built: more than one insertion allele per site, strand bias, a gap_qual derived from quality_profile.
 """
 import ctypes
 import math

@@ -17,8 +17,8 @@ runs are bitwise identical.  phase_sites synchronises with the host once (the nu
 else does.  There is no CPU fallback: CPU tensors raise (the host helpers phased_records / vcf_phased_records take tensors on any
 device).
 Not built: phasing of heterozygous insertions, a per-set tally for reads that span sets (a read is tagged in the set of its most
-confident observation), a weighted-MEC optimum (this is greedy best-link chaining), a phase quality beyond the link margin,
-realignment against the two haplotypes.
+confident observation), a weighted-MEC optimum (this is greedy best-link chaining), a phase quality beyond the link margin.
+Realignment against the two haplotypes is realign.py's.
 """
 from collections import namedtuple
 

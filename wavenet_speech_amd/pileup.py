@@ -22,8 +22,8 @@ Labels are the decoders': 1..4 = A, G, C, T (DEFAULT_ALPHABET " AGCT"), the comp
 A gap inside a repeat is placed by pairwise_align's tie rule in READ orientation, so forward and reverse reads may place it at
 opposite ends of the repeat and split its support: left_align (leftalign.py) between pairwise_align and pileup normalises that.
 Genotype likelihoods and diploid calls with QUAL are genotype.py's, on the same reads beside these tables.
-Not built: realignment against candidate haplotypes, a strand split for insertions, more than one reference ([R] positions of one
-row).
+Realignment against the called haplotypes is realign.py's.
+Not built: a strand split for insertions, more than one reference ([R] positions of one row).
 """
 from collections import namedtuple
 
