@@ -1138,6 +1138,41 @@ int wn_lift_ops(const unsigned char* a_ops, long long a_hap_stride, long long a_
                 int gap_extend, int end_gaps_free, unsigned char* ops, long long ops_stride, int* ops_len, int* score, int* stats,
                 void* workspace, size_t workspace_bytes, int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- Banded global pairwise alignment (wavenet_speech_amd.banded_align): wn_pair_align's recurrence, tie
+ * rules, end-cell rule and op rows inside a per-pair stripe of diagonals.  ref, query, their strides and lengths, the costs,
+ * end_gaps_free, score, stats, ops, ops_len and bad: as wn_pair_align takes them.  diag_lo, diag_hi: DEVICE int32 [B].
+ *   Cell (i, j), 0 <= i <= N_b, 0 <= j <= M_b, is IN BAND iff diag_lo[b] <= j - i <= diag_hi[b]; the width is
+ *   diag_hi - diag_lo + 1.  H, E and F of a cell that is not in band are -infinity wherever they are read; in-band cells with
+ *   i, j >= 1 follow wn_pair_align's recurrence, candidate order and tie rules; in-band border cells take the full matrix's
+ *   border values, whether or not (0, 0) is in band.
+ *   End cell: (N, M) with end gaps penalised; with end_gaps_free the candidates (N, M), (N, M-1) .. (N, 0), (N-1, M) .. (0, M) in
+ *   this order, in-band cells only: the first is taken and a later one replaces it only if strictly greater.
+ *   NO ALIGNMENT (not an error): with end_gaps_free the stripe misses the rectangle (diag_lo > M_b or diag_hi < -N_b); with end
+ *   gaps penalised (N_b, M_b) is not in band.  Then status 0, score INT_MIN, stats 0, ops_len 0, edge_hits 0; not counted in *bad.
+ *   The trace and the end gaps are wn_pair_align's: an op row that consumes exactly N_b and M_b labels.  If every cell of the
+ *   full matrix's traced path is in band, score, stats and ops equal wn_pair_align's; for any stripe the score is <= its score.
+ *   status     [B] int8: 1 aligned, 0 no alignment, -1 a bad pair
+ *   edge_hits  [B] int32 or NULL: the path cells (the cell where the trace stopped, then the cell after every op up to the end
+ *              cell) with j - i == diag_lo or j - i == diag_hi; 0 when the stripe never held the path; -1 for a bad pair
+ * A bad pair -- a length negative or above its maximum, diag_lo > diag_hi, or a width above max_band -- is poisoned as
+ * wn_pair_align poisons one (score INT_MIN, stats -1, ops_len 0), has status -1 and counts once in *bad; no bad value is used
+ * as an index.  ops == NULL and stats == NULL is the score-only form: no workspace, no trace, and edge_hits must be NULL.
+ * workspace: wn_banded_align_workspace_bytes (0 for a bad or unsupported shape), 16-byte aligned:
+ *   round_up(batch * (max_ref_len + max_query_len + 1) * ceil(max_band / 8) * 2, 16)       4 bits per in-band cell of a step
+ *   + batch * round_up(max_ref_len + max_query_len, 16)                                      the path's ops, back to front
+ * One launch, one workgroup per pair; widths up to 512 run in one wave, wider ones in 256 threads.  Nothing is read back.
+ * Checked on the host in this order: batch, max_ref_len, max_query_len, max_band < 1 (WN_ERR_BAD_SHAPE); max_band > 2048,
+ * max_ref_len > 65535, max_query_len > 65535, batch > 65535, the costs outside wn_pair_align's limits (WN_ERR_UNSUPPORTED); a
+ * required pointer NULL, ops without ops_len or the reverse, edge_hits in the score-only form (WN_ERR_NULL); the workspace
+ * (WN_ERR_WORKSPACE).  Nothing is launched then.  The tools that walk op rows keep their own limit of 8192 query labels. */
+size_t wn_banded_align_workspace_bytes(int batch, int max_ref_len, int max_query_len, int max_band);
+int wn_banded_align(const int* ref, long long ref_stride, const int* ref_lengths, const int* query, long long query_stride,
+                    const int* query_lengths, const int* diag_lo, const int* diag_hi, int batch, int max_ref_len, int max_query_len,
+                    int max_band, int match, int mismatch, int gap_open, int gap_extend, int end_gaps_free, int* score,
+                    int* stats /* may be NULL */, unsigned char* ops /* may be NULL */, int* ops_len /* with ops */,
+                    signed char* status, int* edge_hits /* may be NULL */, void* workspace, size_t workspace_bytes,
+                    int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

@@ -18,6 +18,7 @@ from .decoding import (BaseQualities, CTCAlignment, CTCBeamDecoder, PairwiseAlig
                        QualityProfile, ctc_base_qualities, ctc_beam_decode, ctc_forced_align, ctc_greedy_decode, edit_distance,
                        fastq_records, fit_quality_calibration, format_alignment, labels_to_strings, pairwise_align,
                        quality_profile)
+from .decoding import BandedAlignment, band_from_ops, banded_align  # noqa: F401
 from .functional_half import check_fp16_overflow  # noqa: F401
 from .basecalling import Basecaller, Basecalls, ChunkPlan, chunk_plan, receptive_field  # noqa: F401
 from .normalise import read_med_mad, read_normalisation, read_order_statistics, read_quantiles  # noqa: F401

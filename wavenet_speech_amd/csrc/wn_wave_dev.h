@@ -14,6 +14,7 @@
 //                               several values in place, their shuffles interleaved.  No LDS, no barrier.
 //   wave_max_dpp(v)             the maximum of an int over the wave by DPP row operations and a readlane: a scalar.
 //   wave_shr1(v, fill)          lane l gets lane l - 1's v, lane 0 gets fill (DPP wave_shr:1).  int and double.
+//   wave_shl1(v, fill)          lane l gets lane l + 1's v, lane 63 gets fill (DPP wave_shl:1).  int.
 //   edge_publish(edge, k, lane, wave, v) / edge_left(edge, k, wave)   the neighbour hand-off of a systolic step over a caller-declared
 //                               __shared__ T edge[2][kWaves]: lane 63 stores its wave's last value of step k; lane 0 of a wave > 0
 //                               takes what wave - 1 published in step k - 1.  NO barrier in either: the kernel has one __syncthreads()
@@ -102,6 +103,9 @@ __device__ __forceinline__ double wave_shr1(double v, double fill) {
     const int lo = wave_shr1(__double2loint(v), __double2loint(fill)), hi = wave_shr1(__double2hiint(v), __double2hiint(fill));
     return __hiloint2double(hi, lo);
 }
+
+constexpr int kDppWaveShl1 = 0x130;      // DPP control word wave_shl:1
+__device__ __forceinline__ int wave_shl1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, kDppWaveShl1, 0xf, 0xf, false); }
 
 template <typename T, int kWaves>
 __device__ __forceinline__ void edge_publish(T (*edge)[kWaves], int step, int lane, int wave, T v) { if (lane == 63) edge[step & 1][wave] = v; }

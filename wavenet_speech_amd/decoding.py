@@ -266,6 +266,123 @@ def edit_distance(a, a_lengths, b, b_lengths):
     return torch.where(score == -2 ** 31, torch.full_like(score, -1), -score)
 
 
+MAX_BAND = 2048                               # diagonals of a stripe of banded_align
+MAX_BANDED_LEN = 65535                        # labels of either row of banded_align; the tools downstream keep MAX_PAIR_QUERY
+
+
+class BandedAlignment(namedtuple("BandedAlignment", "alignment status edge_hits diag_lo diag_hi")):
+    """alignment: a PairwiseAlignment (every tool that takes pairwise_align's takes it); status [B] int8: 1 aligned, 0 no alignment
+    inside the stripe (score -2^30, counts 0, ops_len 0), -1 a bad pair; edge_hits [B] int32: the path cells on the stripe's first
+    or last diagonal, 0 when the stripe never held the path (None in the score-only form); diag_lo, diag_hi [B] int32: the stripes
+    as the kernel took them.  All on the device."""
+    __slots__ = ()
+
+
+def banded_align(ref, ref_lengths, query, query_lengths, diag_lo, diag_hi, max_band, match=5, mismatch=-4, gap_open=10,
+                 gap_extend=0.5, end_gaps_free=True, return_ops=True, score_only=False):
+    """pairwise_align inside a stripe of diagonals per pair: cell (i, j) of reference label i against query
+    label j takes part iff diag_lo[b] <= j - i <= diag_hi[b]; recurrence, tie rules, end-cell rule, costs and op rows are
+    pairwise_align's.  Work and workspace go with (N + M) * max_band instead of N * M, and both rows may hold up to 65535 labels.
+    diag_lo, diag_hi: [B] integers (band_from_ops and ReadMapping.band make them on the device); max_band: a host integer in
+    [1, 2048], the widest stripe of the batch -- it sizes the launch and the workspace.  If the whole path of pairwise_align lies
+    inside the stripe the result equals pairwise_align's, ties included; otherwise the score is at most its score.  A stripe
+    that misses the rectangle (or, with end gaps penalised, its far corner) gives status 0; a length outside its range,
+    diag_lo > diag_hi or a stripe wider than max_band poisons the pair (status -1; reported through check_device_flags()).
+    return_ops=False leaves the op rows out (counts only); score_only=True runs no trace at all: counts, ops and edge_hits are None.
+    Returns BandedAlignment."""
+    what = "banded_align"
+    costs = _args.affine_costs(what, match, mismatch, gap_open, gap_extend)
+    ref, ref_lengths = _pair_rows(ref, ref_lengths, what, "ref")
+    query, query_lengths = _pair_rows(query, query_lengths, what, "query")
+    B, N, M = int(ref.shape[0]), int(ref.shape[1]), int(query.shape[1])
+    if query.shape[0] != B or query.device != ref.device:
+        raise ValueError("wavenet_speech_amd.%s: ref and query must hold the same number of rows on one device" % what)
+    if B < 1:
+        raise ValueError("wavenet_speech_amd.%s: need at least one pair" % what)
+    if N > MAX_BANDED_LEN or M > MAX_BANDED_LEN:
+        raise ValueError("wavenet_speech_amd.%s: at most %d reference and query labels per pair, got %d and %d" % (what, MAX_BANDED_LEN, N, M))
+    if isinstance(max_band, bool) or not isinstance(max_band, int) or not 1 <= max_band <= MAX_BAND:
+        raise ValueError("wavenet_speech_amd.%s: max_band must be an integer in [1, %d], got %r" % (what, MAX_BAND, max_band))
+    dev = ref.device
+    diag_lo = _args.lengths(diag_lo, B, dev, what, "diag_lo")
+    diag_hi = _args.lengths(diag_hi, B, dev, what, "diag_hi")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        score = torch.empty(B, dtype=torch.int32, device=dev)
+        status = torch.empty(B, dtype=torch.int8, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        stats = ops = ops_len = ws = edge_hits = None
+        ws_bytes = 0
+        if not score_only:
+            ws_bytes = lib.wn_banded_align_workspace_bytes(B, N, M, max_band)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            stats = torch.empty(B, 4, dtype=torch.int32, device=dev)
+            edge_hits = torch.empty(B, dtype=torch.int32, device=dev)
+            if return_ops:
+                ops = torch.empty(B, N + M, dtype=torch.uint8, device=dev)
+                ops_len = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.wn_banded_align(_p(ref), ref.stride(0), _p(ref_lengths), _p(query), query.stride(0), _p(query_lengths), _p(diag_lo),
+                                       _p(diag_hi), B, N, M, max_band, costs[0], costs[1], costs[2], costs[3], int(bool(end_gaps_free)),
+                                       _p(score), _p(stats), _p(ops), _p(ops_len), _p(status), _p(edge_hits), _p(ws), ws_bytes, _p(bad),
+                                       _stream()), "wn_banded_align")
+        _args.note_bad(bad, lambda n, N=N, M=M: "wavenet_speech_amd.%s: ref_lengths outside [0, %d], query_lengths outside [0, %d], "
+                       "diag_lo > diag_hi or a stripe wider than max_band in %d pair(s)" % (what, N, M, n))
+    cols = [None] * 4 if stats is None else [stats[:, k] for k in range(4)]
+    return BandedAlignment(PairwiseAlignment(score.float() * 0.5, cols[0], cols[1], cols[2], cols[3], ops, ops_len), status, edge_hits,
+                           diag_lo, diag_hi)
+
+
+def _clamp_band(lo, hi, max_band):
+    """[lo, hi] about its centre to at most max_band diagonals (tensors; None: as they are)"""
+    if max_band is None:
+        return lo, hi
+    if isinstance(max_band, bool) or not isinstance(max_band, int) or max_band < 1:
+        raise ValueError("wavenet_speech_amd: max_band must be a positive integer or None, got %r" % (max_band,))
+    over = (hi - lo + 1 - max_band).clamp(min=0)
+    lo = lo + torch.div(over, 2, rounding_mode="floor")
+    return lo, torch.where(over > 0, lo + (max_band - 1), hi)
+
+
+def band_from_ops(alignment, margin=0, max_band=None, end_gaps_free=True):
+    """(diag_lo, diag_hi), [B] int32 on the device: the stripe of diagonals j - i the path of every op row of `alignment` (a
+    PairwiseAlignment with ops) runs through, widened by `margin` on each side and, with max_band, clamped about its centre to that
+    width.  The path is read off the row alone: with h the leading run of one gap kind and t the row's length less (with
+    end_gaps_free) its trailing run of one gap kind, its cells are the cell before column h and the cell after every column in
+    [h, t); a row of end gaps only is that single cell.  Under this stripe (margin 0) banded_align returns pairwise_align's result.
+    torch ops on the device; nothing is read back."""
+    what = "band_from_ops"
+    ops, ops_len = _alignment_ops(alignment, what)
+    if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+        raise ValueError("wavenet_speech_amd.%s: margin must be a non-negative integer, got %r" % (what, margin))
+    B, P = int(ops.shape[0]), int(ops.shape[1])
+    dev = ops.device
+    n = ops_len.to(torch.int64).clamp(0, P)
+    if P == 0:
+        zero = torch.zeros(B, dtype=torch.int32, device=dev)
+        return _clamp_band(zero - margin, zero + margin, max_band)
+    col = torch.arange(P, device=dev).unsqueeze(0)
+    inside = col < n.unsqueeze(1)
+    first = ops[:, 0]
+    last = ops.gather(1, (n - 1).clamp(min=0).unsqueeze(1)).squeeze(1)
+    # h: the columns before the first one that differs from a leading gap op; t: the same from the end
+    differs = (ops != first.unsqueeze(1)) | ~inside
+    h = torch.where(differs.any(1), differs.int().argmax(1), n)
+    h = torch.where((first >= OP_REF_GAP) & (n > 0), h, torch.zeros_like(h))
+    differs = ((ops != last.unsqueeze(1)) & inside).flip(1)          # from column P - 1 down
+    run = torch.where(differs.any(1), differs.int().argmax(1) - (P - n), n)
+    t = n - run if end_gaps_free else n
+    t = torch.where((last >= OP_REF_GAP) & (n > 0), t, n)
+    t = torch.maximum(t, h)
+    step = ((ops != OP_REF_GAP) & inside).to(torch.int32) - ((ops != OP_QUERY_GAP) & inside).to(torch.int32)
+    after = step.cumsum(1, dtype=torch.int32)                        # the diagonal after every column
+    start = torch.where(h > 0, after.gather(1, (h - 1).clamp(min=0).unsqueeze(1)).squeeze(1), torch.zeros_like(after[:, 0]))
+    on_path = (col >= h.unsqueeze(1)) & (col < t.unsqueeze(1))
+    big = 1 << 30
+    lo = torch.minimum(start, torch.where(on_path, after, torch.full_like(after, big)).amin(1))
+    hi = torch.maximum(start, torch.where(on_path, after, torch.full_like(after, -big)).amax(1))
+    return _clamp_band(lo - margin, hi + margin, max_band)
+
+
 def format_alignment(ref_row, query_row, ops_row, alphabet=DEFAULT_ALPHABET):
     """host helper: the three text lines of one alignment as needle prints them -- the reference with '-' where the query has
     a label against a gap, '|' for a match and '.' for a mismatch, the query with '-' likewise.  alphabet[i] is the character

@@ -310,6 +310,28 @@ class ReadMapping(_MapFields):
         hi = (self.ref_end.long() + flank).clamp(max=self.reference.R)
         return lo.int(), torch.where(self.mapped, hi - lo, torch.zeros_like(lo)).int()
 
+    def band(self, flank=0, margin=64, max_band=None):
+        """(diag_lo, diag_hi), [B] int32 on the device: the stripe of diagonals j - i that banded_align(rows, lengths, query,
+        query_lengths, ...) takes for the rows labels(flank) returns against the whole reads -- the diagonals of the chain's two end
+        points in those rows' coordinates, widened by `margin` on each side and, with max_band, clamped about the centre to that width
+        (DESIGN.md 7ab).  With (lo, n) = window(flank) the end points are query_start - (ref_start - lo) and query_end - (ref_end - lo)
+        on strand 0, query_start - (lo + n - ref_end) and query_end - (lo + n - ref_start) on strand 1.  (0, 0) where unmapped: the
+        window's length is 0.  No host synchronisation."""
+        from .decoding import _clamp_band
+        what = "ReadMapping.band"
+        margin = _int_in(what, "margin", margin, 0, MAX_REFERENCE)
+        lo, n = self.window(flank)
+        lo, n = lo.long(), n.long()
+        rs, re, qs, qe = (t.long() for t in (self.ref_start, self.ref_end, self.query_start, self.query_end))
+        rev = self.strand == 1
+        d0 = qs - torch.where(rev, lo + n - re, rs - lo)
+        d1 = qe - torch.where(rev, lo + n - rs, re - lo)
+        zero = torch.zeros_like(d0)
+        dlo = torch.where(self.mapped, torch.minimum(d0, d1) - margin, zero)
+        dhi = torch.where(self.mapped, torch.maximum(d0, d1) + margin, zero)
+        dlo, dhi = _clamp_band(dlo, dhi, max_band)
+        return dlo.int(), dhi.int()
+
     def mapq(self):
         """[B] float32 on the device: minimap2's formula 40 (1 - runner_up / score) min(1, n_anchors / 10) ln(score / 16), clamped to
         [0, 60]; a missing runner-up counts as 0; 0 where unmapped.  A CHOICE taken over from minimap2, not calibrated here."""
