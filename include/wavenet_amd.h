@@ -1173,6 +1173,59 @@ int wn_banded_align(const int* ref, long long ref_stride, const int* ref_lengths
                     signed char* status, int* edge_hits /* may be NULL */, void* workspace, size_t workspace_bytes,
                     int* bad /* may be NULL */, wn_stream_t stream);
 
+/* ---- CIGAR runs from op rows and back (wavenet_speech_amd.cigar_runs / cigar_ops): what SAM and BAM carry
+ * of an alignment, written from and turned into the op rows of wn_pair_align.  Ops, walk index w, i, j, rev, the header and the
+ * column validity are those of wn_pileup (csrc/wn_opscan.h); the window condition is wn_pileup's, lo >= 0 and lo + n_ref <= R.
+ * first / last are the first and last aligned (op 1 or 2) walk index.  The walk reverses strand 1, so everything below is in
+ * FORWARD reference orientation.
+ *   wn_cigar_encode: op row -> runs.  ops .. query_lengths, keep, batch, max_query_len, max_ops, reference_len: as wn_pileup takes
+ *   them (the query labels are not needed).  With i(w), j(w) the labels consumed before walk index w:
+ *     pos = lo + i(first), 0-based;  ref_span = i(last) - i(first) + 1;  clip_front = j(first);  clip_back = n_query - j(last) - 1;
+ *     nm = the columns of [first, last] with op 2, 3 or 4.
+ *   Columns outside [first, last] enter nothing, as with wn_pileup: an op 4 there is soft-clipped, an op 3 only moves pos or
+ *   shortens the span.  The runs, in order: (S, clip_front) if clip_front > 0; the run-length encoding of the columns first..last
+ *   by class, op 1 -> '=', op 2 -> 'X' (both 'M' with eqx == 0), op 4 -> 'I', op 3 -> 'D'; (S, clip_back) if clip_back > 0.
+ *     cigar    row b at cigar + b * cigar_stride (elements): one uint32 per run, len << 4 | code, BAM's codes M 0, I 1, D 2, N 3,
+ *              S 4, H 5, P 6, = 7, X 8; n_cigar[b] runs, zero behind them up to max_cigar in every outcome
+ *     fields   [B][5] int32: pos, ref_span, clip_front, clip_back, nm
+ *     used     [B] int8: 1 written.  0 skipped: strand < 0, ref_lengths == 0, keep[b] == 0, or no aligned column; n_cigar 0, pos
+ *              -1, the other fields 0.  -1 bad: exactly the rows wn_pileup calls bad for the same ops, lengths, strand and window
+ *              (there is no qual); fields as for skipped; counted once in *bad (DEVICE int, caller-zeroed, may be NULL).  -2 the
+ *              row needs more than max_cigar runs: nothing of it is written (a row is never truncated), n_cigar[b] holds the
+ *              number needed, the fields are filled; counted once in *bad.
+ *   A row of n_query labels has at most 2 n_query + 3 runs: deletion runs are separated by query-consuming columns.
+ *   wn_cigar_decode: runs -> op row.  pos, strand [B]; reference [reference_len] labels; query row b at query + b * query_stride in
+ *   READ orientation with query_lengths[b] labels.  The runs are walked in forward orientation: M, = and X emit one column per
+ *   base, op 1 if reference[pos + i] equals the forward query label (on strand 1: 5 - v of a label v in 1..4, other labels kept,
+ *   taken at n_query - 1 - j), else op 2; I and S emit op 4; D emits op 3; H, P and a run of length 0 emit nothing.  The row is
+ *   written in READ orientation (reversed on strand 1), zero behind ops_len up to max_ops; ref_lengths = the reference labels
+ *   consumed, stats [B][4] = matches, mismatches, gap columns, length as wn_pair_align counts them; the window's lo is pos.  The
+ *   result is an op row as wn_pair_align writes one: it consumes exactly ref_lengths and query_lengths labels.
+ *     used     [B] int8: 1 written.  0 skipped: strand < 0 or n_cigar == 0; ops_len, ref_lengths and stats 0.  -1 bad: strand > 1,
+ *              n_cigar outside [0, max_cigar], pos < 0, query_lengths outside [0, max_query_len] (nothing else of such a read is
+ *              looked at); a code above 8 or code N; more than max_ops columns; no reference label consumed; pos + the labels
+ *              consumed > reference_len; the query labels consumed differ from query_lengths; with strict an '=' column whose
+ *              labels differ or an 'X' column whose labels are equal.  Then ops_len 0, ref_lengths 0, stats -1, the row zero,
+ *              counted once in *bad.
+ *   No bad value is used as an index; a run's length enters the sums clamped to max_ops + 1 and the sums saturate, so nothing
+ *   wraps.  workspace: wn_cigar_decode_workspace_bytes = round_up(batch * 3 * max_cigar * 4, 16), the scanned offsets of the runs
+ *   (0 for a bad or unsupported shape), 16-byte aligned.
+ * One launch each, one workgroup per read, nothing is read back.  Checked on the host in this order.  WN_ERR_BAD_SHAPE: batch,
+ * max_query_len, max_ops, reference_len or max_cigar < 1, a negative stride, eqx / strict not 0 or 1.  WN_ERR_UNSUPPORTED: batch >
+ * 65535, max_query_len > 8192, max_ops > 65535 + 8192, reference_len > 2^26, max_cigar > 65535 (BAM's own limit).  WN_ERR_NULL:
+ * any pointer but keep and bad.  WN_ERR_WORKSPACE (wn_cigar_decode): workspace_bytes too small or the workspace misaligned. */
+int wn_cigar_encode(const unsigned char* ops, long long ops_stride, const int* ops_len, const int* lo, const int* ref_lengths,
+                    const int* strand, const int* query_lengths, const unsigned char* keep /* may be NULL */, int batch,
+                    int max_query_len, int max_ops, int reference_len, int eqx, int max_cigar, unsigned* cigar,
+                    long long cigar_stride, int* n_cigar, int* fields /* [B][5]: pos, ref_span, clip_front, clip_back, nm */,
+                    signed char* used, int* bad /* may be NULL */, wn_stream_t stream);
+size_t wn_cigar_decode_workspace_bytes(int batch, int max_cigar);
+int wn_cigar_decode(const unsigned* cigar, long long cigar_stride, const int* n_cigar, const int* pos, const int* strand,
+                    const int* reference, int reference_len, const int* query, long long query_stride, const int* query_lengths,
+                    int batch, int max_cigar, int max_query_len, int max_ops, int strict, unsigned char* ops, long long ops_stride,
+                    int* ops_len, int* ref_lengths, int* stats, signed char* used, void* workspace, size_t workspace_bytes,
+                    int* bad /* may be NULL */, wn_stream_t stream);
+
 /* ======================================================================================================================
  * Half-precision-MFMA modes of the same path (opt-in; the entry points above stay exact fp32).
  *

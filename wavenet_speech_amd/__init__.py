@@ -38,6 +38,8 @@ from .phase import (Haplotags, PhasedRecord, PhaseLinks, PhaseSites, Phasing, ha
                     phased_records, vcf_phased_records)
 from .realign import (HaplotypeCalls, HaplotypeWindows, Realignment, haplotype_calls, haplotype_windows, lift_alignment,  # noqa: F401
                       realign)
+from .sam import (CigarAlignment, CigarRows, SamReads, cigar_ops, cigar_runs, cigar_strings, md_strings, parse_sam, sam_header,  # noqa: F401
+                  sam_records)
 from .mapping import MapReference, SignalMapping, join_strands, map_reference, signal_map  # noqa: F401
 from .synthetic import RaggedReads, RawGaussianModelLoader, ragged_reads  # noqa: F401
 

@@ -397,11 +397,13 @@ def map_reads(labels, lengths, index, max_occ=8, anchors_per_read=4096, h=64, ma
     return _chain(what, _seed(what, labels, lengths, index, max_occ, cap, chunk, report=False), args, bool(want_pred))
 
 
-def paf_records(names, lengths, mapping, ref_name, alignment=None, ref_length=None):
+def paf_records(names, lengths, mapping, ref_name, alignment=None, ref_length=None, cigars=None):
     """host helper: one PAF line per MAPPED read (unmapped reads have none, as with minimap2), "\\n"-terminated: query name, length,
     start, end, strand, reference name, length, start, end, matches, alignment length, mapping quality.  Columns 10 and 11 come from
     a PairwiseAlignment of the mapped stretches (matches, length) when one is given; otherwise they are an APPROXIMATION:
-    min(n_anchors k, query span) and the longer of the two spans.  ref_length: needed only for a mapping without a reference."""
+    min(n_anchors k, query span) and the longer of the two spans.  ref_length: needed only for a mapping without a reference.
+    cigars: the CigarRows of cigar_runs (sam.py) for the same reads; a line whose row was written then gains NM:i: and cg:Z:, the
+    runs without the soft clips (PAF has none); a row with used < 0 raises.  Without it every line is as before."""
     what = "paf_records"
     names = [str(n) for n in names]
     ns = [int(n) for n in torch.as_tensor(lengths).cpu().reshape(-1).tolist()]
@@ -420,6 +422,16 @@ def paf_records(names, lengths, mapping, ref_name, alignment=None, ref_length=No
         nmatch, alen = alignment.matches.cpu().tolist(), alignment.length.cpu().tolist()
         if len(nmatch) != len(names):
             raise ValueError("wavenet_speech_amd.%s: the alignment holds %d rows for %d reads" % (what, len(nmatch), len(names)))
+    tags = [""] * len(names)
+    if cigars is not None:
+        from . import sam
+        runs, rows = sam._host_rows(cigars, what)
+        if len(runs) != len(names):
+            raise ValueError("wavenet_speech_amd.%s: the cigars hold %d rows for %d reads" % (what, len(runs), len(names)))
+        if any(u < 0 and s >= 0 for u, s in zip(rows[6], cols[0])):
+            raise ValueError("wavenet_speech_amd.%s: a mapped read has no CIGAR (used < 0)" % what)
+        tags = ["\tNM:i:%d\tcg:Z:%s" % (nm, sam._cigar_text([r for r in run if r[1] != 4], cigars.eqx)) if u == 1 else ""
+                for run, nm, u in zip(runs, rows[5], rows[6])]
     out = []
     for b, name in enumerate(names):
         s, r0, r1, q0, q1, na = (c[b] for c in cols)
@@ -429,6 +441,6 @@ def paf_records(names, lengths, mapping, ref_name, alignment=None, ref_length=No
             m, a = int(nmatch[b]), int(alen[b])
         else:
             m, a = min(na * mapping.k, q1 - q0), max(q1 - q0, r1 - r0)
-        out.append("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % (name, ns[b], q0, q1, "+-"[s], ref_name, int(ref_length), r0, r1, m, a,
-                                                                      int(math.floor(mapq[b] + 0.5))))
+        out.append("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d%s\n" % (name, ns[b], q0, q1, "+-"[s], ref_name, int(ref_length), r0, r1, m, a,
+                                                                        int(math.floor(mapq[b] + 0.5)), tags[b]))
     return out
